@@ -15,11 +15,15 @@ inputs: it warms the allocator pools and, when the committed GEMM tile table lac
 runs K/20 full passes.  Weights are seeded random tensors of the SD-1.5 / AutoencoderKL architecture, inputs synthetic (no network); all
 inputs are resident in HBM before the timed region.  Prints ONE JSON line on rank 0.
 
-Behind the timed pass, untimed: a PROFILED pass of `--profile_steps` denoising steps on the same clip (HIP events around every head_dim-40 flash launch,
-every GEMM / conv call and every VidToMe match call -> `roofline`, `roofline_gemm`, `roofline_match`); the flash kernel alone on its largest launch
-shape (`roofline.alone`); at N = 1 the extras (`configs1`, `configs3`, `producers`, stage 2 at realistic track lengths) and the CPU baseline (the
-oracle on SURVEY 8(d)'s full sample, ~4 minutes of host time; `--cpu_bounded` for a ~30 s sample).  At N > 1 the line adds `per_rank` (phase seconds
-min / max over ranks, seconds and bytes per collective).
+A plain run sets up, warms up, times the K steps and prints the line (`phase_seconds`, `roofline_path2` and, at N > 1, `per_rank` -- phase
+seconds min / max over ranks, seconds and bytes per collective -- come from the timed pass itself).  `--dump-outputs DIR` writes what the
+timed pass returned in its last pass as .npy files (dump_outputs).
+
+`--full` adds, behind the timed pass and untimed: a PROFILED pass of `--profile_steps` denoising steps on the same clip (HIP events around every
+head_dim-40 flash launch, every GEMM / conv call and every VidToMe match call -> `roofline`, `roofline_gemm`, `roofline_match`); the flash kernel
+alone on its largest launch shape (`roofline.alone`); at N = 1 the extras (`configs1`, `configs3`, `producers`, stage 2 at realistic track lengths)
+and the CPU baseline (the oracle on SURVEY 8(d)'s full sample, ~4 minutes of host time; `--cpu_bounded` for a ~30 s sample).  The options
+below that shape those figures act only with `--full`.
 """
 import argparse
 import ctypes
@@ -62,16 +66,86 @@ def parse():
     ap.add_argument("--exclusive", action="store_true", help="one extra untimed pass with the matching chain on the main stream (flash kernel alone on the GPU)")
     ap.add_argument("--no_multi_axis", action="store_true")
     ap.add_argument("--save_gemm_table", type=str, default=None, help="write the GEMM tile table after the run (to refresh tc_light_amd/gemm_tune_gfx950.txt)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="also measure everything reported beside the metric: profiled pass (roofline*), flash alone, "
+                    "--exclusive, the extras and the CPU baseline (--profile_steps, --profile_in_pass, --exclusive, --no_extras, --no_cpu_baseline and "
+                    "--cpu_bounded act only with it)")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR", default=None,
+                    help="write what the timed pass returned in its last pass to DIR/<name>.npy (float32 / float64, < 64 MB in all)")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
 
 
-def synth_inputs(n, H, W, lo, hi, dev, seed=12345):
+def _workers():
+    """Host threads for the input synthesis: the CPUs this process may run on, at most 16."""
+    return max(1, min(16, len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)))
+
+
+def video_clip(n, h, w, seed=12345, shift=(1.5, 0.5)):
+    """tests/synth.py::video_clip's frames / past_flows / masks, bit for bit (tests/test_bench_inputs_cpu.py), in a fraction of its time: the
+    random draws are made in the same order on this thread (numpy releases the GIL while it fills), the per-frame arithmetic runs on a thread
+    pool beside them, and the `edited` frames the bench never reads are not formed (their draws are made and dropped)."""
+    import synth
+    from concurrent.futures import ThreadPoolExecutor
+    rng = np.random.default_rng(seed)
+    pad = int(max(abs(shift[0]), abs(shift[1])) * n) + 4
+    base = synth._smooth(rng, (3, h + 2 * pad, w + 2 * pad), passes=4)
+    base = (base - base.min()) / (base.max() - base.min())
+    frames = np.empty((n, 3, h, w), np.float32)
+    flow = np.empty((n, 2, h, w), np.float32)
+    m = np.empty((n, 1, h, w), np.float32)
+
+    def frame(k):
+        dx, dy = shift[0] * k, shift[1] * k
+        x0, y0 = int(np.floor(dx)), int(np.floor(dy))
+        fx, fy = dx - x0, dy - y0
+
+        def crop(ox, oy):
+            return base[:, pad + y0 + oy: pad + y0 + oy + h, pad + x0 + ox: pad + x0 + ox + w]
+        frames[k] = ((1 - fx) * (1 - fy) * crop(0, 0) + fx * (1 - fy) * crop(1, 0)
+                     + (1 - fx) * fy * crop(0, 1) + fx * fy * crop(1, 1))
+
+    def flow_k(k, z):
+        flow[k, 0] = shift[0]
+        flow[k, 1] = shift[1]
+        flow[k] += 0.05 * z.astype(np.float32)
+        if k == 0:
+            flow[0] = 0
+
+    def smooth_k(k, x):                      # synth._smooth's 6 passes: the blur never crosses frames
+        for _ in range(6):
+            x = (np.roll(x, 1, -1) + x + np.roll(x, -1, -1)) / 3
+            x = (np.roll(x, 1, -2) + x + np.roll(x, -1, -2)) / 3
+        m[k] = x
+
+    def mask_k(k, q, u):
+        m[k] = np.clip((m[k] > q).astype(np.float32) * (0.9 + 0.1 * u), 0, 1)
+
+    with ThreadPoolExecutor(_workers()) as ex:
+        jobs = [ex.submit(frame, k) for k in range(n)]
+        rng.standard_normal(2 * n * 3)                        # gain and bias of `edited`
+        buf = np.empty(3 * h * w)
+        for _ in range(n):                                    # the noise of `edited`
+            rng.standard_normal(out=buf)
+        jobs += [ex.submit(flow_k, k, rng.standard_normal((2, h, w))) for k in range(n)]
+        blur = [ex.submit(smooth_k, k, rng.random((1, h, w), dtype=np.float32)) for k in range(n)]
+        jitter = [rng.random((1, h, w), dtype=np.float32) for _ in range(n)]
+        for j in blur:
+            j.result()
+        q = np.quantile(m, 0.1)
+        jobs += [ex.submit(mask_k, k, q, jitter[k]) for k in range(n)]
+        for j in jobs:
+            j.result()
+    return dict(frames=torch.from_numpy(frames), past_flows=torch.from_numpy(flow), masks=torch.from_numpy(m))
+
+
+def synth_inputs(n, H, W, lo, hi, dev, seed=12345, clip=None):
     """translated low-pass frames, analytic backward flow + noise, soft mask; the track ids (unq_inv, K) come from the engine's
     own get_flowid on those frames / flows / masks (tc_light_amd/flow_ids.py <- utils/flow_utils.py:56-93), as SURVEY 8(d) config 5 asks --
-    untimed input preparation, like the flows themselves."""
-    import synth
+    untimed input preparation, like the flows themselves.  clip: video_clip(n, H, W, seed) when the caller has made it already."""
     from tc_light_amd import flow_ids
-    d = synth.video_clip(n, H, W, seed=seed)
+    d = clip if clip is not None else video_clip(n, H, W, seed=seed)
     past, masks = d["past_flows"].to(dev), d["masks"].to(dev)
     fwd = -past.roll(-1, 0)                                    # forward flow of frame i = minus the backward flow of frame i+1 (pure translation)
     fwd[-1] = 0
@@ -423,6 +497,25 @@ def lib_size():
     return lib().tcl_gemm_tune_size()
 
 
+def dump_outputs(dirname, out, info, frames_bytes=40 << 20, sample=1 << 20):
+    """--dump-outputs: what the timed pass handed its caller in its last pass, for comparing two builds output for output (same arguments ->
+    same inputs).  relit_frames.npy: the relit frames 0, N/2 and N-1 (float32 [F,3,H,W], as many of them as fit `frames_bytes`);
+    relit_sample.npy / relit_sample_index.npy: a fixed seeded sample of `sample` elements of the whole relit clip and their flat indices into
+    [N,3,H,W] (float32 / float64); losses_exposure.npy / losses_unique.npy: the two optimiser stages' losses (float64).  Under 64 MB in all."""
+    os.makedirs(dirname, exist_ok=True)
+    save = lambda name, v: np.save(os.path.join(dirname, name + ".npy"), v)
+    n = out.shape[0]
+    pick = sorted({0, n // 2, n - 1})[:frames_bytes // (out[0].numel() * 4)]
+    if pick:
+        save("relit_frames", out[pick].float().cpu().numpy())
+    idx = np.unique(np.random.default_rng(0).integers(0, out.numel(), min(sample, out.numel())))
+    save("relit_sample", out.reshape(-1)[torch.from_numpy(idx).to(out.device)].float().cpu().numpy())
+    save("relit_sample_index", idx.astype(np.float64))
+    for key in ("losses_exposure", "losses_unique"):
+        if info.get(key) is not None:
+            save(key, torch.as_tensor(info[key]).detach().double().cpu().numpy())
+
+
 def _free_port():
     import socket
     so = socket.socket(); so.bind(("127.0.0.1", 0)); p = so.getsockname()[1]; so.close()
@@ -493,23 +586,35 @@ def main():
     from tc_light_amd.vae import VAEEngine
     from tc_light_amd.vidtome import VidToMe
     d = Dist(rank, world, timed=world > 1)
+
+    def note(msg):                 # progress on stderr (stdout carries the result line alone): a --full run takes minutes
+        if rank == 0:
+            print(f"[bench] {msg}", file=sys.stderr, flush=True)
     d.barrier()
 
     n_total, H, W = a.frames, a.height, a.width
-    passes = a.steps // BASE_STEPS if (a.steps % BASE_STEPS == 0 and a.steps > 0) else 1
+    passes = a.steps // BASE_STEPS if a.steps % BASE_STEPS == 0 else 1
     n_steps = BASE_STEPS if a.steps % BASE_STEPS == 0 else a.steps
     base = dict(alpha_t=0.0 if a.no_multi_axis else 0.01, final_factor_t=0.01, batch_size=16, seed=12345)
     cfg = dict(base, n_timesteps=n_steps, epochs_exposure=a.epochs_exposure, epochs=a.epochs)
-    sd_unet = sd15.random_state_dict(sd15.unet_param_shapes(), seed=1)
-    sd_vae = sd15.random_state_dict(sd15.vae_param_shapes(), seed=2)
-    unet = UNetEngine(sd_unet, dev, VidToMe(dev, seed=12345))
-    vae = VAEEngine(sd_vae, dev)
-    table_entries = int(lib().tcl_gemm_tune_size())
-    gen = Generator(unet, vae, cfg, dist=d)
-    lo, hi = d.range(n_total)
+    # host-side setup on threads beside each other (the clip's draws and the two weight sets come from independent generators): what the
+    # pass receives is the same as when they are made one after the other
+    from concurrent.futures import ThreadPoolExecutor
     t_setup = time.perf_counter()
-    frames, flows, masks, inv, K = synth_inputs(n_total, H, W, lo, hi, dev)
+    with ThreadPoolExecutor(3) as pool:
+        clip = pool.submit(video_clip, n_total, H, W)
+        sd_unet = pool.submit(sd15.random_state_dict, sd15.unet_param_shapes(), 1)
+        sd_vae = pool.submit(sd15.random_state_dict, sd15.vae_param_shapes(), 2)
+        sd_unet, sd_vae = sd_unet.result(), sd_vae.result()
+        unet = UNetEngine(sd_unet, dev, VidToMe(dev, seed=12345))
+        vae = VAEEngine(sd_vae, dev)
+        table_entries = int(lib().tcl_gemm_tune_size())
+        gen = Generator(unet, vae, cfg, dist=d)
+        lo, hi = d.range(n_total)
+        frames, flows, masks, inv, K = synth_inputs(n_total, H, W, lo, hi, dev, clip=clip.result())
+        del clip
     t_setup = time.perf_counter() - t_setup
+    note(f"setup {t_setup:.1f} s")
     g = np.random.default_rng(5)
     conds = torch.from_numpy(g.standard_normal((2, 154, 768)).astype(np.float32)).to(dev).half()     # 2 x 77-token chunks (A4)
     conds_t = torch.from_numpy(g.standard_normal((2, 77, 768)).astype(np.float32)).to(dev).half()
@@ -535,28 +640,36 @@ def main():
                 prof.append((ms.value, fl.value, cnt.value))
         return out, info, prof
 
+    t_warm = time.perf_counter()
     if a.warmup > 0:       # untimed: W denoising steps + one epoch of each optimiser stage on the same inputs
         one_pass(Generator(unet, vae, dict(base, n_timesteps=a.warmup, epochs_exposure=1, epochs=1), dist=d))
+        torch.cuda.synchronize()
+    t_warm = time.perf_counter() - t_warm
+    note(f"warm-up {t_warm:.1f} s")
     d.reset_stats()
     d.barrier(); torch.cuda.synchronize()
     t0 = time.perf_counter()
     info = prof = None
     for s in range(passes):
-        out, info, p = one_pass(gen, profile=(a.profile_in_pass and s == 0))
+        out, info, p = one_pass(gen, profile=(a.full and a.profile_in_pass and s == 0))
         prof = prof or p
     d.barrier(); torch.cuda.synchronize()
     dt = d.max_float(time.perf_counter() - t0, dev)
+    note(f"timed {passes * n_steps} steps {dt:.1f} s")
     assert torch.isfinite(out).all(), "non-finite output"
     flops_pass, flops_exec = unet.flops, unet.flops_executed
     coll = {k: dict(v) for k, v in d.collect_stats().items()}       # (event pairs recorded inside the pass, resolved here: no synchronise in the timed region)
     if a.save_gemm_table and rank == 0:
         lib().tcl_gemm_tune_save(a.save_gemm_table)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, out, info)
 
     # The profiled pass: the same clip, same shapes, `--profile_steps` denoising steps and one epoch of each stage, UNTIMED, with HIP events around
     # every launch of the three matrix-pipe consumers (round 3 recorded the flash events inside the timed pass: 59k event records in the
     # measured region).  Every rank runs it (the collectives need all of them); rank 0's numbers are reported.
     prof_how = "HIP events around every launch on the launch stream, timed pass 0, rank 0 (tcl_flash_profile_*)"
-    if not a.profile_in_pass and a.profile_steps > 0:
+    if a.full and not a.profile_in_pass and a.profile_steps > 0:
+        note("profiled pass")
         _, _, prof = one_pass(Generator(unet, vae, dict(base, n_timesteps=a.profile_steps, epochs_exposure=1, epochs=1), dist=d), profile=True)
         prof_how = (f"HIP events around every launch on the launch stream (in-library), rank 0, in an UNTIMED profiled pass run right behind the timed one: "
                     f"same clip and shapes, {a.profile_steps} denoising steps, matching chain on its side stream as in the timed pass")
@@ -565,7 +678,8 @@ def main():
     # In the timed region the VidToMe matching chain runs on a second stream beside the attention kernels, so the launch
     # durations above are those of a kernel SHARING the GPU.  --exclusive: one extra untimed pass with the chain back on the main stream.
     prof_ex = None
-    if world == 1 and a.exclusive:
+    if world == 1 and a.full and a.exclusive:
+        note("exclusive pass")
         os.environ["TCL_TOME_STREAM"] = "0"
         try:
             _, _, prof_ex = one_pass(gen, profile=True)
@@ -606,7 +720,7 @@ def main():
                        "gemm_tile_table_entries_loaded": table_entries,
                        "rccl_version": ".".join(str(v) for v in torch.cuda.nccl.version()) if hasattr(torch.cuda, "nccl") else None},
             "phase_seconds": {k: round(v, 3) for k, v in info["timing"].items()},
-            "pass_seconds": dt / passes, "input_synthesis_seconds": round(t_setup, 1),
+            "pass_seconds": dt / passes, "setup_seconds": round(t_setup, 1), "warmup_seconds": round(t_warm, 1),     # (setup: weights, engines, inputs)
             "max_memory_allocated_MiB": round(info["max_memory_allocated"]),
             "roofline": {"bound": "mfma", "kernel": "k_flash<40,...> (head_dim 40 attention: self-attention over VidToMe-merged tokens + text cross-attention)",
                          "achieved": ach, "peak": MFMA_F16_DENSE_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": ach / MFMA_F16_DENSE_PEAK_TFLOPS,
@@ -628,6 +742,8 @@ def main():
                                   "side-stream kernels); the kernel-time basis (rocprofv3 --kernel-trace of the same command) is profiles/r5_bench_kernel_stats.txt -- "
                                   "for this kernel the two agree to 1 %"},
         }
+        if not a.full:
+            del res["roofline"]                       # its figures come from the profiled pass, a run of its own (--full)
         if prof and len(prof) > 2:
             # the other two matrix-pipe consumers of the denoise loop, same profiled pass, same units (the 48 PFLOP of VidToMe score
             # GEMMs were in no roofline figure; the GEMM family had none of its own)
@@ -703,18 +819,21 @@ def main():
             ax = prof_ex[0][1] / (prof_ex[0][0] * 1e-3) / 1e12
             res["roofline"]["exclusive"] = {"achieved": ax, "frac": ax / MFMA_F16_DENSE_PEAK_TFLOPS, "avg_launch_ms": prof_ex[0][0] / max(prof_ex[0][2], 1),
                                             "how": "same launches in one extra untimed pass with the matching chain on the main stream (TCL_TOME_STREAM=0)"}
-        if world == 1 and not a.no_extras:
+        if world == 1 and a.full and not a.no_extras:
+            note("extra: stage 2 at realistic track lengths")
             del out
             try:                                               # path 2 at a codebook with realistic track lengths (extra key)
                 res["roofline_path2"]["realistic_codebook"] = stage2_realistic_codebook(frames, flows, masks, cfg, dev)
             except Exception as e:
                 res.setdefault("roofline_path2", {})["realistic_codebook"] = {"error": repr(e)}
+            note("extra: producers")
             try:                                               # the SURVEY 8(f) rows, measured beside the metric (never part of `value`)
                 res["producers"] = producer_timings(frames, dev, flows, masks)
             except Exception as e:
                 res["producers"] = {"error": repr(e)}
             del frames, flows, masks, inv
             torch.cuda.empty_cache()
+            note("extra: configs[1]")
             try:                                               # BASELINE.json configs[1] (round 1's bench workload), kept as an extra key
                 f2, fl2, m2, i2, k2 = synth_inputs(30, 720, 960, 0, 30, dev)
                 g2 = Generator(unet, vae, dict(base, n_timesteps=BASE_STEPS, epochs_exposure=35, epochs=70), dist=d)
@@ -727,11 +846,13 @@ def main():
                 del f2, fl2, m2, i2, g2
             except Exception as e:
                 res["configs1"] = {"error": repr(e)}
+            note("extra: configs[3]")
             try:                                               # BASELINE.json configs[3]: foreground / background mode, VidToMe 0.9 / 0.8
                 res["configs3"] = config3_pass(unet, vae, base, conds, conds_t, d, dev)
             except Exception as e:
                 res["configs3"] = {"error": repr(e)}
-        if world == 1 and not a.no_cpu_baseline:
+        if world == 1 and a.full and not a.no_cpu_baseline:
+            note("CPU baseline")
             try:
                 res["cpu_baseline"] = cpu_baseline(sd_unet, H, W, n_total, flops_pass, cfg, full=not a.cpu_bounded)
             except Exception as e:  # the baseline must never sink the measurement

@@ -19,7 +19,7 @@ def test_bench_gpus2_launches_two_ranks_itself():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(TCL_DIST_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--frames", "16", "--height", "256", "--width", "256", "--steps", "2",
-           "--warmup", "0", "--epochs", "2", "--epochs_exposure", "2", "--no_cpu_baseline", "--no_extras", "--profile_steps", "1"]
+           "--warmup", "0", "--epochs", "2", "--epochs_exposure", "2", "--full", "--no_cpu_baseline", "--no_extras", "--profile_steps", "1"]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=1500)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]

@@ -7,7 +7,7 @@ OUT=$GRAFT_REPO_ROOT/gpurun_out/profiles_r6
 mkdir -p $OUT
 cd $GRAFT_REPO_ROOT
 if [ "$1" != traffic_only ]; then
-timeout 1500 python bench.py > $OUT/bench_final_run.json 2> $OUT/bench_final_run.err; tail -c 400 $OUT/bench_final_run.json; echo
+timeout 1500 python bench.py --full > $OUT/bench_final_run.json 2> $OUT/bench_final_run.err; tail -c 400 $OUT/bench_final_run.json; echo
 cd /tmp && export TMPDIR=/tmp
 timeout 1500 rocprofv3 --kernel-trace --stats -d /tmp/kt -o kt -- python $GRAFT_REPO_ROOT/bench.py --no_cpu_baseline --no_extras --profile_steps 0 > $OUT/bench_under_rocprof.json 2> /dev/null
 python $GRAFT_REPO_ROOT/tools/prof_summary.py /tmp/kt 70 --timed-pass > $OUT/bench_kernel_stats.txt; rm -rf /tmp/kt

@@ -7,7 +7,7 @@ O=gpurun_out/profiles_r6; mkdir -p $O
 for t in 4 2 4 2; do echo "== TCL_TOME320=$t"; TCL_TOME320=$t python tools/micro/bench_tome.py 2>/dev/null | grep "C=320"; done > $O/ab_tome_x2_alone.txt 2>&1
 grep -v "^+" $O/ab_tome_x2_alone.txt
 for i in 1 2; do for t in 4 2; do
-  TCL_TOME320=$t timeout 900 python bench.py --frames 60 --no_cpu_baseline --no_extras --profile_steps 1 2>/dev/null | python -c "
+  TCL_TOME320=$t timeout 900 python bench.py --frames 60 --full --no_cpu_baseline --no_extras --profile_steps 1 2>/dev/null | python -c "
 import json,sys
 r=json.loads([l for l in sys.stdin if l.startswith('{')][0]); print('TCL_TOME320=$t', round(r['value'],4), r['phase_seconds'], 'flash', round(r['roofline']['achieved']), 'match', round(r['roofline_match']['achieved']), 'gemm', round(r['roofline_gemm']['achieved']))"
 done; done > $O/ab_tome_x2_inpass.txt 2>&1
