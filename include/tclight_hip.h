@@ -352,6 +352,24 @@ int tcl_rows_f16_to_nchw_f32(const void* x, float* y, int B, int Cs, int P, int 
 int tcl_axpy_f16(const void* a, const void* b, float s, void* y, long n, hipStream_t st);
 int tcl_upsample_flow_f32(const float* flow, const void* mask, int ldm, float mask_scale, float* up, int B, int h, int w, hipStream_t st);
 
+
+/* ---- RAFT (utils/evaluation/core/raft.py:73-131, update.py:33-136, extractor.py:139-172) -- the update block and the fnet stem; csrc/raft.hip.
+ * tcl_raft_sepconv_f16: one SepConvGRU convolution group (update.py:37-56: convz/convr/convq 1 and 2, 1x5 pad (0,2) when vertical = 0, 5x1 pad (2,0)
+ *   when vertical = 1) as an implicit GEMM over x = [src0 | src1] (f16 rows [B*H*W, 128] each; C1 = 0: src1 absent, else 128), W [N, 5*(128+C1)] f16
+ *   with column tap*(128+C1) + source*128 + c.  mode 0: out32 [M,N] f32 = conv + bias (the context term of the GRU input, computed once per pair);
+ *   mode 1 (N = 256, [convz | convr]): z [M,128] f32 = sigmoid(conv + pbias[:, :128]), rh [M,128] f16 = sigmoid(conv + pbias[:, 128:]) * h (update.py:45-46);
+ *   mode 2 (N = 128, convq over [rh | x]): h <- (1 - z) h + z tanh(conv + pbias) in place, f32 blend, one rounding (update.py:47-48). */
+int tcl_raft_sepconv_f16(const void* src0, const void* src1, int C1, const void* w, const float* bias, const float* pbias, float* out32, float* z,
+                         void* rh, void* h, int B, int H, int W, int N, int vertical, int mode, hipStream_t st);
+/* tcl_raft_convf1_f16: BasicMotionEncoder.convf1 + ReLU (update.py:78,85) on flow = coords1 - coords0 read from coords1 [B,2,H,W] f32 NCHW (coords0 is
+ *   the pixel grid, utils.py:83-86) -> f16 rows [B*H*W, ldo], channels 0..127; w_t [98,128] f32, row c*49 + ky*7 + kx. */
+int tcl_raft_convf1_f16(const float* coords1, const float* w_t, const float* bias, void* y, int ldo, int B, int H, int W, hipStream_t st);
+/* tcl_conv7x7s2_instnorm_f16: the instance-norm encoder's stem (extractor.py:139,164-166: conv1 7x7 stride 2 -> InstanceNorm2d(64) -> ReLU) with the
+ *   convolution kept in f32 up to the normalisation (two-pass f32 statistics): x [B,3,H,W] f32 NCHW -> y [B,Ho,Wo,64] f16 NHWC; w_t as
+ *   tcl_conv7x7s2_c3_f16.  ws: tcl_stem_instnorm_workspace_bytes(B, H, W) bytes. */
+size_t tcl_stem_instnorm_workspace_bytes(int B, int H, int W);
+int tcl_conv7x7s2_instnorm_f16(const float* x, const float* w_t, const float* bias, void* y, int B, int H, int W, float eps, void* ws, hipStream_t st);
+
 #ifdef __cplusplus
 }
 #endif

@@ -52,7 +52,7 @@ def main(argv=None):
     frames_all = parser.load_video(frame_ids)
     flows = None
     if config.post_opt.apply_opt:
-        # rank 0 owns the flow cache (read, or estimated with MemFlowNet and written: video_dataparser.py:63-110); the other ranks
+        # rank 0 owns the flow cache (read, or estimated with MemFlowNet / RAFT (data.flow_model) and written: video_dataparser.py:63-110); the other ranks
         # receive the tensors.  A failure on rank 0 (e.g. missing MemFlow weights) is announced before the payload so that every
         # rank raises instead of waiting in the broadcast until the collective times out.
         err = None
@@ -60,9 +60,7 @@ def main(argv=None):
             try:
                 flows = parser.load_flow_cache(frame_ids)
                 if flows is None:
-                    from tc_light_amd.memflow import MemFlowEngine
-                    from tc_light_amd.model_utils import load_memflow_state
-                    flows = parser.estimate_and_cache_flow(frames_all, frame_ids, MemFlowEngine(load_memflow_state(models.get("memflow"), allow=ok_random), dev))
+                    flows = parser.estimate_and_cache_flow(frames_all, frame_ids, parser.make_flow_engine(models, ok_random))
             except Exception as e:            # noqa: BLE001 - re-raised below on every rank
                 err = e
         if world > 1:

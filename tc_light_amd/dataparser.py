@@ -260,6 +260,9 @@ def save_loss_curve(loss_list, output_path, title="Loss Curve"):
         pass
 
 
+FLOW_MODELS = ("memflow", "raft")                                # video_dataparser.py:71-74
+
+
 class VideoDataParser:
     def __init__(self, data_config, device):
         self.rgb_path = data_config.get("rgb_path")
@@ -307,12 +310,34 @@ class VideoDataParser:
             out.append(torch.cat([_torch_load(os.path.join(d, f"{fid:04d}.pt")).reshape(1, 2, self.h, self.w) for fid in frame_ids]))
         return out[0].to(self.device), out[1].to(self.device)
 
+    def flow_model_name(self):
+        """'memflow' or 'raft' (video_dataparser.py:71-74 picks the loader by flow_model.lower()); anything else is refused here, where the
+        reference would call None."""
+        m = str(self.flow_model).lower()
+        if m not in FLOW_MODELS:
+            raise ValueError(f"data.flow_model must be one of {FLOW_MODELS}, got {self.flow_model!r}")
+        return m
+
+    def make_flow_engine(self, models, allow_random=False):
+        """The estimator data.flow_model names, with its weights from models.memflow / models.raft (eu.prepare_memflow_model / prepare_raft_model)."""
+        if self.flow_model_name() == "raft":
+            from .model_utils import load_raft_state
+            from .raft import RAFTEngine
+            return RAFTEngine(load_raft_state(models.get("raft"), allow=allow_random), self.device)
+        from .memflow import MemFlowEngine
+        from .model_utils import load_memflow_state
+        return MemFlowEngine(load_memflow_state(models.get("memflow"), allow=allow_random), self.device)
+
     def estimate_and_cache_flow(self, frames, frame_ids, engine, save_flow=True):
-        """load_flow for flow_model 'memflow' (video_dataparser.py:63-110): frames [N,3,h,w] in [0,1] (already processed to the working size)
-        -> (future_flows, past_flows) [N,2,h,w]; saved per frame as [1,2,h,w] tensors under <video>_{future,past}_flow_memflow/%04d.pt
+        """load_flow (video_dataparser.py:63-124) for flow_model 'memflow' or 'raft': frames [N,3,h,w] in [0,1] (already processed to the working
+        size) -> (future_flows, past_flows) [N,2,h,w]; saved per frame as [1,2,h,w] tensors under <video>_{future,past}_flow_<model>/%04d.pt
         (each file is written under a temporary name and renamed, so a reader never sees a partial file)."""
-        from .memflow import estimate_flows
-        fut, past = estimate_flows(engine, frames)
+        if self.flow_model_name() == "raft":
+            from .raft import estimate_flows_raft
+            fut, past = estimate_flows_raft(engine, frames)
+        else:
+            from .memflow import estimate_flows
+            fut, past = estimate_flows(engine, frames)
         if save_flow and self.rgb_path:
             for kind, fl in (("future", fut), ("past", past)):
                 d = self._flow_dir(kind)

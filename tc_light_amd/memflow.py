@@ -187,16 +187,23 @@ class EncoderEngine:
         self.L.tcl_conv3x3_f16(x, w, b, 0, y, B, H, W, ci, co, stride, 1, 0, 0, 3 if relu else 0, stream())
         return y, Ho, Wo
 
+    def _stem(self, img):
+        """conv1 + norm1 + relu1 -> f16 rows [B*h*w, 64], h, w."""
+        B, _, H, W = img.shape
+        h, w = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+        x = torch.empty(B * h * w, 64, dtype=H16, device=self.dev)
+        bn = self.norm == "batch"
+        self.L.tcl_conv7x7s2_c3_f16(img.float().contiguous(), self.stem[0], self.stem[1], x, B, H, W, int(bn), stream())
+        if not bn:
+            x = self._inorm(x, B, h * w, 64, True)
+        return x, h, w
+
     @torch.no_grad()
     def forward(self, img):
         """img [B,3,H,W] f32 (H, W multiples of 8) -> feature map [B*(H/8)*(W/8), 256] f16 (NHWC rows), (H/8, W/8)."""
         L, bn = self.L, self.norm == "batch"
-        B, _, H, W = img.shape
-        h, w = (H - 1) // 2 + 1, (W - 1) // 2 + 1
-        x = torch.empty(B * h * w, 64, dtype=H16, device=self.dev)
-        L.tcl_conv7x7s2_c3_f16(img.float().contiguous(), self.stem[0], self.stem[1], x, B, H, W, int(bn), stream())
-        if not bn:
-            x = self._inorm(x, B, h * w, 64, True)
+        B = img.shape[0]
+        x, h, w = self._stem(img)
         for blk in self.blocks:
             st = blk["stride"]
             y, h2, w2 = self._conv3(x, B, h, w, blk["conv1"], st, bn)

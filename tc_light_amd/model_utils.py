@@ -92,6 +92,16 @@ def load_memflow_state(path=None, seed=4, allow=False):
     return {(k[7:] if k.startswith("module.") else k): v for k, v in raw.items()}
 
 
+def load_raft_state(path=None, seed=5, allow=False):
+    """raft-things.pth (eval_utils.py:178-195): a DataParallel state dict, keys prefixed `module.`; a plain tensor dict, so weights_only=True."""
+    from . import raft
+    if not (path and os.path.exists(path)):
+        _missing("RAFT", path, allow)
+        return raft.seeded_state_dict(seed)
+    raw = torch.load(path, map_location="cpu", weights_only=True)
+    return {(k[7:] if k.startswith("module.") else k): v for k, v in raw.items()}
+
+
 def load_rmbg_state(path=None, seed=3, allow=False):
     """briaai/RMBG-1.4 weights (`model.safetensors` / `model.pth` with the reference module's keys, generate.py:149)."""
     from . import rmbg
