@@ -1,0 +1,60 @@
+"""Evaluate a relit video: `python evaluate.py --output_dir <run output directory> [--eval_cost] [--raft PATH]` (the reference's evaluate.py).
+
+Reads `<output_dir>/config.yaml`, the relit video (output_opt / output, .mp4 or .avi, else output.npy) and the source video (output_gt), computes
+warp-error-ssim on the device (tc_light_amd/evaluate.py: RAFT flows of the source frames, cubic warp, forward-backward mask, SSIM) and writes
+`<output_dir>/result.txt` in the reference's format, one block per prompt of `generation.prompt` (the file keeps the last one, as the reference's
+does).  --eval_cost adds the run's cost figures (z_*).  RAFT weights: `models.raft` of the config or --raft; a missing file is an error unless
+`models.allow_random` / TCL_ALLOW_RANDOM_WEIGHTS=1 allows seeded stand-ins.  CLIP-frame, CLIP-text and PickScore are not computed.
+"""
+import argparse
+import os
+import sys
+
+import yaml
+
+ROOT = os.path.dirname(os.path.abspath(__file__))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--output_dir", type=str, default="workdir")
+    ap.add_argument("--eval_cost", action="store_true")
+    ap.add_argument("--raft", type=str, default=None, help="RAFT checkpoint (raft-things.pth); default: models.raft of config.yaml")
+    ap.add_argument("--batch", type=int, default=4, help="frame pairs per RAFT / metric batch")
+    a = ap.parse_args(argv)
+
+    import torch
+    from tc_light_amd.config_utils import _wrap
+    from tc_light_amd.evaluate import NOT_COMPUTED, cost_scores, find_videos, format_results, read_video_u8, video_name, warp_ssim
+    from tc_light_amd.model_utils import allow_random, load_raft_state
+    from tc_light_amd.raft import RAFTEngine
+
+    with open(os.path.join(a.output_dir, "config.yaml")) as f:
+        config = _wrap(yaml.safe_load(f) or {})
+    if not torch.cuda.is_available():
+        raise RuntimeError("evaluate.py runs its metric on the GPU and found none")
+    models = config.get("models") or {}
+    edit_path, source_path = find_videos(a.output_dir)
+    edit, source = read_video_u8(edit_path), read_video_u8(source_path)
+    print(f"[INFO] edit {edit_path} ({tuple(edit.shape)}), source {source_path} ({tuple(source.shape)})")
+    print(f"[INFO] not computed here: {', '.join(NOT_COMPUTED)} (their CLIP / PickScore models are not part of this project)")
+    engine = RAFTEngine(load_raft_state(a.raft or models.get("raft"), allow=allow_random(models)), "cuda")
+    score, _ = warp_ssim(edit, source, engine, batch=a.batch)
+    scores = {"warp-error-ssim": score}
+    if a.eval_cost:
+        scores.update(cost_scores(config, edit.shape[2], edit.shape[1]))
+    prompts = ((config.get("generation") or {}).get("prompt") or {})
+    prompts = list(prompts.values()) if isinstance(prompts, dict) else [prompts]
+    name = video_name(config)
+    for prompt in prompts or [""]:
+        text = format_results(name, prompt, scores)
+        with open(os.path.join(a.output_dir, "result.txt"), "w") as f:
+            f.write(text)
+        print(text)
+    return scores
+
+
+if __name__ == "__main__":
+    main()

@@ -370,6 +370,18 @@ int tcl_raft_convf1_f16(const float* coords1, const float* w_t, const float* bia
 size_t tcl_stem_instnorm_workspace_bytes(int B, int H, int W);
 int tcl_conv7x7s2_instnorm_f16(const float* x, const float* w_t, const float* bias, void* y, int B, int H, int W, float eps, void* ws, hipStream_t st);
 
+/* ---- warp-error-ssim (evaluate.py:74-78; utils/evaluation/eval_utils.py:265-350: SaveWarpingImage with RAFT flows, warp_flow = cv2.remap INTER_CUBIC /
+ *   BORDER_CONSTANT, compute_fwdbwd_mask's bwd_mask, np.uint8, skimage structural_similarity(channel_axis=2)); csrc/evaluate.hip.
+ * tcl_eval_warp_mask_u8: pairs i = i0 .. i0+B-1 of edit [N,H,W,3] u8 with fwd = fut[i], bwd = past[i+1] (fut / past [N,2,H,W] f32 as
+ *   estimate_flows_raft returns them): cubic remap on cv2's 1/32-pixel grid, mask = |bwd + remap(fwd, bwd)| < 0.5 (|bwd| + |remap(fwd, bwd)|) + 0.5,
+ *   warped [B,H,W,3] u8 = u8(mask ? remap(edit[i], bwd) : 0), target [B,H,W,3] u8 = mask ? edit[i+1] : 0 (u8: truncate toward zero, keep 8 bits).
+ * tcl_eval_ssim_u8: out[b] (f64) = SSIM of x[b] vs y[b] (u8 [B,H,W,3], 7x7 uniform window, sample covariance, data range 255, mean over the interior
+ *   cropped by 3 pixels and the 3 channels); H, W >= 7; ws: tcl_eval_ssim_workspace_bytes(B, H, W) bytes.  Deterministic (fixed-order sums). */
+int tcl_eval_warp_mask_u8(const void* edit, const float* fut, const float* past, void* warped, void* target, int N, int H, int W, int i0, int B,
+                          hipStream_t st);
+size_t tcl_eval_ssim_workspace_bytes(int B, int H, int W);
+int tcl_eval_ssim_u8(const void* x, const void* y, double* out, int B, int H, int W, void* ws, hipStream_t st);
+
 #ifdef __cplusplus
 }
 #endif

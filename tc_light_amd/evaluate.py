@@ -1,0 +1,200 @@
+"""warp-error-ssim, the temporal-consistency figure of the reference's evaluate.py (evaluate.py:1-133, utils/evaluation/eval_utils.py:252-350).
+
+For every pair of neighbouring frames (i, i+1) of a relit video, RAFT estimates the forward and backward flow between the SOURCE frames i and i+1
+(20 iterations, test mode, the frames in 0..255 and replicate-padded to multiples of 8, the flows unpadded); the relit frame i is warped onto
+frame i+1 along the backward flow with a cubic remap, pixels failing the forward-backward consistency check are zeroed in both frames, and the
+score of the pair is the SSIM of the two uint8 images.  The metric is the mean over the pairs.  RAFT is `raft.RAFTEngine` through
+`raft.estimate_flows_raft` (fwd = fut[i], bwd = past[i+1]); the warp, mask and SSIM are the kernels of csrc/evaluate.hip.  CLIP-frame, CLIP-text,
+PickScore and FrameLPIPS are not computed (their models are not part of this project).
+"""
+import math
+import os
+
+import numpy as np
+import torch
+
+from .lib import lib, stream
+from .memflow import _pad8
+from .raft import estimate_flows_raft
+
+EDIT_STEMS = ("output_opt", "output")          # evaluate.py:27: output_opt.mp4 if it exists, else output.mp4
+SOURCE_STEM = "output_gt"                       # evaluate.py:28
+VIDEO_EXTS = (".mp4", ".avi")                   # .avi: what dataparser.save_video writes without an H.264 encoder
+NOT_COMPUTED = ("clip-frame", "clip-text", "pick-score")
+
+
+# ---- the kernels
+def warp_mask_planes(edit_u8, fut, past, i0, B):
+    """Pairs i0 .. i0+B-1 -> (warped, target) uint8 [B,H,W,3] on the device.  edit_u8 [N,H,W,3] uint8, fut / past [N,2,H,W] f32 (device)."""
+    N, H, W = edit_u8.shape[:3]
+    dev = fut.device
+    warped = torch.empty(B, H, W, 3, dtype=torch.uint8, device=dev)
+    target = torch.empty_like(warped)
+    lib().tcl_eval_warp_mask_u8(edit_u8, fut, past, warped, target, N, H, W, i0, B, stream())
+    return warped, target
+
+
+def ssim_u8(x, y):
+    """x, y uint8 [B,H,W,3] on the device -> f64 [B]: skimage structural_similarity(channel_axis=2) with its defaults, per plane pair."""
+    B, H, W = x.shape[:3]
+    if x.shape != y.shape or x.shape[-1] != 3 or x.dtype != torch.uint8 or y.dtype != torch.uint8:
+        raise ValueError(f"ssim_u8 takes two uint8 [B,H,W,3] tensors of one shape, got {tuple(x.shape)} {x.dtype} / {tuple(y.shape)} {y.dtype}")
+    if H < 7 or W < 7:
+        raise ValueError(f"SSIM's 7x7 window needs H, W >= 7, got {H}x{W}")
+    out = torch.empty(B, dtype=torch.float64, device=x.device)
+    L = lib()
+    ws = torch.empty(L.tcl_eval_ssim_workspace_bytes(B, H, W), dtype=torch.uint8, device=x.device)
+    L.tcl_eval_ssim_u8(x.contiguous(), y.contiguous(), out, B, H, W, ws, stream())
+    return out
+
+
+def warp_ssim_from_flows(edit_u8, fut, past, batch=4):
+    """edit_u8 [N,H,W,3] uint8 (the relit frames), fut / past [N,2,H,W] f32 (estimate_flows_raft's layout, on the device) ->
+    (mean over the N-1 pairs, per-pair float64 numpy array).  Pairs run `batch` at a time."""
+    N, H, W = edit_u8.shape[:3]
+    if N < 2:
+        raise ValueError(f"warp-error-ssim needs at least 2 frames, got {N}")
+    if tuple(fut.shape) != (N, 2, H, W) or tuple(past.shape) != (N, 2, H, W):
+        raise ValueError(f"flows must be [N,2,H,W] = {(N, 2, H, W)}, got {tuple(fut.shape)} / {tuple(past.shape)}")
+    if H < 7 or W < 7:
+        raise ValueError(f"SSIM's 7x7 window needs H, W >= 7, got {H}x{W}")
+    dev = fut.device
+    e = torch.as_tensor(edit_u8).to(dev).contiguous()
+    if e.dtype != torch.uint8 or e.shape[-1] != 3:
+        raise ValueError(f"edit frames must be uint8 [N,H,W,3], got {e.dtype} {tuple(e.shape)}")
+    fut, past = fut.float().contiguous(), past.float().contiguous()
+    L = lib()
+    batch = max(1, min(batch, N - 1))
+    scores = torch.empty(N - 1, dtype=torch.float64, device=dev)
+    warped = torch.empty(batch, H, W, 3, dtype=torch.uint8, device=dev)
+    target = torch.empty_like(warped)
+    ws = torch.empty(L.tcl_eval_ssim_workspace_bytes(batch, H, W), dtype=torch.uint8, device=dev)
+    for s in range(0, N - 1, batch):
+        b = min(batch, N - 1 - s)
+        L.tcl_eval_warp_mask_u8(e, fut, past, warped, target, N, H, W, s, b, stream())
+        L.tcl_eval_ssim_u8(warped, target, scores[s:], b, H, W, ws, stream())
+    per = scores.cpu().numpy()
+    return float(np.mean(per)), per
+
+
+def _nhwc_u8(frames):
+    t = torch.as_tensor(np.asarray(frames)) if not isinstance(frames, torch.Tensor) else frames
+    if t.dim() != 4 or t.shape[-1] != 3 or t.dtype != torch.uint8:
+        raise ValueError(f"frames must be uint8 [N,H,W,3], got {t.dtype} {tuple(t.shape)}")
+    return t
+
+
+def resize_like(source_u8, H, W):
+    """PIL Image.resize((W, H)) with its default filter on every frame (evaluate.py:34-35), uint8 [N,h,w,3] -> [N,H,W,3]."""
+    from PIL import Image
+    src = source_u8.cpu().numpy()
+    return torch.from_numpy(np.stack([np.asarray(Image.fromarray(f).resize((W, H))) for f in src]))
+
+
+@torch.no_grad()
+def warp_ssim(edit_u8, source_u8, raft_engine, batch=4):
+    """The reference's SaveWarpingImage with RAFT flows (flow lists None): edit_u8 / source_u8 uint8 [N,H,W,3] (numpy or tensors) ->
+    (warp-error-ssim, per-pair float64 array).  Source frames of another size are resized to the edit size first (PIL, default filter)."""
+    from .raft import check_size
+    edit, src = _nhwc_u8(edit_u8), _nhwc_u8(source_u8)
+    N, H, W = edit.shape[:3]
+    if N < 2 or len(src) < N:
+        raise ValueError(f"warp-error-ssim needs at least 2 edit frames and as many source frames, got {N} / {len(src)}")
+    if tuple(src.shape[1:3]) != (H, W):
+        src = resize_like(src, H, W)
+    x = src[:N].to(raft_engine.dev).permute(0, 3, 1, 2).float()            # load_image: float 0..255
+    x, pad = _pad8(x)
+    check_size(*x.shape[-2:])
+    fut, past = estimate_flows_raft(raft_engine, x, batch=batch)            # 0..255 in: RAFT's own normalisation is then the right one
+    del x
+    l, r, t, b = pad
+    Hp, Wp = fut.shape[-2:]
+    if any(pad):
+        fut = fut[..., t:Hp - b, l:Wp - r].contiguous()
+        past = past[..., t:Hp - b, l:Wp - r].contiguous()
+    return warp_ssim_from_flows(edit, fut, past, batch=batch)
+
+
+# ---- files
+def find_videos(output_dir):
+    """-> (edit path, source path) in the reference's order: output_opt, then output, each as .mp4 then .avi, then output.npy for the edit;
+    output_gt as .mp4, then .avi, then .npy for the source.  FileNotFoundError when either is missing."""
+    def first(stems, tail):
+        for s in stems:
+            for ext in VIDEO_EXTS:
+                p = os.path.join(output_dir, s + ext)
+                if os.path.exists(p):
+                    return p
+        p = os.path.join(output_dir, tail)
+        return p if os.path.exists(p) else None
+    edit = first(EDIT_STEMS, "output.npy")
+    source = first((SOURCE_STEM,), SOURCE_STEM + ".npy")
+    if edit is None:
+        raise FileNotFoundError(f"no relit video in {output_dir} (output_opt / output as .mp4 or .avi, or output.npy)")
+    if source is None:
+        raise FileNotFoundError(f"no source video in {output_dir} ({SOURCE_STEM}.mp4 / .avi / .npy)")
+    return edit, source
+
+
+def read_video_u8(path):
+    """A video file -> uint8 [N,H,W,3] with the decoded values exactly (no float round trip)."""
+    from .dataparser import read_mjpeg_avi
+    if path.endswith(".npy"):
+        a = np.load(path)
+        if a.ndim == 4 and a.shape[1] == 3 and a.shape[-1] != 3:
+            a = a.transpose(0, 2, 3, 1)
+        if a.dtype != np.uint8:
+            raise ValueError(f"{path}: expected uint8 frames, got {a.dtype}")
+        return torch.from_numpy(np.ascontiguousarray(a))
+    if path.lower().endswith(".avi"):
+        fr = read_mjpeg_avi(path)
+        if fr is not None:
+            return fr
+    try:
+        import torchvision.io as tvio
+        return tvio.read_video(path, pts_unit="sec", output_format="THWC")[0]
+    except ImportError:
+        pass
+    try:
+        import cv2
+    except ImportError:
+        raise RuntimeError(f"no video decoder (torchvision.io / cv2) for {path}; write the frames as a Motion-JPEG .avi or a uint8 .npy") from None
+    cap, out = cv2.VideoCapture(path), []
+    while True:
+        ok, fr = cap.read()
+        if not ok:
+            break
+        out.append(torch.from_numpy(fr[..., ::-1].copy()))
+    if not out:
+        raise RuntimeError(f"cv2 decoded no frames from {path}")
+    return torch.stack(out)
+
+
+# ---- the report
+def video_name(config):
+    """evaluate.py:123: the parent directory of config.input_path, else 'unknown_video'."""
+    p = config.get("input_path") if hasattr(config, "get") else None
+    return p.split("/")[-2] if isinstance(p, str) and "/" in p else "unknown_video"
+
+
+def cost_scores(config, width, height):
+    """evaluate.py:61-66 (--eval_cost): the z_* entries from the run's config.yaml."""
+    missing = [k for k in ("sec_per_frame", "max_memory_allocated", "total_number_of_frames", "total_time") if k not in config]
+    if missing:
+        raise KeyError(f"--eval_cost needs {missing} in config.yaml (written by run.py)")
+    return {"z_fps": 1 / config["sec_per_frame"], "z_max_memory_allocated(M)": config["max_memory_allocated"],
+            "z_resolution": math.sqrt(width * height), "z_total_frames": config["total_number_of_frames"], "z_total_time(s)": config["total_time"]}
+
+
+def format_results(name, prompt, scores):
+    """print_and_save_results (evaluate.py:70-95): the header `{name} - {prompt}`, then the metrics sorted by name; warp-error-ssim x100 with 2
+    decimals, everything else with 4.  Returns the text of result.txt."""
+    lines = [f"{name} - {prompt}"]
+    for metric, score in sorted(scores.items()):
+        if "warp-error-l1" in metric:
+            lines.append(f"{metric}: {score * 1e5:.2f}")
+        elif "warp-error-l2" in metric or "warp-error-ssim" in metric:
+            lines.append(f"{metric}: {score * 100:.2f}")
+        else:
+            lines.append(f"{metric}: {score:.4f}")
+    return "\n".join(lines) + "\n"
