@@ -3,15 +3,22 @@
 // through torch SDPA / xformers (AttnProcessor2_0, utils/model_utils.py:66-67; patch.py:170-176).  T x T scores are
 // never materialised.
 //
-// Two kernels:
-//  pack : Q,K,V rows (heads interleaved in channels) -> head-major, zero-padded panels
-//           Qp [B,H,Tqp,DP] (pre-scaled by softmax_scale*log2 e), Kp [B,H,Tkp,DP], Vt [B,H,DPV,Tkp] (V transposed so the
-//           PV contraction reads keys contiguously).  DP = d rounded to 16, DPV = d rounded to 32.
-//  flash: block = 4 waves x 32 query rows; 64-key K/V tiles staged global->VGPR->LDS, double-buffered.
-//         S^T = K.Q^T with mfma_f32_32x32x16_f16 (swapped operands: lane l owns query l&31, so the row max/sum is
-//         in-lane + one lane<->lane+32 exchange); P stays in registers as the B operand of O^T = V^T.P^T (the key
-//         permutation of the accumulator layout is matched by the V^T fragment addresses instead of shuffling P).
-//         Block id -> head = id % H so that each head's K/V panel lives in one XCD's L2.
+// What is in this file:
+//  pack : Q,K,V rows (heads interleaved in channels) -> head-major, zero-padded panels, one launch (k_pack_qkv; k_pack_rows / k_pack_vt when only
+//           a part is packed): Qp [B,H,Tqp,DP] (pre-scaled by softmax_scale*log2 e), Kp [B,H,Tkp,DP+8], Vt [B,H,Tkp/64,DPV,V_STRIDE] (V transposed and
+//           tile-major, so that a 64-key K or V^T tile is one contiguous LDS image).  DP = d rounded to 16, DPV = d rounded to 32.
+//  flash: k_flash, block = 4 waves x QB blocks of 32 query rows.  64-key K / V^T tiles go global -> LDS by LDS-DMA (global_load_lds_dwordx4,
+//           no VGPR staging) into a ring of NSTG slots, prefetch distance NSTG - 1, counted vmcnt and one raw barrier per tile -- or per pair
+//           of tiles (TPB = 2, 4-slot ring).  S^T = K.Q^T with mfma_f32_32x32x16_f16 (swapped operands: lane l owns query l&31, so the row
+//           max/sum is in-lane + one lane<->lane+32 exchange); P stays in registers as the B operand of O^T = V^T.P^T (the key permutation
+//           of the accumulator layout is matched by the V^T fragment addresses instead of shuffling P).  Block id -> head = id % H so that
+//           each head's K/V panel lives in one XCD's L2.  The forms the dispatch in tcl_attention_f16 picks:
+//             d = 40, large grid : QB = 2, NSTG = 4, TPB = 2, SPEC = 1 (speculative softmax: no row maxima in the loop), followed by the same
+//                                  kernel with SPEC = 0 (exact maxima) gated by the per-block overflow flags of the first
+//             d = 40, small grid : QB = 1, NSTG = 2, four blocks per CU
+//             d = 80 / 128       : QB = 1, NSTG = 2;   d = 160: QB = 1, NSTG = 3
+//  split-KV: k_flash_lse (the d = 128 body over one chunk of the keys per batch entry, which also hands on log2 of its softmax denominator)
+//           and k_attn_merge (joins the chunks' partial outputs).
 #include "common.h"
 #include "gemm_conv.h"
 #include "prof.h"
@@ -26,21 +33,11 @@ typedef float float4v __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
-#ifndef TCL_FLASH80_DEFAULT
-#define TCL_FLASH80_DEFAULT 4
-#endif
-#ifndef TCL_FLASH_PV32_DEFAULT
-#define TCL_FLASH_PV32_DEFAULT 0
-#endif
 #define KV_TILE 64
 #define V_STRIDE 72   // halves: 144 B = 9 x 16 B (odd) -> the 16-lane groups of a ds_read_b128 are conflict-free
-// Head_dim 40's V^T tile: DPV rows of V_STRIDE halves.  PV16 reads 48 rows (40 + the ones row + 7 idle); rounds 2-4 stored 64 (9 KiB per tile, 16 DMA
-// pieces per 64-key stage with the 7 KiB K image).  TCL_DPV40 = 48 (round 5): 48 rows, tile padded to 7 KiB so that a stage is exactly 14 pieces --
-// 12.5 % less L2 -> LDS traffic and two DMA instructions less per tile; the PV32 variant needs all 64 rows.
-#ifndef TCL_DPV40
-#define TCL_DPV40 64
-#endif
-__host__ __device__ constexpr int vt_tile_halves(int dpv) { return dpv == 48 ? 3584 : dpv * V_STRIDE; }
+// V^T tile of 64 keys: DPV rows of V_STRIDE halves.  Head_dim 40 stores 64 rows (9 KiB per tile, 16 DMA pieces per 64-key stage with the 7 KiB K
+// image), of which its PV on 16x16x32 MFMAs reads 48 (40 + the ones row + 7 idle).
+__host__ __device__ constexpr int vt_tile_halves(int dpv) { return dpv * V_STRIDE; }
 
 // one_col >= 0: that column (a padding column, >= d) is set to 1 in valid rows (the K panel's ones column for the folded shift)
 __device__ __forceinline__ void pack_rows_blk(int blk, int nblk, const _Float16* __restrict__ src, long bstride, int ld, int T, int H, int d, float scale,
@@ -134,15 +131,15 @@ __device__ __forceinline__ float xhalf_max(float v) {
 
 // (the body of k_flash for ONE block index: the kernel below calls it once, or -- the flag-gated exact pass behind the speculative kernel -- once per
 // flagged index of its stride class)
-template <int D, int DP, int DPV, int QB, int NSTG, int TPB, int MINB, int SPEC, int PVW, int NW, bool SPLIT = false>
+template <int D, int DP, int DPV, int QB, int NSTG, int TPB, int MINB, int SPEC, bool SPLIT = false>
 __device__ __forceinline__ void flash_block(const int bid, const _Float16* __restrict__ Qp, const _Float16* __restrict__ Kp, const _Float16* __restrict__ Vt,
                                             _Float16* __restrict__ O, int H, int Tq, int Tk, int Tqp, int Tkp, int d, int ldo, long obstride,
                                             int kv_div, int nqb, int* __restrict__ flags, float* __restrict__ lse = nullptr) {
     constexpr int KS = DP + 8;                    // K row stride (halves); KS/8 odd -> conflict-free b128 reads
     constexpr int NQK = DP / 16, NDT = DPV / 32;
     constexpr int KBYTES = KV_TILE * KS * 2, VBYTES = vt_tile_halves(DPV) * 2, SBYTES = KBYTES + VBYTES;
-    // NW waves per block (4; 8 for head_dim 80, round 5): a K / V^T stage serves 32 QB NW queries -- its DMA pieces per query halve with 8 waves
-    constexpr int NPIECE = (SBYTES + 1023) / 1024, NPW = (NPIECE + NW - 1) / NW, SSTRIDE = NPIECE * 1024;
+    // 1-KiB DMA pieces of a stage, and pieces per wave (4 waves per block: a K / V^T stage serves 128 QB queries)
+    constexpr int NPIECE = (SBYTES + 1023) / 1024, NPW = (NPIECE + 3) / 4, SSTRIDE = NPIECE * 1024;
     constexpr bool LROW = DPV > D;
     constexpr bool FOLD = DP > D && LROW && (D % 16 == 8);        // spare Q/K column D: lanes hl == 1, element 0 of fragment D/16
     constexpr bool PVQ = QB > 1;                                  // PV per query block right behind its softmax (V^T fragments held in registers)
@@ -153,27 +150,19 @@ __device__ __forceinline__ void flash_block(const int bid, const _Float16* __res
     // X.row1 <-> Y.row0, X.row3 <-> Y.row2 turns X into the operand of queries 0-15 and Y into that of queries 16-31, key groups in the order
     // (A, B, C, D) = keys {0-3,8-11}, {16-19,24-27}, {4-7,12-15}, {20-23,28-31} -- which the V^T panel's in-tile key permutation already
     // stores at halves 0, 16, 8, 24 of a 32-key block.
-    // PVW = 32 (round 5): head_dim 40 back on 8 MFMAs 32x32x16 over all 64 V^T rows.  The loop is bound by vector ISSUE, not by matrix cycles
-    // (tools/micro/flash_mix.hip): the 16 permlane16_swap of a wave-tile and 4 of its 12 + 6 MFMA issues cost more issue slots than the 64
-    // matrix cycles PV16 saves; the 32x32 P registers ARE the 32x32x16 B operand (the panel's in-tile key permutation absorbs the key order).
-    constexpr bool PV16 = PVW == 16 && D == 40 && LROW && DPV >= 48;
+    constexpr bool PV16 = D == 40 && LROW && DPV >= 48;
     constexpr int NT16 = 3;                                       // 16-row V^T tiles: rows 0-39 V, row 40 ones, 41-47 zero
     extern __shared__ __attribute__((aligned(16))) char smem[];          // 3 stages of SSTRIDE bytes + 1 KiB dump
 
     const int head = bid % H, qb_ = (bid / H) % nqb, b = bid / (H * nqb);
     const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6), hl = lane >> 5, ql = lane & 31;
-    const int q0 = qb_ * (32 * NW * QB) + wid * (32 * QB);
+    const int q0 = qb_ * (128 * QB) + wid * (32 * QB);
     const long bh = (long)b * H + head, kbh = (long)(b / kv_div) * H + head;
     const int nt = Tkp / KV_TILE, nfull = Tk / KV_TILE;      // tiles / tiles without padded keys
     const char* kbase = (const char*)(Kp + kbh * Tkp * KS);
     const char* vbase = (const char*)(Vt + kbh * nt * vt_tile_halves(DPV));
     const char* zero = (const char*)g_flash_zero;
 
-#ifdef TCL_FLASH_PRIO_EXP
-    // lab (round 5, tools/ab/ab_attn.sh): static priority for every other block of an XCD's sequence -- MI355X_MICROARCH "static priority for the
-    // younger half", transplanted to two independent 4-wave blocks sharing a CU.  Measured: see DESIGN 4.12 (not in the product build).
-    if ((bid >> 3) & 1) __builtin_amdgcn_s_setprio(TCL_FLASH_PRIO_EXP);
-#endif
     half8 qf[QB][NQK];
 #pragma unroll
     for (int qb = 0; qb < QB; ++qb) {
@@ -195,11 +184,11 @@ __device__ __forceinline__ void flash_block(const int bid, const _Float16* __res
         const char* vt_ = vbase + (long)(IT) * VBYTES;                                                                        \
         const int st_ = ((IT) % NSTG) * SSTRIDE;                                                                              \
         _Pragma("unroll") for (int i = 0; i < NPW; ++i) {                                                                    \
-            const int pb_ = (wid + NW * i) * 1024;                                                                            \
+            const int pb_ = (wid + 4 * i) * 1024;                                                                            \
             const char* src_ = (pb_ < KBYTES ? kt_ + pb_ : vt_ + (pb_ - KBYTES)) + lane16;                                    \
             if (SBYTES % 1024 != 0) src_ = pb_ + lane16 < SBYTES ? src_ : zero + lane16;                                      \
-            else if (NSTG != 3 && NPW * NW != NPIECE && (wid + NW * i) >= NPIECE) continue;   /* nothing to issue past the stage (wave-uniform; the 3-slot ring COUNTS its pieces: it keeps the dump piece) */ \
-            const int dst_ = (wid + NW * i) < NPIECE ? st_ + pb_ : NSTG * SSTRIDE;      /* pieces past the stage: 1 KiB dump */  \
+            else if (NSTG != 3 && NPW * 4 != NPIECE && (wid + 4 * i) >= NPIECE) continue;   /* nothing to issue past the stage (wave-uniform; the 3-slot ring COUNTS its pieces: it keeps the dump piece) */ \
+            const int dst_ = (wid + 4 * i) < NPIECE ? st_ + pb_ : NSTG * SSTRIDE;      /* pieces past the stage: 1 KiB dump */  \
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src_,                             \
                                              (__attribute__((address_space(3))) void*)(lds0 + dst_), 16, 0, 0);               \
         }                                                                                                                     \
@@ -237,10 +226,7 @@ __device__ __forceinline__ void flash_block(const int bid, const _Float16* __res
     // tile pair pay a rebase (keys scaled by a ramp 0.3 .. 6 along the sequence: 567 against 758 TFLOP/s for the exact kernel); keys in
     // token order have no such trend.  Tiles with padded keys (the last one) take the exact-maximum
     // path below -- same shift convention, any shift is valid there -- so the speculative code carries no key masks.
-#ifndef TCL_SPEC_OFF
-#define TCL_SPEC_OFF 3
-#endif
-    constexpr float OFF = TCL_SPEC_OFF;
+    constexpr float OFF = 3.f;
     unsigned orv = 0;                                 // SPEC: OR of the packed P registers since the last guard test
     static_assert(!SPEC || (FOLD && (PV16 || PVQ)), "the speculative softmax is the head_dim-40 path");
     auto rebase = [&](const int it, const bool first) __attribute__((always_inline)) {
@@ -610,8 +596,8 @@ __device__ __forceinline__ void flash_block(const int bid, const _Float16* __res
     }
 }
 
-template <int D, int DP, int DPV, int QB, int NSTG, int TPB, int MINB, int SPEC, int PVW, int NW>
-__global__ __launch_bounds__(64 * NW, (MINB ? MINB : (QB == 1 && DP <= 80 && TPB == 1 ? 3 : 2)) * (NW >= 4 ? NW / 4 : 1)) void k_flash(const _Float16* __restrict__ Qp, const _Float16* __restrict__ Kp, const _Float16* __restrict__ Vt,
+template <int D, int DP, int DPV, int QB, int NSTG, int TPB, int MINB, int SPEC>
+__global__ __launch_bounds__(256, MINB ? MINB : (QB == 1 && DP <= 80 && TPB == 1 ? 3 : 2)) void k_flash(const _Float16* __restrict__ Qp, const _Float16* __restrict__ Kp, const _Float16* __restrict__ Vt,
                                                   _Float16* __restrict__ O, int H, int Tq, int Tk, int Tqp, int Tkp, int d, int ldo, long obstride,
                                                   int kv_div, int nqb, int* __restrict__ flags, int nblk) {
     if constexpr (D == 40 && QB == 2 && !SPEC) {
@@ -619,232 +605,24 @@ __global__ __launch_bounds__(64 * NW, (MINB ? MINB : (QB == 1 && DP <= 80 && TPB
         // 222 VGPRs / 66 KiB LDS just to read one word each took 57 us per attention call on the main stream (1.6 s per 300-frame pass).  The
         // gated pass is launched with at most 512 blocks (one resident round); a block walks the flags of its stride class and runs the flagged ones.
         if (flags) {
-            // Round 5, second pass: a block reads its flags 64 NW at a time (one load per thread, one round trip per window) instead of one after the other
+            // Round 5, second pass: a block reads its flags 256 at a time (one load per thread, one round trip per window) instead of one after the other
             // -- a block of a 16-block grid walked ~370 DEPENDENT L2 round trips, which is why small grids measured slower (profiles/r5_ab_flash_gate.txt);
             // with the windowed scan a 32-block grid costs the same as 512 IN THE PASS too (profiles/r5c_ab_gate_inpass.txt: 33.12-33.14 s of denoise at
             // 60 frames either way, 8 blocks +0.3 %): the ~52 us of this launch are not a wait for slots between the matching chain's blocks.  512 stays.
             const int per = (nblk + (int)gridDim.x - 1) / (int)gridDim.x, lo = (int)blockIdx.x * per, hi = min(lo + per, nblk);
-            for (int base = lo; base < hi; base += 64 * NW) {
+            for (int base = lo; base < hi; base += 256) {
                 const int mine = base + (int)threadIdx.x < hi ? flags[base + threadIdx.x] : 0;
                 if (!__syncthreads_or(mine)) continue;
-                for (int bid = base; bid < min(base + 64 * NW, hi); ++bid) {          // (rare: some block of this window flagged an overflow)
+                for (int bid = base; bid < min(base + 256, hi); ++bid) {          // (rare: some block of this window flagged an overflow)
                     if (!flags[bid]) continue;
-                    flash_block<D, DP, DPV, QB, NSTG, TPB, MINB, SPEC, PVW, NW>(bid, Qp, Kp, Vt, O, H, Tq, Tk, Tqp, Tkp, d, ldo, obstride, kv_div, nqb, flags);
+                    flash_block<D, DP, DPV, QB, NSTG, TPB, MINB, SPEC>(bid, Qp, Kp, Vt, O, H, Tq, Tk, Tqp, Tkp, d, ldo, obstride, kv_div, nqb, flags);
                     __syncthreads();              // the next item re-uses the LDS ring
                 }
             }
             return;
         }
     }
-    flash_block<D, DP, DPV, QB, NSTG, TPB, MINB, SPEC, PVW, NW>(blockIdx.x, Qp, Kp, Vt, O, H, Tq, Tk, Tqp, Tkp, d, ldo, obstride, kv_div, nqb, flags);
-}
-
-// ---------------------------------------------------------------------------------------------------------------------------------
-// Head_dim 40, software-pipelined across key tiles (k_flash40p).  The loop of k_flash is bound by VALU issue, and within one wave its
-// matrix and vector work are a dependency chain (QK^T -> max -> exp -> PV): the two pipes only overlap where the two waves of a SIMD
-// happen to be in opposite phases (matrix pipe 46 %, VALU 68 % busy).  Here every loop iteration i issues three INDEPENDENT streams:
-//     vector:  softmax of tile i          (scores from the QK^T MFMAs issued one iteration earlier)
-//     matrix:  PV of tile i-1             (P from the softmax of the previous iteration)
-//     matrix:  QK^T of tile i+1           (for the softmax of the next iteration)
-// so one wave keeps both pipes busy by itself.  The price is two score tiles and two P tiles live: with ONE 32-query block per wave that
-// is ~170 VGPRs (two query blocks would need ~300), i.e. each K / V^T fragment read from LDS feeds one MFMA instead of two -- LDS array
-// time doubles to ~28 %, still off the critical path.  Same arithmetic as k_flash<40,...> (swapped-operand S^T, shift folded into the
-// spare Q column, ones-row row sums, PV on 16x16x32 MFMAs, lazy re-basing when a row maximum climbs 2^6 above the shift).
-// Ring of 4 tile slots: iteration i reads V^T of tile i-1 and K of tile i+1 while tile i+2 streams in; one barrier per tile.
-// Re-basing at tile i (rare): PV(i-1) is issued early in that path (it belongs to the old shift), O and the scores of tile i move to the
-// new shift, and the QK^T of tile i+1 -- issued after the decision -- already sees the new shift in the Q column.
-template <int NW, int NSTG>        // waves per block (4: two blocks per CU; 8: one), ring slots (prefetch distance NSTG - 3 tiles beyond the next)
-__global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) void k_flash40p(const _Float16* __restrict__ Qp, const _Float16* __restrict__ Kp, const _Float16* __restrict__ Vt,
-                                                    _Float16* __restrict__ O, int H, int Tq, int Tk, int Tqp, int Tkp, int ldo, long obstride,
-                                                    int kv_div, int nqb) {
-    constexpr int D = 40, DP = 48, DPV = 64, KS = DP + 8, NQK = 3, NT16 = 3, PF = NSTG - 3;      // PF: tiles in flight beyond tile it+1
-    constexpr int KBYTES = KV_TILE * KS * 2, VBYTES = DPV * V_STRIDE * 2, SBYTES = KBYTES + VBYTES, NPIECE = SBYTES / 1024, NPW = NPIECE / NW, SSTRIDE = SBYTES;
-    static_assert(KBYTES % 1024 == 0 && NPIECE % NW == 0 && PF >= 1 && PF <= 3, "tile image must split into NW x NPW pieces");
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    __attribute__((address_space(3))) char* const lds0 = (__attribute__((address_space(3))) char*)smem;
-    const int bid = blockIdx.x, head = bid % H, qb_ = (bid / H) % nqb, b = bid / (H * nqb);
-    const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6), hl = lane >> 5, ql = lane & 31;
-    const int q0 = qb_ * (NW * 32) + wid * 32;
-    const long bh = (long)b * H + head, kbh = (long)(b / kv_div) * H + head;
-    const int nt = Tkp / KV_TILE, nfull = Tk / KV_TILE;
-    const char* kbase = (const char*)(Kp + kbh * Tkp * KS);
-    const char* vbase = (const char*)(Vt + kbh * nt * DPV * V_STRIDE);
-    const int lane16 = lane * 16, goff = (((lane >> 4) & 1) * 16 + (lane >> 5) * 8) ^ ((((lane & 15) + 4) & 8) ? 16 : 0);
-    half8 qf[NQK];
-    {
-        const _Float16* qrow = Qp + (bh * Tqp + q0 + ql) * DP + 8 * hl;
-#pragma unroll
-        for (int ks = 0; ks < NQK; ++ks) qf[ks] = *(const half8*)(qrow + ks * 16);
-    }
-#define P40_ISSUE(IT)                                                                                                         \
-    {                                                                                                                         \
-        const char* kt_ = kbase + (long)(IT) * KBYTES;                                                                        \
-        const char* vt_ = vbase + (long)(IT) * VBYTES;                                                                        \
-        const int st_ = ((IT) % NSTG) * SSTRIDE;                                                                              \
-        _Pragma("unroll") for (int i = 0; i < NPW; ++i) {                                                                    \
-            const int pb_ = (wid + NW * i) * 1024;                                                                            \
-            const char* src_ = (pb_ < KBYTES ? kt_ + pb_ : vt_ + (pb_ - KBYTES)) + lane16;                                    \
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src_,                             \
-                                             (__attribute__((address_space(3))) void*)(lds0 + st_ + pb_), 16, 0, 0);          \
-        }                                                                                                                     \
-    }
-    float4v o16[2][NT16];
-#pragma unroll
-    for (int qt = 0; qt < 2; ++qt)
-#pragma unroll
-        for (int t = 0; t < NT16; ++t) o16[qt][t] = float4v{0.f, 0.f, 0.f, 0.f};
-    float m = 0.f;
-    // QK^T of one tile: S^T[key, query] for the wave's 32 queries against the 64 keys of the tile in ring slot (it & 3)
-    auto qk = [&](const int it, float16v (&sc)[2]) __attribute__((always_inline)) {
-        const _Float16* kt = (const _Float16*)(smem + (it % NSTG) * SSTRIDE);
-#pragma unroll
-        for (int blk = 0; blk < 2; ++blk) {
-            half8 kf[NQK];
-#pragma unroll
-            for (int ks = 0; ks < NQK; ++ks) kf[ks] = *(const half8*)(kt + (blk * 32 + ql) * KS + 8 * hl + ks * 16);
-            float16v z;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) z[r] = 0.f;
-            sc[blk] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[0], qf[0], z, 0, 0, 0);
-#pragma unroll
-            for (int ks = 1; ks < NQK; ++ks) sc[blk] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[ks], qf[ks], sc[blk], 0, 0, 0);
-        }
-    };
-    // O^T += V^T . P^T of one tile (P already in the 16x16x32 operand layout: [blk][queries 0-15 | 16-31])
-    auto pv = [&](const int it, const half8 (&pp)[2][2]) __attribute__((always_inline)) {
-        const _Float16* vt = (const _Float16*)(smem + (it % NSTG) * SSTRIDE + KBYTES);
-#pragma unroll
-        for (int blk = 0; blk < 2; ++blk)
-#pragma unroll
-            for (int t = 0; t < NT16; ++t) {
-                const half8 vf = *(const half8*)(vt + (t * 16 + (lane & 15)) * V_STRIDE + blk * 32 + goff);
-                o16[0][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vf, pp[blk][0], o16[0][t], 0, 0, 0);
-                o16[1][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vf, pp[blk][1], o16[1][t], 0, 0, 0);
-            }
-    };
-    // exp2 of one score tile -> P in the PV operand layout (cvt_pk pairs + permlane16 exchange, see k_flash PV16)
-    auto softmax = [&](const float16v (&sc)[2], half8 (&pp)[2][2]) __attribute__((always_inline)) {
-#pragma unroll
-        for (int blk = 0; blk < 2; ++blk) {
-            half8 x, y;
-#pragma unroll
-            for (int r = 0; r < 8; ++r) { x[r] = (_Float16)__builtin_amdgcn_exp2f(sc[blk][r]); y[r] = (_Float16)__builtin_amdgcn_exp2f(sc[blk][8 + r]); }
-            u32x4 xu = __builtin_bit_cast(u32x4, x), yu = __builtin_bit_cast(u32x4, y);
-#pragma unroll
-            for (int w = 0; w < 4; ++w) {
-                const auto sw = __builtin_amdgcn_permlane16_swap(xu[w], yu[w], false, false);
-                xu[w] = sw[0]; yu[w] = sw[1];
-            }
-            pp[blk][0] = __builtin_bit_cast(half8, xu); pp[blk][1] = __builtin_bit_cast(half8, yu);
-        }
-    };
-    // One pipeline step for tile `it`: scores of tile it in sc, P of tile it-1 in pprev; leaves scores of it+1 in snext and P of it in pcur.
-    // FIRST: tile 0 (no pending PV, the shift is always based); LAST: no next tile.  The steady state (neither) has NO conditional around its
-    // three streams, so they are one basic block for the scheduler; the rare re-basing path carries its own copy of the streams.
-    auto step = [&](const int it, float16v (&sc)[2], float16v (&snext)[2], const half8 (&pprev)[2][2], half8 (&pcur)[2][2], auto FIRST, auto LAST)
-                    __attribute__((always_inline)) {
-        constexpr bool first = decltype(FIRST)::value, last = decltype(LAST)::value;
-        if (it >= nfull) {                                                      // wave-uniform: only the last tile has padded keys
-            asm volatile("; mask");
-#pragma unroll
-            for (int blk = 0; blk < 2; ++blk)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) { const int kv = it * KV_TILE + blk * 32 + (r & 3) + 8 * (r >> 2) + 4 * hl; if (kv >= Tk) sc[blk][r] = -1e30f; }
-        }
-        float mx = sc[0][0];
-#pragma unroll
-        for (int blk = 0; blk < 2; ++blk)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) mx = fmaxf(mx, sc[blk][r]);
-        mx = xhalf_max(mx);
-        if (first || __any(mx > 6.f)) {                                         // re-base the shift (tile 0 always; later only on a 2^6 climb)
-            if (!first) { asm volatile("; rebase"); pv(it - 1, pprev); }        // the pending PV belongs to the OLD shift: add it before O is rescaled
-            const float mn = (float)(_Float16)(m + (first ? mx : fmaxf(mx, 0.f)));
-            const float delta = mn - m, alpha = __builtin_amdgcn_exp2f(-delta);
-            m = mn;
-            if (hl == 1) qf[D / 16][0] = (_Float16)(-mn);
-            if (!first) {
-#pragma unroll
-                for (int qt = 0; qt < 2; ++qt) {
-                    const float aq = __shfl(alpha, (lane & 15) + 16 * qt, 64);
-#pragma unroll
-                    for (int t = 0; t < NT16; ++t) o16[qt][t] *= aq;
-                }
-            }
-#pragma unroll
-            for (int blk = 0; blk < 2; ++blk)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) sc[blk][r] -= delta;
-            if (!last) qk(it + 1, snext);
-            softmax(sc, pcur);
-        } else {
-            // the three independent streams of the steady state
-            pv(it - 1, pprev);
-            if (!last) qk(it + 1, snext);
-            softmax(sc, pcur);
-        }
-    };
-    // Before step `it`: tile it+1 (its K is read by this step's QK^T) must have landed -- up to PF younger tiles stay in flight (counted
-    // vmcnt); past the barrier every wave has finished step it-1, i.e. the V^T of tile it-2, so slot (it+1+PF) % NSTG is free for tile it+1+PF.
-#define P40_SYNC(IT)                                                                                                          \
-    if ((IT) + 1 < nt) {                                                                                                      \
-        /* in flight here: tiles IT+1 .. IT+PF (those that exist); tile IT+1 has landed once at most the younger ones remain */ \
-        if (PF >= 3 && (IT) + 3 < nt) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * NPW) : "memory");                          \
-        else if (PF >= 2 && (IT) + 2 < nt) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NPW) : "memory");                         \
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                                                 \
-        __builtin_amdgcn_s_barrier();                                                                                         \
-        if ((IT) + 1 + PF < nt) P40_ISSUE((IT) + 1 + PF);                                                                     \
-    }
-    float16v sA[2], sB[2];
-    half8 pA[2][2], pB[2][2];
-    const std::true_type T_{}; const std::false_type F_{};
-    P40_ISSUE(0);
-#pragma unroll
-    for (int j = 1; j <= PF; ++j) if (j < nt) P40_ISSUE(j);                     // tiles 1 .. PF in flight behind tile 0
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                            // (prologue: simply everything)
-    __builtin_amdgcn_s_barrier();                                               // tile 0 landed for every wave
-    qk(0, sA);
-    if (nt == 1) { step(0, sA, sB, pB, pA, T_, T_); pv(0, pA); }
-    else {
-        P40_SYNC(0);
-        step(0, sA, sB, pB, pA, T_, F_);                                        // -> P(0) in pA, scores(1) in sB
-        int it = 1;
-        for (; it + 2 < nt; it += 2) {                                          // it odd; steps it and it+1 are both steady
-            P40_SYNC(it);
-            step(it, sB, sA, pA, pB, F_, F_);
-            P40_SYNC(it + 1);
-            step(it + 1, sA, sB, pB, pA, F_, F_);
-        }
-        if (it + 1 < nt) {                                                      // two tiles left: a steady odd step, then the last (even) one
-            P40_SYNC(it);
-            step(it, sB, sA, pA, pB, F_, F_);
-            step(it + 1, sA, sB, pB, pA, F_, T_);
-            pv(it + 1, pA);
-        } else {                                                                // one tile left (odd)
-            step(it, sB, sA, pA, pB, F_, T_);
-            pv(it, pB);
-        }
-    }
-#undef P40_SYNC
-#undef P40_ISSUE
-    // ---- epilogue (as k_flash PV16): row sums in O^T row 40 = tile 2, lanes 32-47, register 0
-#pragma unroll
-    for (int qt = 0; qt < 2; ++qt) {
-        const float inv = 1.f / __shfl(o16[qt][2][0], 32 + (lane & 15), 64);
-        const int q = q0 + qt * 16 + (lane & 15);
-        if (q < Tq) {
-            _Float16* orow = O + (long)b * obstride + (long)q * ldo + head * D;
-#pragma unroll
-            for (int t = 0; t < NT16; ++t) {
-                const int dd = t * 16 + 4 * (lane >> 4);
-                if (dd < D) {
-                    const float4v v = o16[qt][t];
-                    half4 w = {(_Float16)(v[0] * inv), (_Float16)(v[1] * inv), (_Float16)(v[2] * inv), (_Float16)(v[3] * inv)};
-                    *(half4*)(orow + dd) = w;
-                }
-            }
-        }
-    }
+    flash_block<D, DP, DPV, QB, NSTG, TPB, MINB, SPEC>(blockIdx.x, Qp, Kp, Vt, O, H, Tq, Tk, Tqp, Tkp, d, ldo, obstride, kv_div, nqb, flags);
 }
 
 // ---- optional in-library timing of the flash kernel (bench.py roofline leg): HIP events recorded on the launch stream
@@ -866,14 +644,14 @@ static void flash_prof_drain(bool all) {
     }
 }
 
-template <int D, int DP, int DPV, int QB, int NSTG, int TPB = 1, int MINB = 0, int SPEC = 0, int PVW = 16, int NW = 4>
+template <int D, int DP, int DPV, int QB, int NSTG, int TPB = 1, int MINB = 0, int SPEC = 0>
 static int launch_flash(const _Float16* Qp, const _Float16* Kp, const _Float16* Vt, _Float16* O, int B, int H, int Tq, int Tk, int Tqp, int Tkp,
                         int d, int ldo, long obs, int kv_div, hipStream_t st, int* flags = nullptr, bool count = true) {
     constexpr int SB = KV_TILE * (DP + 8) * 2 + vt_tile_halves(DPV) * 2, NPIECE = (SB + 1023) / 1024;
     const size_t lds = (size_t)NSTG * NPIECE * 1024 + 1024;
     static bool set = false;
-    if (!set) { (void)hipFuncSetAttribute((const void*)k_flash<D, DP, DPV, QB, NSTG, TPB, MINB, SPEC, PVW, NW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); set = true; }
-    const int nqb = Tqp / (32 * NW * QB);
+    if (!set) { (void)hipFuncSetAttribute((const void*)k_flash<D, DP, DPV, QB, NSTG, TPB, MINB, SPEC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); set = true; }
+    const int nqb = Tqp / (128 * QB);
     const bool prof = g_prof.on && (g_prof.dfilter == 0 || g_prof.dfilter == d);
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (prof) {
@@ -883,10 +661,10 @@ static int launch_flash(const _Float16* Qp, const _Float16* Kp, const _Float16* 
     const int nblk = B * H * nqb;
     // gated exact pass: a small grid of blocks walks the flags (normally none is set: what the launch costs is the DISPATCH of its 222-VGPR / 66-KiB blocks --
     // 57 us with one block per flag (round 3), 56 us in the pass with one resident round of 512 (round 4).  Round 5 measured smaller grids
-    // (TCL_FLASH_GATE_BLOCKS, profiles/r5_ab_flash_gate.txt): 64 blocks the same call rate as 512, 16 blocks 1.4 % SLOWER -- the pass is not dispatch-bound)
-    static const int gate_blocks = getenv("TCL_FLASH_GATE_BLOCKS") ? atoi(getenv("TCL_FLASH_GATE_BLOCKS")) : 512;
-    const int grid = (D == 40 && QB == 2 && !SPEC && flags && nblk > gate_blocks) ? gate_blocks : nblk;
-    hipLaunchKernelGGL((k_flash<D, DP, DPV, QB, NSTG, TPB, MINB, SPEC, PVW, NW>), dim3(grid), dim3(64 * NW), lds, st, Qp, Kp, Vt, O, H, Tq, Tk, Tqp, Tkp, d, ldo, obs, kv_div, nqb, flags, nblk);
+    // (profiles/r5_ab_flash_gate.txt): 64 blocks the same call rate as 512, 16 blocks 1.4 % SLOWER -- the pass is not dispatch-bound)
+    constexpr int GATE_BLOCKS = 512;
+    const int grid = (D == 40 && QB == 2 && !SPEC && flags && nblk > GATE_BLOCKS) ? GATE_BLOCKS : nblk;
+    hipLaunchKernelGGL((k_flash<D, DP, DPV, QB, NSTG, TPB, MINB, SPEC>), dim3(grid), dim3(256), lds, st, Qp, Kp, Vt, O, H, Tq, Tk, Tqp, Tkp, d, ldo, obs, kv_div, nqb, flags, nblk);
     if (prof) { (void)hipEventRecord(e1, st); g_prof.ev.push_back(e0); g_prof.ev.push_back(e1); if (count) { const double fl = 4.0 * B * H * (double)Tq * Tk * d; g_prof.flops += fl; g_prof.launches++; if (fl > g_prof.bigfl) { g_prof.bigfl = fl; g_prof.big[0] = B; g_prof.big[1] = H; g_prof.big[2] = Tq; g_prof.big[3] = Tk; } } }
     return hipPeekAtLastError() == hipSuccess ? TCL_OK : TCL_ELAUNCH;
 }
@@ -899,7 +677,7 @@ template <int D, int DP, int DPV, int QB, int NSTG>
 __global__ __launch_bounds__(256, 2) void k_flash_lse(const _Float16* __restrict__ Qp, const _Float16* __restrict__ Kp, const _Float16* __restrict__ Vt,
                                                       _Float16* __restrict__ O, int H, int Tq, int Tk, int Tqp, int Tkp, int d, int ldo, long obstride, int nqb,
                                                       float* __restrict__ lse) {
-    flash_block<D, DP, DPV, QB, NSTG, 1, 0, 0, 16, 4, true>(blockIdx.x, Qp, Kp, Vt, O, H, Tq, Tk, Tqp, Tkp, d, ldo, obstride, 1, nqb, nullptr, lse);
+    flash_block<D, DP, DPV, QB, NSTG, 1, 0, 0, true>(blockIdx.x, Qp, Kp, Vt, O, H, Tq, Tk, Tqp, Tkp, d, ldo, obstride, 1, nqb, nullptr, lse);
 }
 // parts [S][Tq][HD] f16, lse [S][H][Tq] -> out [Tq][ldo] (first HD columns)
 __global__ void k_attn_merge(const _Float16* __restrict__ parts, const float* __restrict__ lse, _Float16* __restrict__ out, int S, int H, int Tq, int d, int ldo) {
@@ -924,33 +702,7 @@ __global__ void k_attn_merge(const _Float16* __restrict__ parts, const float* __
     }
 }
 
-static int launch_flash40p(const _Float16* Qp, const _Float16* Kp, const _Float16* Vt, _Float16* O, int B, int H, int Tq, int Tk, int Tqp, int Tkp,
-                           int ldo, long obs, int kv_div, hipStream_t st) {
-    constexpr int NW = 8, NSTG = 6;
-    const size_t lds = (size_t)NSTG * (KV_TILE * 56 * 2 + 64 * V_STRIDE * 2);
-    static bool set = false;
-    if (!set) { (void)hipFuncSetAttribute((const void*)k_flash40p<NW, NSTG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); set = true; }
-    const int nqb = Tqp / (NW * 32);
-    const bool prof = g_prof.on && (g_prof.dfilter == 0 || g_prof.dfilter == 40);
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (prof) {
-        if (g_prof.ev.size() > 8192) flash_prof_drain(false);
-        (void)hipEventCreate(&e0); (void)hipEventCreate(&e1); (void)hipEventRecord(e0, st);
-    }
-    hipLaunchKernelGGL((k_flash40p<NW, NSTG>), dim3(B * H * nqb), dim3(NW * 64), lds, st, Qp, Kp, Vt, O, H, Tq, Tk, Tqp, Tkp, ldo, obs, kv_div, nqb);
-    if (prof) { (void)hipEventRecord(e1, st); g_prof.ev.push_back(e0); g_prof.ev.push_back(e1); g_prof.flops += 4.0 * B * H * (double)Tq * Tk * 40; g_prof.launches++; }
-    return hipPeekAtLastError() == hipSuccess ? TCL_OK : TCL_ELAUNCH;
-}
-
 static inline int rup(int x, int m) { return (x + m - 1) / m * m; }
-// head_dim 40: PV on 32x32x16 MFMAs (1, round 5) or on 16x16x32 MFMAs behind permlane16 swaps (0, rounds 2-4).  The V^T panel's row skew belongs to
-// the 16x16x32 fragment read, so the packing and every head_dim-40 kernel variant of a process follow the same switch (TCL_FLASH_PV=16|32).
-static int g_pv32 = -1;
-static inline bool flash_pv32() {
-    if (g_pv32 < 0) { const char* e = getenv("TCL_FLASH_PV"); g_pv32 = e ? (atoi(e) == 32) : TCL_FLASH_PV32_DEFAULT; }
-    return g_pv32 != 0;
-}
-
 extern "C" {
 
 // Timing of the flash kernel launches (all head dims, or only head_dim == dfilter) with HIP events on their stream.
@@ -980,7 +732,8 @@ size_t tcl_attention_kv_bytes(int Bkv, int H, int Tk, int d) {
 // runs it on another stream than the attention itself passes pack_kv bit 2 (and bit 0 = 0) to tcl_attention_f16 afterwards.
 static int attention_pack(const void* q, int ldq, long qbs, const void* k, int ldk, long kbs, const void* v, int ldv, long vbs, int B, int H, int Tq,
                           int Tk, int d, float scale, int kv_div, int pack_q, int pack_kv, void* ws_q, void* ws_kv, hipStream_t st) {
-    const int Tqp = rup(Tq, 256), Tkp = rup(Tk, 64), DP = rup(d, 16), KS = DP + 8, DPV = d == 40 && !flash_pv32() ? TCL_DPV40 : rup(d, 32), Bkv = B / kv_div;
+    const int Tqp = rup(Tq, 256), Tkp = rup(Tk, 64), DP = rup(d, 16), KS = DP + 8, DPV = rup(d, 32), Bkv = B / kv_div;
+    const int skew = d == 40 ? 1 : 0;      // head_dim 40 (64 V^T rows, PV on 16x16x32 MFMAs) reads the skewed panel, see pack_vt_blk
     _Float16* Qp = (_Float16*)ws_q;
     _Float16* Kp = (_Float16*)ws_kv;
     _Float16* Vt = Kp + (((size_t)Bkv * H * Tkp * KS + 511) / 512) * 512;        // 1-KiB aligned
@@ -990,7 +743,7 @@ static int attention_pack(const void* q, int ldq, long qbs, const void* k, int l
         PackRows pq = {(const _Float16*)q, qbs, ldq, Tq, d, scale * 1.4426950408889634f, Qp, Tqp, DP, qc, -1};
         PackRows pk = {(const _Float16*)k, kbs, ldk, Tk, d, 1.f, Kp, Tkp, KS, kc, d == 40 ? d : -1};
         hipLaunchKernelGGL(k_pack_qkv, dim3(gq + gk + nt * Bkv * H), dim3(256), (size_t)64 * (DPV + 2) * 2, st, pq, pk, gq, gk, H, (const _Float16*)v, vbs, ldv, Tk, d, Vt,
-                           nt, DPV, d == 40 && !flash_pv32() ? 1 : 0);
+                           nt, DPV, skew);
         return hipPeekAtLastError() == hipSuccess ? TCL_OK : TCL_ELAUNCH;
     }
     if (pack_q)
@@ -999,7 +752,7 @@ static int attention_pack(const void* q, int ldq, long qbs, const void* k, int l
     if (pack_kv) {
         hipLaunchKernelGGL(k_pack_rows, dim3(stream_grid(kc, 256, 2)), dim3(256), 0, st, (const _Float16*)k, kbs, ldk, Tk, H, d, 1.f, Kp, Tkp, KS, kc,
                            d == 40 ? d : -1);
-        hipLaunchKernelGGL(k_pack_vt, dim3(Tkp / 64, Bkv * H), dim3(256), (size_t)64 * (DPV + 2) * 2, st, (const _Float16*)v, vbs, ldv, Tk, H, d, Vt, Tkp / 64, DPV, d == 40 && !flash_pv32() ? 1 : 0);
+        hipLaunchKernelGGL(k_pack_vt, dim3(Tkp / 64, Bkv * H), dim3(256), (size_t)64 * (DPV + 2) * 2, st, (const _Float16*)v, vbs, ldv, Tk, H, d, Vt, Tkp / 64, DPV, skew);
     }
     return hipPeekAtLastError() == hipSuccess ? TCL_OK : TCL_ELAUNCH;
 }
@@ -1019,10 +772,11 @@ int tcl_attention_pack_f16(const void* q, int ldq, long qbs, const void* k, int 
 int tcl_gemm_qkv_panels_f16(const void* x, long x_bs, const int* row_index, const void* W, int ne, int T, int H, int d, int K, int ldx, int ldw, float scale,
                             void* ws_q, void* ws_kv, hipStream_t st) {
     TCL_CHECK_ARG(x && W && ws_q && ws_kv && ne > 0 && T > 0 && H > 0 && (d == 40 || d == 80) && K > 0 && K % 32 == 0 && ldx >= K && ldw >= K);
-    const int Tqp = rup(T, 256), Tkp = rup(T, 64), DP = rup(d, 16), KS = DP + 8, DPV = d == 40 && !flash_pv32() ? TCL_DPV40 : rup(d, 32);
+    const int Tqp = rup(T, 256), Tkp = rup(T, 64), DP = rup(d, 16), KS = DP + 8, DPV = rup(d, 32);
+    const int skew = d == 40 ? 1 : 0;      // the layout attention_pack writes: head_dim 40 panels are skewed, 64 V^T rows
     _Float16* Kp = (_Float16*)ws_kv;
     _Float16* Vt = Kp + (((size_t)ne * H * Tkp * KS + 511) / 512) * 512;
-    const QkvPanel qp = {(_Float16*)ws_q, Kp, Vt, T, Tqp, Tkp, H, d, DP, KS, DPV, vt_tile_halves(DPV), d == 40 ? 40 : -1, d == 40 && !flash_pv32() ? 1 : 0,
+    const QkvPanel qp = {(_Float16*)ws_q, Kp, Vt, T, Tqp, Tkp, H, d, DP, KS, DPV, vt_tile_halves(DPV), d == 40 ? 40 : -1, skew,
                          scale * 1.4426950408889634f, row_index, x_bs};
     TclProfScope ps(TCL_PROF_GEMM, st, 2.0 * ne * T * 3.0 * H * d * K);
     return gemm_dma_qkv_panels((const _Float16*)x, (const _Float16*)W, ne, K, ldx, ldw, qp, st);
@@ -1043,49 +797,29 @@ int tcl_attention_f16(const void* q, int ldq, long qbs, const void* k, int ldk, 
     _Float16* Vt = Kp + (((size_t)Bkv * H * Tkp * KS + 511) / 512) * 512;        // 1-KiB aligned
     if (attention_pack(q, ldq, qbs, k, ldk, kbs, v, ldv, vbs, B, H, Tq, Tk, d, scale, kv_div, !prepacked, pack_kv, ws_q, ws_kv, st) != TCL_OK) return TCL_ELAUNCH;
     // d = 40: two query blocks per wave (shared K/V fragments), 4-slot ring and two tiles per barrier, 2 blocks per CU, when the grid still
-    // fills the chip several times over (750 TFLOP/s at T = 35.6k; the variants below reach 700 / 660 / 655 there); else one query block
-    // per wave on a 2-slot ring at 4 blocks per CU (107 VGPRs: four waves per SIMD hide each other's softmax; 582 vs 557 TFLOP/s at T = 8.9k
-    // for the 3-slot / 3-block variant).  d = 80: one block, 2-slot ring (50 KB LDS -> 3 blocks per CU)
+    // fills the chip several times over (750 TFLOP/s at T = 35.6k); else one query block per wave on a 2-slot ring at 4 blocks per CU (107 VGPRs:
+    // four waves per SIMD hide each other's softmax; 582 TFLOP/s at T = 8.9k).  d = 80: one block, 2-slot ring (50 KB LDS -> 3 blocks per CU)
     const bool qb2 = (long)B * (pair ? 2 : 1) * H * (Tqp / 256) >= 1024;
-    static const int var40 = getenv("TCL_FLASH40") ? atoi(getenv("TCL_FLASH40")) : 0;      // tuning hook: force a d = 40 variant (tools/ab)
-    if (d == 40 && var40 == 4 && TCL_DPV40 == 64 && !flash_pv32()) return launch_flash40p(Qp, Kp, Vt, (_Float16*)o, B, H, Tq, Tk, Tqp, Tkp, ldo, obs, kv_div, st);
-    if (d == 40 && var40 == 2) return launch_flash<40, 48, TCL_DPV40, 1, 3>(Qp, Kp, Vt, (_Float16*)o, B, H, Tq, Tk, Tqp, Tkp, d, ldo, obs, kv_div, st);
-    if (d == 40 && var40 == 3) return launch_flash<40, 48, TCL_DPV40, 1, 4, 2, 2>(Qp, Kp, Vt, (_Float16*)o, B, H, Tq, Tk, Tqp, Tkp, d, ldo, obs, kv_div, st);
-    if (d == 40 && flash_pv32()) {
-        if (qb2 && var40 == 0) {
-            int* flags = (int*)((char*)ws_q + (((size_t)B * H * Tqp * DP * 2 + 255) / 256) * 256);
-            int rc = launch_flash<40, 48, 64, 2, 4, 2, 0, 1, 32>(Qp, Kp, Vt, (_Float16*)o, B, H, Tq, Tk, Tqp, Tkp, d, ldo, obs, kv_div, st, flags);
-            if (rc == TCL_OK) rc = launch_flash<40, 48, 64, 2, 4, 2, 0, 0, 32>(Qp, Kp, Vt, (_Float16*)o, B, H, Tq, Tk, Tqp, Tkp, d, ldo, obs, kv_div, st, flags, false);
-            return rc;
-        }
-        return qb2 && var40 != 1 ? launch_flash<40, 48, 64, 2, 4, 2, 0, 0, 32>(Qp, Kp, Vt, (_Float16*)o, B, H, Tq, Tk, Tqp, Tkp, d, ldo, obs, kv_div, st)
-                                 : launch_flash<40, 48, 64, 1, 2, 1, 4, 0, 32>(Qp, Kp, Vt, (_Float16*)o, B, H, Tq, Tk, Tqp, Tkp, d, ldo, obs, kv_div, st);
-    }
+    // TCL_FLASH40: 0 = the dispatch above (default), 1 = always the one-query-block kernel, 5 = no speculative softmax (the exact two-query-block
+    // kernel alone: the kill switch; tools/micro/prec_attn.py, bench_attn_long.py).  Any other value behaves as 0.
+    static const int var40 = [] { const char* e = getenv("TCL_FLASH40"); const int v = e ? atoi(e) : 0; return v == 1 || v == 5 ? v : 0; }();
     if (d == 40 && qb2 && var40 == 0) {
         // speculative softmax (no row maxima in the loop), then the exact kernel over the blocks that flagged an f16 overflow of P (normally none:
         // its blocks read one flag and leave)
         int* flags = (int*)((char*)ws_q + (((size_t)B * H * Tqp * DP * 2 + 255) / 256) * 256);
-        int rc = launch_flash<40, 48, TCL_DPV40, 2, 4, 2, 0, 1>(Qp, Kp, Vt, (_Float16*)o, B, H, Tq, Tk, Tqp, Tkp, d, ldo, obs, kv_div, st, flags);
-        if (rc == TCL_OK) rc = launch_flash<40, 48, TCL_DPV40, 2, 4, 2>(Qp, Kp, Vt, (_Float16*)o, B, H, Tq, Tk, Tqp, Tkp, d, ldo, obs, kv_div, st, flags, false);
+        int rc = launch_flash<40, 48, 64, 2, 4, 2, 0, 1>(Qp, Kp, Vt, (_Float16*)o, B, H, Tq, Tk, Tqp, Tkp, d, ldo, obs, kv_div, st, flags);
+        if (rc == TCL_OK) rc = launch_flash<40, 48, 64, 2, 4, 2>(Qp, Kp, Vt, (_Float16*)o, B, H, Tq, Tk, Tqp, Tkp, d, ldo, obs, kv_div, st, flags, false);
         return rc;
     }
-    if (d == 40) return qb2 && var40 != 1 ? launch_flash<40, 48, TCL_DPV40, 2, 4, 2>(Qp, Kp, Vt, (_Float16*)o, B, H, Tq, Tk, Tqp, Tkp, d, ldo, obs, kv_div, st)
-                                          : launch_flash<40, 48, TCL_DPV40, 1, 2, 1, 4>(Qp, Kp, Vt, (_Float16*)o, B, H, Tq, Tk, Tqp, Tkp, d, ldo, obs, kv_div, st);
-    // d = 80: the 4-wave kernel moves 24.5 KiB of K / V^T image per 128 queries and tile through LDS-DMA -- ~40 B / clk / CU at three blocks per CU, the
-    // measured ceiling of that path (profiles/r3_lds_dma_rate.txt); 8 waves per block (TCL_FLASH80=8) halve the bytes per query.
-    static const int var80 = getenv("TCL_FLASH80") ? atoi(getenv("TCL_FLASH80")) : TCL_FLASH80_DEFAULT;
-    if (d == 80 && var80 == 8 && (long)B * H * (Tqp / 256) >= 256)
-        return launch_flash<80, 80, 96, 1, 2, 1, 1, 0, 16, 8>(Qp, Kp, Vt, (_Float16*)o, B, H, Tq, Tk, Tqp, Tkp, d, ldo, obs, kv_div, st);
+    if (d == 40) return qb2 && var40 != 1 ? launch_flash<40, 48, 64, 2, 4, 2>(Qp, Kp, Vt, (_Float16*)o, B, H, Tq, Tk, Tqp, Tkp, d, ldo, obs, kv_div, st)
+                                          : launch_flash<40, 48, 64, 1, 2, 1, 4>(Qp, Kp, Vt, (_Float16*)o, B, H, Tq, Tk, Tqp, Tkp, d, ldo, obs, kv_div, st);
+    // d = 80: the kernel moves 24.5 KiB of K / V^T image per 128 queries and tile through LDS-DMA -- ~40 B / clk / CU at three blocks per CU, the
+    // measured ceiling of that path (profiles/r3_lds_dma_rate.txt)
     if (d == 80) return launch_flash<80, 80, 96, 1, 2>(Qp, Kp, Vt, (_Float16*)o, B, H, Tq, Tk, Tqp, Tkp, d, ldo, obs, kv_div, st);
-    if (d == 128) {   // MemFlowNet memory read: ONE head, ONE entry -- at 1280x720 14 400 queries are 114 blocks of 128 for 256 CUs (profiles/r6_memflow_kernel_stats_before.txt:
-        // 507 us per call, 0.17 of peak).  Round 6 tried 2-wave blocks (64 queries, twice the blocks; same per-wave work and bits): the frame pair got SLOWER, 47.7
-        // against 45.9 ms on one box (profiles/r6_ab_memflow_graph_nw.txt) -- a 2-wave block issues twice the LDS-DMA pieces per wave and hides less of it; the
-        // kernel is not simply grid-limited.  TCL_FLASH128_NW=2 selects that form; 4 waves stay the default.
-        static const int nw128 = getenv("TCL_FLASH128_NW") ? atoi(getenv("TCL_FLASH128_NW")) : 4;
-        if (nw128 == 2)
-            return launch_flash<128, 128, 128, 1, 2, 1, 0, 0, 16, 2>(Qp, Kp, Vt, (_Float16*)o, B, H, Tq, Tk, Tqp, Tkp, d, ldo, obs, kv_div, st);
-        return launch_flash<128, 128, 128, 1, 2>(Qp, Kp, Vt, (_Float16*)o, B, H, Tq, Tk, Tqp, Tkp, d, ldo, obs, kv_div, st);
-    }
+    // d = 128, MemFlowNet memory read: ONE head, ONE entry -- at 1280x720 14 400 queries are 114 blocks of 128 for 256 CUs (507 us per call, 0.17 of peak,
+    // profiles/r6_memflow_kernel_stats_before.txt).  2-wave blocks (twice the blocks) made the frame pair SLOWER, 47.7 against 45.9 ms
+    // (profiles/r6_ab_memflow_graph_nw.txt): the kernel is not simply grid-limited (tcl_attention_splitkv_f16 below cuts the keys instead)
+    if (d == 128) return launch_flash<128, 128, 128, 1, 2>(Qp, Kp, Vt, (_Float16*)o, B, H, Tq, Tk, Tqp, Tkp, d, ldo, obs, kv_div, st);
     return launch_flash<160, 160, 160, 1, 3>(Qp, Kp, Vt, (_Float16*)o, B, H, Tq, Tk, Tqp, Tkp, d, ldo, obs, kv_div, st);
 }
 

@@ -3,21 +3,17 @@
 // generate.py:342-347 -> diffusers UNet2DConditionModel convs / Linears).
 //
 // Block = 512 threads = 8 waves = exactly two waves per SIMD, one block per CU.  Block tile (WM*MT*32) x (WN*NT*32), K step 32.
-// The waves form two groups (waves 0-3 / 4-7: wave w and w+4 share a SIMD) that run the SAME program shifted by one barrier
-// interval, so in every interval one group issues its MFMAs while the other one does its LDS fragment reads and issues the
-// LDS-DMA (global_load_lds_dwordx4) pieces of a later stage: the matrix pipe of every SIMD is fed back to back and the
-// loads/ds_reads ride in its shadow.  Per wave and K step t:
-//      G0:        { bar  L(t)         bar  M(t) W(t+1) } x nk   bar
-//      G1:  bar   { bar  L(t) W(t+1)  bar  M(t)        } x nk          (2 nk + 1 barriers each)
-//   L(t): ds_read the 2 x (MT+NT) b128 fragments of stage t, issue the NP DMA pieces of stage t+PD, s_waitcnt lgkmcnt(0)
-//   M(t): 2 x MT x NT MFMA 32x32x16 on the fragments (s_setprio 1)
-//   W(t+1): s_waitcnt vmcnt((PD-1)*NP)  -- my pieces of stage t+1 have landed; later stages stay in flight (never drained)
-// Invariants (b_k = k-th block barrier; G0 runs L(t) in (b_2t, b_2t+1), G1 in (b_2t+1, b_2t+2)):
-//   RAW  every wave executes W(t) before b_2t, every read of stage t comes after b_2t.
-//   WAR  stage t+PD reuses the ring slot of stage t-1 (PD+1 slots); the last reads of stage t-1 (G1, L(t-1)) are retired by
-//        the lgkmcnt(0) that precedes b_2t; the earliest DMA into that slot is issued by G0 in L(t), after b_2t.
+// The waves form two groups (waves 0-3 / 4-7: wave w and w+4 share a SIMD) that run the SAME program shifted against each other, so that
+// one group's MFMAs cover the other's LDS fragment reads, and the LDS-DMA pieces (16 rows x 64 B = 1 KiB per wave instruction) of the stage
+// PD = 3 K steps ahead go out BETWEEN the MFMAs, one piece every nM / NP matrix instructions: the matrix pipe of every SIMD is fed back to
+// back and the loads ride in its shadow.  Ring of PD + 1 = 4 stages; a wave waits with a counted vmcnt for its own pieces of the next stage
+// and never drains the queue.  Two schedules over the same tiles, ring, swizzle, K order and epilogue (bit-identical results):
+//   k_gemm8p (default): half-step pipeline, ONE block barrier per K step, buffer-addressed DMA (32-bit offsets; out-of-range rows read zeros
+//                       through the descriptor's bounds check).  Invariants at the kernel.
+//   k_gemm8s          : two barriers per K step (L = reads + addresses | M = MFMAs + DMA), 64-bit source pointers and a zero page: operands
+//                       of 4 GiB and more, and convolutions with the nearest up-sampling in the gather.  Invariants at the kernel.
 // LDS rows are 64 B (32 halves), 16-B chunk index XOR-swizzled with (row>>2)&3 on the DMA source address and on the ds_read
-// address (conflict-free b128 reads, guide rule 21).  Out-of-range rows / conv taps read a zero page.
+// address (conflict-free b128 reads, guide rule 21).
 // Epilogue: each wave stages its own 32-row strips through a private LDS region (no block barrier) and writes whole 16-B
 // row chunks (+ residual).
 #include "common.h"
@@ -91,160 +87,15 @@ __device__ __forceinline__ void g8_epilogue(float16v (&acc)[MT][NT], char* smem,
     }
 }
 
-template <int MT, int NT, int WM, int WN, bool CONV>
-__global__ __launch_bounds__(512) void k_gemm8(const _Float16* __restrict__ A, const _Float16* __restrict__ W, const _Float16* __restrict__ bias,
-                                               const _Float16* __restrict__ resid, _Float16* __restrict__ C, int M, int N, int K, int lda, int ldw,
-                                               int ldc, int ldr, int act, ConvP cp, int tiles_m, int tiles_n) {
-    static_assert(WM * WN == 8, "8 waves");
-    constexpr int BM = WM * MT * 32, BN = WN * NT * 32, KB = 32, ROWB = 64;
-    constexpr int NS = 4;                                      // ring slots: stage t in use, t+1 .. t+3 in flight
-    constexpr int A_P = BM / 16, B_P = BN / 16;                // 1-KiB pieces (16 rows x 64 B) per operand and stage
-    constexpr int NP = (A_P + B_P + 7) / 8;                    // pieces per wave and stage (a dummy piece pads the last round)
-    constexpr int NPA = A_P / 8, NPB = NP - NPA;               // rounds that carry A pieces (A_P % 8 == 0) / W pieces
-    constexpr int STAGE = (A_P + B_P) * 1024;
-    static_assert(A_P % 8 == 0, "BM must be a multiple of 128");
-    extern __shared__ __attribute__((aligned(16))) char smem[];     // NS stages, then a 1-KiB dump for the dummy pieces
-
-    const int bid = blockIdx.x, xcd = bid & 7, j = bid >> 3;
-    const int tn = j % tiles_n, tm = (j / tiles_n) * 8 + xcd;
-    if (tm >= tiles_m) return;
-    const int m0 = tm * BM, n0 = tn * BN;
-    const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6), grp = wid >> 2;
-    const int wm = wid % WM, wn = wid / WM;
-
-    // ---- DMA descriptors: round i handles piece q = wid + 8 i; lane -> row rr = lane>>2 of the piece, LDS chunk lane&3.
-    // Invalid rows (m >= M, n >= N) and the dummy piece point at the zero page.
-    const int rr = lane >> 2, csrc = ((lane & 3) ^ ((rr >> 2) & 3)) * 8;
-    const _Float16* zero = (const _Float16*)g_zero_page8;
-    const _Float16* ap[NPA]; int a_oy[NPA], a_ox[NPA];          // dense: row pointer (k advances); conv: image base + (oy, ox)
-#pragma unroll
-    for (int i = 0; i < NPA; ++i) {
-        const int m = m0 + (wid + 8 * i) * 16 + rr;
-        if (!CONV) { ap[i] = m < M ? A + (long)m * lda + csrc : nullptr; a_oy[i] = a_ox[i] = 0; }
-        else {
-            int hw = cp.Hout * cp.Wout, b = m / hw, r = m - b * hw, oy = r / cp.Wout, ox = r - oy * cp.Wout;
-            ap[i] = A + (long)b * cp.Hin * cp.Win * cp.Cin + csrc;
-            a_oy[i] = m < M ? oy * cp.stride - cp.pad : -(1 << 20); a_ox[i] = ox * cp.stride - cp.pad;
-        }
-    }
-    const _Float16* wp[NPB]; int wdst[NPB];
-#pragma unroll
-    for (int i = 0; i < NPB; ++i) {
-        const int q = wid + 8 * (i + NPA), n = n0 + (q - A_P) * 16 + rr;
-        const bool real = q < A_P + B_P;
-        wp[i] = (real && n < N) ? W + (long)n * ldw + csrc : nullptr;
-        wdst[i] = real ? q * 1024 : NS * STAGE;                  // dummy piece -> dump area
-    }
-
-    // issue the pieces of stage KT, then those of stage KT+1 (when < nk): the second 64-B halves of the same 128-B lines follow
-    // within a few instructions, while the first requests are still pending in the vector L1
-#define G8_GLDS(SRC, DST) __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(SRC), (__attribute__((address_space(3))) void*)(DST), 16, 0, 0)
-#define G8_ISSUE2(KT)                                                                                                         \
-    {                                                                                                                         \
-        int k0_ = (KT) * KB;                                                                                                  \
-        const int nst_ = (KT) + 1 < nk ? 2 : 1;                                                                               \
-        int tdy_ = 0, tdx_ = 0, c0_ = k0_;                                                                                    \
-        if (CONV) { const int tap_ = conv_kmap(k0_, cp.Cin, c0_); tdy_ = tap_ / 3; tdx_ = tap_ - tdy_ * 3; k0_ = tap_ * cp.Cin + c0_; }   \
-        const _Float16* sa_[NPA];                                                                                             \
-        _Pragma("unroll") for (int i = 0; i < NPA; ++i) {                                                                    \
-            if (!CONV) sa_[i] = ap[i] ? ap[i] + k0_ : nullptr;                                                                \
-            else {                                                                                                            \
-                int iy_ = a_oy[i] + tdy_, ix_ = a_ox[i] + tdx_;                                                               \
-                const bool in_ = iy_ >= 0 && iy_ < cp.Hup && ix_ >= 0 && ix_ < cp.Wup;                                        \
-                if (cp.Hup != cp.Hin || cp.Wup != cp.Win) { iy_ = min((int)floorf(iy_ * cp.sy), cp.Hin - 1); ix_ = min((int)floorf(ix_ * cp.sx), cp.Win - 1); } \
-                sa_[i] = in_ ? ap[i] + ((long)iy_ * cp.Win + ix_) * cp.Cin + c0_ : nullptr;                                   \
-            }                                                                                                                 \
-        }                                                                                                                     \
-        for (int h_ = 0; h_ < nst_; ++h_) {                                                                                   \
-            char* sb_ = smem + (((KT) + h_) % NS) * STAGE;                                                                    \
-            _Pragma("unroll") for (int i = 0; i < NPA; ++i) G8_GLDS(sa_[i] ? sa_[i] + h_ * KB : zero, sb_ + (wid + 8 * i) * 1024); \
-            _Pragma("unroll") for (int i = 0; i < NPB; ++i) G8_GLDS(wp[i] ? wp[i] + k0_ + h_ * KB : zero, (wdst[i] == NS * STAGE ? smem : sb_) + wdst[i]); \
-        }                                                                                                                     \
-    }
-
-    float16v acc[MT][NT];
-#pragma unroll
-    for (int a = 0; a < MT; ++a)
-#pragma unroll
-        for (int b = 0; b < NT; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
-
-    const int nk = K / KB;
-    const int frow = lane & 31, fh = lane >> 5;
-    half8 fa[2][MT], fb[2][NT];
-    // fragment read: tile row R (lane&31 within a 32-row block), logical chunk 2*ks + (lane>>5), physical chunk ^ ((R>>2)&3)
-#define G8_READ(KT)                                                                                                           \
-    {                                                                                                                         \
-        const char* ab_ = smem + ((KT) % NS) * STAGE + (wm * MT * 32) * ROWB;                                                 \
-        const char* bb_ = smem + ((KT) % NS) * STAGE + BM * ROWB + (wn * NT * 32) * ROWB;                                     \
-        _Pragma("unroll") for (int ks = 0; ks < 2; ++ks) {                                                                   \
-            _Pragma("unroll") for (int a = 0; a < MT; ++a) { int R = a * 32 + frow; fa[ks][a] = *(const half8*)(ab_ + R * ROWB + (((2 * ks + fh) ^ ((R >> 2) & 3)) << 4)); } \
-            _Pragma("unroll") for (int b = 0; b < NT; ++b) { int R = b * 32 + frow; fb[ks][b] = *(const half8*)(bb_ + R * ROWB + (((2 * ks + fh) ^ ((R >> 2) & 3)) << 4)); } \
-        }                                                                                                                     \
-    }
-#define G8_MFMA()                                                                                                             \
-    {                                                                                                                         \
-        __builtin_amdgcn_s_setprio(1);                                                                                        \
-        _Pragma("unroll") for (int ks = 0; ks < 2; ++ks)                                                                      \
-            _Pragma("unroll") for (int a = 0; a < MT; ++a)                                                                    \
-                _Pragma("unroll") for (int b = 0; b < NT; ++b) acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[ks][a], fb[ks][b], acc[a][b], 0, 0, 0); \
-        __builtin_amdgcn_s_setprio(0);                                                                                        \
-    }
-    // W(T) executed at the end of step T-1's interval: my pieces of stage T have landed.  Issued so far: stages <= T+2 when T-1 is
-    // even (the pair (T+1, T+2) went out in L(T-1)), <= T+1 when T-1 is odd; later stages stay in flight.
-#define G8_WAIT(T)                                                                                                            \
-    {                                                                                                                         \
-        const int rem_ = min(((T) & 1) ? (T) + 2 : (T) + 1, nk - 1) - (T);                                                    \
-        if (rem_ >= 2) wait_vm<2 * NP>(); else if (rem_ == 1) wait_vm<NP>(); else wait_vm<0>();                               \
-    }
-#define G8_LSEG(T)                                                                                                            \
-    {                                                                                                                         \
-        G8_READ(T);                                                                                                           \
-        if (!((T) & 1) && (T) + 2 < nk) G8_ISSUE2((T) + 2);                                                                   \
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                                    \
-    }
-
-    G8_ISSUE2(0);
-    if (nk > 1) wait_vm<NP>(); else wait_vm<0>();              // W(0): stage 1 may still be in flight
-    if (grp == 0) {
-        for (int t = 0; t < nk; ++t) {
-            __builtin_amdgcn_s_barrier();
-            G8_LSEG(t);
-            __builtin_amdgcn_s_barrier();
-            G8_MFMA();
-            if (t + 1 < nk) G8_WAIT(t + 1);
-        }
-        __builtin_amdgcn_s_barrier();
-    } else {
-        __builtin_amdgcn_s_barrier();                 // one interval behind group 0
-        for (int t = 0; t < nk; ++t) {
-            __builtin_amdgcn_s_barrier();
-            G8_LSEG(t);
-            if (t + 1 < nk) G8_WAIT(t + 1);
-            __builtin_amdgcn_s_barrier();
-            G8_MFMA();
-        }
-    }
-#undef G8_ISSUE2
-#undef G8_GLDS
-#undef G8_READ
-#undef G8_MFMA
-#undef G8_WAIT
-#undef G8_LSEG
-
-    g8_epilogue<MT, NT, WM, WN>(acc, smem, bias, resid, C, M, N, ldc, ldr, act, m0, n0, wid, lane, wm, wn);
-}
-
 // ---------------------------------------------------------------------------------------------------------------------
-// Schedule 2 ("DMA in the MFMA shadow", round 3).  Same tiles, ring, swizzle, K order and epilogue as k_gemm8 -- so the results are
-// bit-identical -- but the LDS-DMA pieces of the stage PD = 3 steps ahead are issued INSIDE the MFMA segment, one piece every
-// nM / PM matrix instructions, with their source addresses computed beforehand in the (short) LDS-read segment:
+// Schedule 1 (k_gemm8s, "DMA in the MFMA shadow", round 3).  Two barrier intervals per K step; the LDS-DMA pieces of the stage PD = 3 steps
+// ahead are issued INSIDE the MFMA segment, one piece every nM / PM matrix instructions, with their source addresses computed beforehand
+// in the (short) LDS-read segment:
 //      G0:        { bar  L(t) P(t+3)          bar  M(t)+D(t+3) W0(t+1) } x nk   bar
 //      G1:  bar   { bar  L(t) P(t+3) W1(t+1)  bar  M(t)+D(t+3)         } x nk
 //   P(s): per-lane source pointers of my NP pieces of stage s (VALU / SALU only; conv: tap, bounds, nearest-upsample mapping)
 //   D(s): the NP glds instructions (the first NL of them already in the L segment), pinned between the MFMAs (sched_barrier)
-// Measured reason (r2 PMC: waves 52 % parked, matrix pipe 27-50 %): an LDS-DMA piece costs 100-185 issue cycles inside a segment that
+// Measured reason (r2 PMC of the round-2 ping-pong that issued its DMA in the read segment: waves 52 % parked, matrix pipe 27-50 %): an LDS-DMA piece costs 100-185 issue cycles inside a segment that
 // also carries 12-14 ds_read_b128, so the L segment (5 pieces + reads) was longer than the partner's 16-20 MFMAs and the matrix pipe
 // waited for it; among bare MFMAs a piece costs ~60 cycles, half of which the running MFMA covers.
 // Invariants (G0 runs L(t) in I(2t), M(t) in I(2t+1); G1 one interval later; I(k) = (b_k, b_k+1)):
@@ -450,8 +301,8 @@ __global__ __launch_bounds__(512) void k_gemm8s(const _Float16* __restrict__ A, 
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// Schedule 5 (k_gemm8p, round 3): software-pipelined half steps, ONE block barrier per K step, buffer-addressed LDS-DMA.  Same tiles,
-// ring, swizzle, K order and epilogue as k_gemm8 (bit-identical results).
+// Schedule 2 (k_gemm8p, round 3; the default): software-pipelined half steps, ONE block barrier per K step, buffer-addressed LDS-DMA.  Same
+// tiles, ring, swizzle, K order and epilogue as k_gemm8s (bit-identical results).
 //
 // Why (segment timers of tools/micro/gemm8_lab.hip on k_gemm8s, 256 x 320 tile, cycles per K step of 32): the two-barrier ping-pong
 // spends 2 x (640 MFMA + 5 x 50 DMA issue) in the two MFMA segments plus 110-170 idle cycles per barrier hand-over, and the LDS-read +
@@ -665,15 +516,15 @@ __global__ __launch_bounds__(512) void k_gemm8p(const _Float16* __restrict__ A, 
 }
 
 #ifndef G8_LAB_ONLY   // tools/micro/gemm8_lab.hip instantiates single kernels itself
-// schedule: 0 = k_gemm8 (round-2 ping-pong, DMA in the LDS-read segment), 1 = k_gemm8s (two barriers, DMA in the MFMA segment), 2 = k_gemm8p
-// (half-step pipeline, one barrier per step, buffer-addressed DMA; default).  TCL_GEMM8_SCHED overrides it (experiments; bit-identical results).
+// schedule: 1 = k_gemm8s (two barriers, DMA in the MFMA segment), 2 = k_gemm8p (half-step pipeline, one barrier per step, buffer-addressed DMA;
+// default).  TCL_GEMM8_SCHED = 1 forces k_gemm8s (experiments; bit-identical results); any other value is the default.
 // Measured on the metric's shapes (tools/micro/gemm8_lab.hip, profiles/r3_gemm8_lab.txt): dense K >= 640 +17...33 %, 3x3 convs +6...10 % over
-// schedule 0; variants that lost and are not in the tree: two early pieces in the read segment (-4 %), static / alternating s_setprio
-// (+-1 %), a 24-cycle stagger of the four SIMDs behind each barrier (-8 %).
+// the round-2 ping-pong (DMA in the LDS-read segment); variants that lost and are not in the tree: that ping-pong itself, two early pieces in
+// the read segment (-4 %), static / alternating s_setprio (+-1 %), a 24-cycle stagger of the four SIMDs behind each barrier (-8 %).
 int g_gemm8_sched = -1;
 static int gemm8_sched() {
     if (g_gemm8_sched < 0) { const char* e = getenv("TCL_GEMM8_SCHED"); g_gemm8_sched = e ? atoi(e) : 2; }
-    return g_gemm8_sched;
+    return g_gemm8_sched == 1 ? 1 : 2;
 }
 
 template <int MT, int NT, int WM, int WN>
@@ -684,8 +535,6 @@ static int launch8(const _Float16* A, const _Float16* W, const _Float16* bias, c
     const size_t ring = (size_t)4 * (BM + BN) * 64 + 1024, epi = (size_t)8 * 32 * (NT * 32 + 8) * 2, lds = ring > epi ? ring : epi;
     static bool attr_set = false;
     if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)k_gemm8<MT, NT, WM, WN, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute((const void*)k_gemm8<MT, NT, WM, WN, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         (void)hipFuncSetAttribute((const void*)k_gemm8s<MT, NT, WM, WN, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         (void)hipFuncSetAttribute((const void*)k_gemm8s<MT, NT, WM, WN, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         (void)hipFuncSetAttribute((const void*)k_gemm8p<MT, NT, WM, WN, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -700,8 +549,7 @@ static int launch8(const _Float16* A, const _Float16* W, const _Float16* bias, c
     if (sched == 2 && (a_bytes >= 0xffffff00ull || w_bytes >= 0xffffff00ull || (cp.conv && (cp.Hup != cp.Hin || cp.Wup != cp.Win)))) sched = 1;
 #define G8_LAUNCH(KERN, ...) hipLaunchKernelGGL((KERN), grid, dim3(512), lds, st, A, W, bias, resid, C, M, N, K, lda, ldw, ldc, ldr, act, cp, tm, tn, ##__VA_ARGS__)
     if (sched == 2) { if (cp.conv) G8_LAUNCH((k_gemm8p<MT, NT, WM, WN, true>), (unsigned)a_bytes, (unsigned)w_bytes); else G8_LAUNCH((k_gemm8p<MT, NT, WM, WN, false>), (unsigned)a_bytes, (unsigned)w_bytes); }
-    else if (sched == 1) { if (cp.conv) G8_LAUNCH((k_gemm8s<MT, NT, WM, WN, true>)); else G8_LAUNCH((k_gemm8s<MT, NT, WM, WN, false>)); }
-    else { if (cp.conv) G8_LAUNCH((k_gemm8<MT, NT, WM, WN, true>)); else G8_LAUNCH((k_gemm8<MT, NT, WM, WN, false>)); }
+    else { if (cp.conv) G8_LAUNCH((k_gemm8s<MT, NT, WM, WN, true>)); else G8_LAUNCH((k_gemm8s<MT, NT, WM, WN, false>)); }
 #undef G8_LAUNCH
     return hipPeekAtLastError() == hipSuccess ? TCL_OK : TCL_ELAUNCH;
 }

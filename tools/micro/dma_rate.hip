@@ -1,7 +1,7 @@
 // How fast can one CU move L2-resident operand tiles into LDS?  (stand-alone: hipcc --offload-arch=gfx950 -O3 tools/micro/dma_rate.hip)
 // 256 blocks x 512 threads (8 waves, one block per CU).  Every wave moves NIT pieces of 1 KiB from a per-block window of a row-major
 // f16 matrix (row stride LD bytes) into a 128 KiB LDS ring; modes:
-//   0  LDS-DMA, piece = 16 rows x 64 B   (k_gemm8's K = 32 stages)
+//   0  LDS-DMA, piece = 16 rows x 64 B   (k_gemm8p's K = 32 stages)
 //   1  LDS-DMA, piece =  8 rows x 128 B  (full cache lines, K = 64 stages)
 //   2  LDS-DMA, every lane reads the same 16 B (no fetch traffic at all: the LDS-write side alone)
 //   3  LDS-DMA through a buffer descriptor, 16 rows x 64 B

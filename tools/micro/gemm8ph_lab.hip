@@ -1,5 +1,5 @@
 // Lab: the "256^2 8-phase" GEMM template of /opt/skills/guides/cdna_hip_programming.md:612-660 written out for f16, timed
-// beside the product's k_gemm8 / k_gemm8p on the same uniform-random operands.
+// beside the product's k_gemm8s / k_gemm8p on the same uniform-random operands.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -Wno-comment tools/micro/gemm8ph_lab.hip -o tools/micro/bin/gemm8ph_lab
 // Template as written: 256 x 256 tile, BK = 64, 8 waves as 2 (M) x 4 (N), mfma_f32_16x16x32_f16, LDS = 2 buffers x {A, B} x 2 half-tiles of
 // [128 rows][64 k] (128-B rows, 16 KiB each, 128 KiB), st_16x32 swizzle on the DMA source address and on the ds_read address, one half-tile
@@ -238,11 +238,11 @@ int main(int argc, char** argv) {
         const double flop = 2.0 * M * N * K;
         printf("== %d x %d x %d  (%.1f GFLOP), uniform random [-1,1) operands\n", M, N, K, flop / 1e9);
         ConvP cp = {};
-        // variants: 0 = k_gemm8 256x256 (round-2 ping-pong), 1 = k_gemm8p 256x256 (product default), 2 = 8-phase st_16x32 + setprio (as written),
+        // variants: 0 = k_gemm8s 256x256 (two barriers per K step), 1 = k_gemm8p 256x256 (product default), 2 = 8-phase st_16x32 + setprio (as written),
         //           3 = 8-phase st_16x32 without setprio, 4 = 8-phase with the conflict-free swizzle + setprio
-        const char* names[7] = {"k_gemm8  256x256 (r2 ping-pong)", "k_gemm8p 256x256 (product)", "8-phase st_16x32 setprio (guide)", "8-phase st_16x32 no setprio", "8-phase full swizzle setprio", "8-phase st_16x32, 4-row bands", "8-phase st_16x32, 8-row bands"};
+        const char* names[7] = {"k_gemm8s 256x256 (two barriers)", "k_gemm8p 256x256 (product)", "8-phase st_16x32 setprio (guide)", "8-phase st_16x32 no setprio", "8-phase full swizzle setprio", "8-phase st_16x32, 4-row bands", "8-phase st_16x32, 8-row bands"};
         auto launch = [&](int v, _Float16* C) {
-            if (v == 0) { g_gemm8_sched = 0; gemm8_dispatch(3, A, W, nullptr, nullptr, C, M, N, K, K, K, N, N, 0, cp, st); }
+            if (v == 0) { g_gemm8_sched = 1; gemm8_dispatch(3, A, W, nullptr, nullptr, C, M, N, K, K, K, N, N, 0, cp, st); }
             else if (v == 1) { g_gemm8_sched = 2; gemm8_dispatch(3, A, W, nullptr, nullptr, C, M, N, K, K, K, N, N, 0, cp, st); }
             else if (v == 2) run_ph<0, 1>(A, W, C, M, N, K, st);
             else if (v == 3) run_ph<0, 0>(A, W, C, M, N, K, st);
