@@ -382,6 +382,39 @@ int tcl_eval_warp_mask_u8(const void* edit, const float* fut, const float* past,
 size_t tcl_eval_ssim_workspace_bytes(int B, int H, int W);
 int tcl_eval_ssim_u8(const void* x, const void* y, double* out, int B, int H, int W, void* ws, hipStream_t st);
 
+/* ---- clip-frame / clip-text (evaluate.py:39-49,119: clip.load("ViT-B/32"); utils/evaluation/eval_utils.py:129-161 clip_text / clip_frame); csrc/clip.hip.
+ *   The model is OpenAI CLIP (clip/model.py: VisionTransformer, Transformer / ResidualAttentionBlock, QuickGELU, CLIP.encode_image / encode_text); its
+ *   Linears and LayerNorms run on tcl_gemm_f16 / tcl_layernorm_f16, the entry points below are the rest.
+ * tcl_clip_resize_geometry: the sizes of `preprocess` (clip.py _transform(n_px): Resize(n_px, BICUBIC) -> CenterCrop(n_px)) for an H x W frame:
+ *   h_geom (HOST, 4 ints) = resized height, resized width (short side `side`, long side int(side * long / short)), crop top, crop left
+ *   (int(round((size - side) / 2.0)), round half to even).
+ * tcl_clip_preprocess_u8: `preprocess(pil)` of eval_utils.py:137,151 on frames [N,H,W,3] u8: PIL Image.resize(BICUBIC) restated in its integer
+ *   arithmetic (a = -0.5, support widened by the down-scale factor, normalised coefficients rounded to 22-bit fixed point, horizontal pass rounded and
+ *   clipped to u8 before the vertical pass), centre crop, / 255, (x - mean) / std with CLIP's constants.  Only the cropped window is computed.
+ *   crop [N,side,side,3] u8 (may be NULL): the resized and cropped image, bit-identical to PIL.  patches [N, (side/patch)^2, 3*patch*patch] f16 (may
+ *   be NULL): the normalised pixels as patch rows in the column order of visual.conv1.weight.reshape(width, -1) (channel, row, column), so that
+ *   VisionTransformer.conv1 is one tcl_gemm_f16.  Down-scale factors up to about 17. */
+int tcl_clip_resize_geometry(int H, int W, int side, int* h_geom);
+int tcl_clip_preprocess_u8(const void* frames, void* crop, void* patches, int N, int H, int W, int side, int patch, hipStream_t st);
+/* tcl_clip_attention_f16: nn.MultiheadAttention of ResidualAttentionBlock.attention (self-attention, need_weights=False) after its in_proj: qkv
+ *   [B*T, 3*H*d] f16 = [q | k | v], head hh at columns hh*d of each third, read in place; out [B*T, H*d] f16 = softmax(scale q k^T (+ causal mask)) v,
+ *   heads concatenated (the operand of out_proj).  causal: key j > query i is masked (CLIP.build_attention_mask, the text tower).  One workgroup per
+ *   (sample, head) with the head's K and V in LDS, exact softmax.  d % 16 == 0, d <= 128, T <= 288 and K, V within 160 KB of LDS (d = 64: T <= 288;
+ *   d = 80: T <= 288); anything else returns TCL_EINVAL. */
+int tcl_clip_attention_f16(const void* qkv, void* out, int B, int T, int H, int d, float scale, int causal, hipStream_t st);
+/* tcl_clip_embed_f16: the rows that enter a tower, out [B*T, W] f16.  ids == NULL (VisionTransformer.forward): row 0 of every sample = cls [W], rows
+ *   1 .. T-1 = patch [B, T-1, W] (the conv1 GEMM's output), + pos [T, W], then LayerNorm(gamma, beta, eps) = ln_pre.  ids != NULL (CLIP.encode_text):
+ *   table[ids[b, t]] + pos[t] (ids int32 [B,T], table [vocab, W]).  gamma / beta NULL: no LayerNorm.  f32 up to the one rounding; W <= 2048. */
+int tcl_clip_embed_f16(const void* patch, const void* cls, const int* ids, const void* table, const void* pos, const void* gamma, const void* beta,
+                       void* out, int B, int T, int W, int vocab, float eps, hipStream_t st);
+/* tcl_clip_quick_gelu_f16: QuickGELU (clip/model.py: x * sigmoid(1.702 * x)), n f16 elements, n % 8 == 0; y may be x. */
+int tcl_clip_quick_gelu_f16(const void* x, void* y, long n, hipStream_t st);
+/* tcl_clip_scores: feats [N,D] f32, text [D] f32 (may be NULL) -> out2 (device, 2 doubles): out2[0] = clip_frame (eval_utils.py:156-159: the sum of the
+ *   off-diagonal entries of the cosine matrix / (N (N - 1))), out2[1] = clip_text (eval_utils.py:140-142: the mean cosine of the rows to `text`; 0 when
+ *   text is NULL).  f64 sums in a fixed order, no atomics: the same input gives the same bits.  ws: tcl_clip_scores_workspace_bytes(N) bytes. */
+size_t tcl_clip_scores_workspace_bytes(int N);
+int tcl_clip_scores(const float* feats, const float* text, int N, int D, double* out2, void* ws, hipStream_t st);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,8 +4,12 @@ For every pair of neighbouring frames (i, i+1) of a relit video, RAFT estimates 
 (20 iterations, test mode, the frames in 0..255 and replicate-padded to multiples of 8, the flows unpadded); the relit frame i is warped onto
 frame i+1 along the backward flow with a cubic remap, pixels failing the forward-backward consistency check are zeroed in both frames, and the
 score of the pair is the SSIM of the two uint8 images.  The metric is the mean over the pairs.  RAFT is `raft.RAFTEngine` through
-`raft.estimate_flows_raft` (fwd = fut[i], bwd = past[i+1]); the warp, mask and SSIM are the kernels of csrc/evaluate.hip.  CLIP-frame, CLIP-text,
-PickScore and FrameLPIPS are not computed (their models are not part of this project).
+`raft.estimate_flows_raft` (fwd = fut[i], bwd = past[i+1]); the warp, mask and SSIM are the kernels of csrc/evaluate.hip.
+
+clip-frame and clip-text (evaluate.py:39-49, eval_utils.py:129-161) are computed when a CLIP checkpoint is configured (`models.clip` / --clip): the
+frames go through `clip.CLIPEngine.encode_image`, clip-frame is the mean off-diagonal cosine between the frame features and clip-text the mean cosine
+of the frame features to the prompt's text feature (tcl_clip_scores).  With no CLIP path nothing of it is loaded and the two figures are listed as not
+computed, as before.  PickScore and FrameLPIPS are not computed (their models are not part of this project).
 """
 import math
 import os
@@ -21,6 +25,21 @@ EDIT_STEMS = ("output_opt", "output")          # evaluate.py:27: output_opt.mp4 
 SOURCE_STEM = "output_gt"                       # evaluate.py:28
 VIDEO_EXTS = (".mp4", ".avi")                   # .avi: what dataparser.save_video writes without an H.264 encoder
 NOT_COMPUTED = ("clip-frame", "clip-text", "pick-score")
+
+
+def not_computed(clip_on):
+    """The figures of the reference's table this run leaves out: all of NOT_COMPUTED without a CLIP checkpoint, pick-score alone with one."""
+    return tuple(m for m in NOT_COMPUTED if not (clip_on and m.startswith("clip-")))
+
+
+def clip_settings(models, clip_arg=None, tokenizer_arg=None):
+    """-> (CLIP checkpoint path or None, tokenizer directory or None).  The path is --clip, else `models.clip`; None switches the CLIP figures off
+    (allow_random alone never switches them on).  The tokenizer directory is --clip_tokenizer, else `models.clip_tokenizer`, else
+    `models.text_encoder`."""
+    models = models or {}
+    path = clip_arg or models.get("clip") or None
+    tok = tokenizer_arg or models.get("clip_tokenizer") or models.get("text_encoder") or None
+    return path, (tok if path else None)
 
 
 # ---- the kernels
@@ -113,6 +132,43 @@ def warp_ssim(edit_u8, source_u8, raft_engine, batch=4):
         fut = fut[..., t:Hp - b, l:Wp - r].contiguous()
         past = past[..., t:Hp - b, l:Wp - r].contiguous()
     return warp_ssim_from_flows(edit, fut, past, batch=batch)
+
+
+# ---- the CLIP figures
+@torch.no_grad()
+def clip_frame(edit_u8, engine, batch=64, features=None):
+    """eu.clip_frame (eval_utils.py:146-161): the sum of the off-diagonal cosines between the frame features / (N (N - 1)).  edit_u8 uint8 [N,H,W,3]."""
+    from . import clip
+    feats = engine.encode_image(_nhwc_u8(edit_u8), batch=batch) if features is None else features
+    if feats.shape[0] < 2:
+        raise ValueError(f"clip-frame needs at least 2 frames, got {feats.shape[0]}")
+    return clip.scores(feats)[0]
+
+
+def prompt_id_rows(prompt, tokenizer, context=77, allow_random=False):
+    """The token rows clip-text is computed from: the whole prompt when it fits the context, else (evaluate.py:43-49) its non-empty parts between
+    full stops, whose scores are averaged."""
+    from .clip import tokenize
+    try:
+        return [tokenize(prompt, tokenizer, context, allow_random)]
+    except RuntimeError:
+        print(f"[WARN] Prompt too long: '{prompt}', splitting.")
+        return [tokenize(p, tokenizer, context, allow_random) for p in prompt.split(".") if p.strip()]
+
+
+def _text_score(feats, ids, engine):
+    from . import clip
+    return clip.scores(feats, engine.encode_text(ids)[0])[1]
+
+
+@torch.no_grad()
+def clip_text(edit_u8, prompt, engine, tokenizer, allow_random=False, batch=64, features=None):
+    """eu.clip_text (eval_utils.py:129-144) with evaluate.py:41-49's fallback: the mean cosine of the frame features to the prompt's text feature."""
+    feats = engine.encode_image(_nhwc_u8(edit_u8), batch=batch) if features is None else features
+    rows = prompt_id_rows(prompt, tokenizer, engine.context, allow_random)
+    if not rows:
+        raise ValueError(f"empty prompt {prompt!r}: nothing to score")
+    return float(np.mean([_text_score(feats, ids, engine) for ids in rows]))
 
 
 # ---- files

@@ -102,6 +102,24 @@ def load_raft_state(path=None, seed=5, allow=False):
     return {(k[7:] if k.startswith("module.") else k): v for k, v in raw.items()}
 
 
+def load_clip_state(path=None, seed=6, allow=False):
+    """OpenAI CLIP weights (evaluate.py:119 clip.load("ViT-B/32")): `ViT-B-32.pt` is a TorchScript archive, so torch.jit.load(...).state_dict() is
+    tried first and a plain torch.load second; a `.safetensors` file holds `transformers.CLIPModel`'s layout and goes through clip.from_hf_state."""
+    from . import clip
+    if not (path and os.path.exists(path)):
+        _missing("CLIP", path, allow)
+        return clip.seeded_state_dict(seed)
+    if path.endswith(".safetensors"):
+        return clip.from_hf_state({k: v for k, v in _load_safetensors(path).items()})
+    try:
+        raw = torch.jit.load(path, map_location="cpu").state_dict()
+    except RuntimeError:
+        raw = torch.load(path, map_location="cpu", weights_only=True)
+        raw = raw.get("state_dict", raw) if isinstance(raw, dict) else raw
+    sd = {(k[7:] if k.startswith("module.") else k): v for k, v in raw.items()}
+    return clip.from_hf_state(sd) if "visual_projection.weight" in sd else sd
+
+
 def load_rmbg_state(path=None, seed=3, allow=False):
     """briaai/RMBG-1.4 weights (`model.safetensors` / `model.pth` with the reference module's keys, generate.py:149)."""
     from . import rmbg
