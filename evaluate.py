@@ -1,4 +1,4 @@
-"""Evaluate a relit video: `python evaluate.py --output_dir <run output directory> [--eval_cost] [--raft PATH] [--clip PATH]` (the reference's evaluate.py).
+"""Evaluate a relit video: `python evaluate.py --output_dir <run output directory> [--eval_cost] [--raft PATH] [--clip PATH] [--pick PATH]` (the reference's evaluate.py).
 
 Reads `<output_dir>/config.yaml`, the relit video (output_opt / output, .mp4 or .avi, else output.npy) and the source video (output_gt), computes
 warp-error-ssim on the device (tc_light_amd/evaluate.py: RAFT flows of the source frames, cubic warp, forward-backward mask, SSIM) and writes
@@ -6,7 +6,10 @@ warp-error-ssim on the device (tc_light_amd/evaluate.py: RAFT flows of the sourc
 does).  --eval_cost adds the run's cost figures (z_*).  RAFT weights: `models.raft` of the config or --raft; a missing file is an error unless
 `models.allow_random` / TCL_ALLOW_RANDOM_WEIGHTS=1 allows seeded stand-ins.  clip-frame and clip-text are computed when a CLIP ViT-B/32 checkpoint is
 named (`models.clip` or --clip, OpenAI's ViT-B-32.pt or a transformers .safetensors; tokenizer directory: --clip_tokenizer, else
-`models.clip_tokenizer`, else `models.text_encoder`); clip-text differs per prompt.  Without a CLIP path they are not computed; PickScore never is.
+`models.clip_tokenizer`, else `models.text_encoder`); clip-text differs per prompt.  pick-score is computed when a PickScore_v1 checkpoint is named
+(`models.pick` or --pick: a transformers snapshot directory or a .safetensors / .bin file; tokenizer directory: --pick_tokenizer, else
+`models.pick_tokenizer`, else the snapshot itself, else the CLIP one); it differs per prompt too.  Figures whose checkpoint is not named are listed as
+not computed; with both named result.txt holds the reference's four figures.
 """
 import argparse
 import os
@@ -26,14 +29,16 @@ def main(argv=None):
     ap.add_argument("--raft", type=str, default=None, help="RAFT checkpoint (raft-things.pth); default: models.raft of config.yaml")
     ap.add_argument("--clip", type=str, default=None, help="CLIP ViT-B/32 checkpoint (ViT-B-32.pt); default: models.clip of config.yaml; none: no CLIP figures")
     ap.add_argument("--clip_tokenizer", type=str, default=None, help="CLIP tokenizer directory; default: models.clip_tokenizer, else models.text_encoder")
+    ap.add_argument("--pick", type=str, default=None, help="PickScore_v1 checkpoint (snapshot directory or .safetensors); default: models.pick; none: no pick-score")
+    ap.add_argument("--pick_tokenizer", type=str, default=None, help="tokenizer directory for pick-score; default: models.pick_tokenizer, else the snapshot, else the CLIP one")
     ap.add_argument("--batch", type=int, default=4, help="frame pairs per RAFT / metric batch")
     a = ap.parse_args(argv)
 
     import torch
     from tc_light_amd.config_utils import _wrap
-    from tc_light_amd.evaluate import (clip_frame, clip_settings, clip_text, cost_scores, find_videos, format_results, not_computed, read_video_u8,
-                                       video_name, warp_ssim)
-    from tc_light_amd.model_utils import allow_random, load_clip_state, load_raft_state
+    from tc_light_amd.evaluate import (clip_frame, clip_settings, clip_text, cost_scores, find_videos, format_results, not_computed, pick_score,
+                                       pick_settings, read_video_u8, video_name, warp_ssim)
+    from tc_light_amd.model_utils import allow_random, load_clip_state, load_pick_state, load_raft_state
     from tc_light_amd.raft import RAFTEngine
 
     with open(os.path.join(a.output_dir, "config.yaml")) as f:
@@ -45,29 +50,46 @@ def main(argv=None):
     edit, source = read_video_u8(edit_path), read_video_u8(source_path)
     print(f"[INFO] edit {edit_path} ({tuple(edit.shape)}), source {source_path} ({tuple(source.shape)})")
     clip_path, tok_dir = clip_settings(models, a.clip, a.clip_tokenizer)
-    if clip_path:
-        print(f"[INFO] not computed here: {', '.join(not_computed(True))} (its PickScore model is not part of this project)")
-    else:
-        print(f"[INFO] not computed here: {', '.join(not_computed(False))} (their CLIP / PickScore models are not part of this project)")
+    pick_path, pick_tok_dir = pick_settings(models, a.pick, a.pick_tokenizer)
+    left_out = not_computed(bool(clip_path), bool(pick_path))
+    if left_out and pick_path:
+        print(f"[INFO] not computed here: {', '.join(left_out)} (no CLIP checkpoint is configured: models.clip / --clip)")
+    elif left_out and clip_path:
+        print(f"[INFO] not computed here: {', '.join(left_out)} (its PickScore model is not part of this project)")
+    elif left_out:
+        print(f"[INFO] not computed here: {', '.join(left_out)} (their CLIP / PickScore models are not part of this project)")
     engine = RAFTEngine(load_raft_state(a.raft or models.get("raft"), allow=allow_random(models)), "cuda")
     score, _ = warp_ssim(edit, source, engine, batch=a.batch)
     scores = {"warp-error-ssim": score}
     del engine
-    feats = clip_engine = tokenizer = None
+    prompts = ((config.get("generation") or {}).get("prompt") or {})
+    prompts = (list(prompts.values()) if isinstance(prompts, dict) else [prompts]) or [""]
+    per_prompt = [{} for _ in prompts]
     if clip_path:
         from tc_light_amd.clip import CLIPEngine, load_tokenizer
         clip_engine = CLIPEngine(load_clip_state(clip_path, allow=allow_random(models)), "cuda")
         tokenizer = load_tokenizer(tok_dir)
         feats = clip_engine.encode_image(edit)
         scores["clip-frame"] = clip_frame(edit, clip_engine, features=feats)
+        for extra, prompt in zip(per_prompt, prompts):
+            extra["clip-text"] = clip_text(edit, prompt, clip_engine, tokenizer, allow_random=allow_random(models), features=feats)
+        del clip_engine, feats                                              # freed before the larger PickScore engine is built
+        torch.cuda.empty_cache()
+    if pick_path:
+        from tc_light_amd.clip import load_tokenizer, pick_engine
+        state, pick_config = load_pick_state(pick_path, allow=allow_random(models))
+        pick_eng = pick_engine(state, "cuda", pick_config)
+        del state
+        tokenizer = load_tokenizer(pick_tok_dir)
+        feats = pick_eng.encode_image(edit)                                 # once; every prompt reuses them
+        for extra, prompt in zip(per_prompt, prompts):
+            extra["pick-score"] = pick_score(edit, prompt, pick_eng, tokenizer, allow_random=allow_random(models), features=feats)
+        del pick_eng, feats
     if a.eval_cost:
         scores.update(cost_scores(config, edit.shape[2], edit.shape[1]))
-    prompts = ((config.get("generation") or {}).get("prompt") or {})
-    prompts = list(prompts.values()) if isinstance(prompts, dict) else [prompts]
     name = video_name(config)
-    for prompt in prompts or [""]:
-        if clip_engine is not None:
-            scores["clip-text"] = clip_text(edit, prompt, clip_engine, tokenizer, allow_random=allow_random(models), features=feats)
+    for extra, prompt in zip(per_prompt, prompts):
+        scores.update(extra)
         text = format_results(name, prompt, scores)
         with open(os.path.join(a.output_dir, "result.txt"), "w") as f:
             f.write(text)

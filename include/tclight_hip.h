@@ -396,6 +396,15 @@ int tcl_eval_ssim_u8(const void* x, const void* y, double* out, int B, int H, in
  *   VisionTransformer.conv1 is one tcl_gemm_f16.  Down-scale factors up to about 17. */
 int tcl_clip_resize_geometry(int H, int W, int side, int* h_geom);
 int tcl_clip_preprocess_u8(const void* frames, void* crop, void* patches, int N, int H, int W, int side, int patch, hipStream_t st);
+/* The same two in the convention of transformers' CLIP image processor, which feeds PickScore (evaluate.py:120-121 AutoProcessor of
+ *   laion/CLIP-ViT-H-14-laion2B-s32B-b79K; eval_utils.py:163-176 pick_score_func): the same PIL bicubic resize, but `center_crop` starts at
+ *   (size - side) / 2 rounded DOWN.  rule: 0 = the rounded crop above, 1 = floor; they differ by one row or column when size - side = 2 (mod 4),
+ *   e.g. a 227 x 224 frame.  tcl_clip_preprocess_ld_u8 also takes the stride ldp of a patch row in halves, ldp >= 3*patch*patch and ldp % 64 == 0
+ *   (or ldp == 3*patch*patch): columns 3*patch*patch .. ldp-1 of every row are written as zeros, so a patch size whose 3*patch*patch is not a
+ *   multiple of tcl_gemm_f16's K step (ViT-H/14: 588 -> ldp 640) still embeds with one GEMM against a conv1 weight zero-padded the same way.  With
+ *   rule 0 and ldp = 3*patch*patch it is tcl_clip_preprocess_u8 byte for byte (one kernel serves both).  The u8 crop is bit-identical to PIL. */
+int tcl_clip_resize_geometry_rule(int H, int W, int side, int rule, int* h_geom);
+int tcl_clip_preprocess_ld_u8(const void* frames, void* crop, void* patches, int N, int H, int W, int side, int patch, int ldp, int rule, hipStream_t st);
 /* tcl_clip_attention_f16: nn.MultiheadAttention of ResidualAttentionBlock.attention (self-attention, need_weights=False) after its in_proj: qkv
  *   [B*T, 3*H*d] f16 = [q | k | v], head hh at columns hh*d of each third, read in place; out [B*T, H*d] f16 = softmax(scale q k^T (+ causal mask)) v,
  *   heads concatenated (the operand of out_proj).  causal: key j > query i is masked (CLIP.build_attention_mask, the text tower).  One workgroup per
@@ -414,6 +423,11 @@ int tcl_clip_quick_gelu_f16(const void* x, void* y, long n, hipStream_t st);
  *   text is NULL).  f64 sums in a fixed order, no atomics: the same input gives the same bits.  ws: tcl_clip_scores_workspace_bytes(N) bytes. */
 size_t tcl_clip_scores_workspace_bytes(int N);
 int tcl_clip_scores(const float* feats, const float* text, int N, int D, double* out2, void* ws, hipStream_t st);
+/* tcl_pick_scores: pick-score (evaluate.py:52-56; eval_utils.py:163-176 pick_score_func: logit_scale.exp() * text_embs @ image_embs.T of the
+ *   normalised embeddings, averaged over the frames).  feats [N,D] f32, text [D] f32, logit_scale = the log as the checkpoint stores it -> out
+ *   (device, N + 1 doubles): out[0] = the mean, out[1 + i] = exp(logit_scale) cos(text, feats[i]).  f64 sums in a fixed order, no atomics: the same
+ *   input gives the same bits. */
+int tcl_pick_scores(const float* feats, const float* text, int N, int D, float logit_scale, double* out, hipStream_t st);
 
 #ifdef __cplusplus
 }

@@ -9,6 +9,12 @@ end-of-text token (`ids.argmax(-1)`) -> text_projection.  A block is LayerNorm, 
 size and context length come from the tensor shapes and the head count is width // 64 (clip/model.py build_model), so another CLIP of this family
 loads unchanged.  Activations are f16 with f32 accumulation; the features are returned as f32.
 
+The same engine runs PickScore_v1, the model behind pick-score (evaluate.py:52-56,120-121; eval_utils.py:163-176): a transformers.CLIPModel at CLIP
+ViT-H/14 (`PICKSCORE_V1`), built by `pick_engine` with what its tensors do not say: 16 heads per tower, erf GELU (c_fc's GEMM epilogue), and the
+preprocessing of transformers' image processor, whose centre crop is floored where clip's is rounded.  A patch size whose 3 P^2 is not a multiple of
+64 (14: 588) gets patch rows and a conv1 weight zero-padded to the next multiple.  `tokenize_truncated` is that processor's text side and
+`pick_scores` the figure (tcl_pick_scores).  Pinned by tests/golden/pick.npz (tests/test_gpu_pick.py).
+
 State dicts use OpenAI's key names.  `from_hf_state` / `to_hf_state` map to and from `transformers.CLIPModel`'s names (q / k / v concatenated into
 in_proj, the projections transposed).  Pinned against `transformers.CLIPModel` in f32 by tests/golden/clip.npz (tests/test_gpu_clip.py).
 """
@@ -26,6 +32,12 @@ HEAD_DIM = 64                                                            # clip/
 VIT_B32 = dict(embed_dim=512, image_resolution=224, vision_layers=12, vision_width=768, vision_patch_size=32, context_length=77, vocab_size=49408,
                transformer_width=512, transformer_layers=12)
 SOT, EOT = 49406, 49407                                                  # <|startoftext|>, <|endoftext|> of clip's BPE vocabulary
+# pickapic-anonymous/PickScore_v1 (evaluate.py:120-121): transformers.CLIPModel at CLIP ViT-H/14 (laion/CLIP-ViT-H-14-laion2B-s32B-b79K).  The first
+# nine entries are clip_param_shapes' arguments (arch_shapes); the rest is what a transformers checkpoint keeps in config.json, not in its tensors.
+PICKSCORE_V1 = dict(embed_dim=1024, image_resolution=224, vision_layers=32, vision_width=1280, vision_patch_size=14, context_length=77,
+                    vocab_size=49408, transformer_width=1024, transformer_layers=24, vision_heads=16, text_heads=16, act="gelu", eps=1e-5)
+ACTS = {"quick_gelu": 0, "gelu": 4}                                      # -> tcl_gemm_f16's act of c_fc (QuickGELU is a pass of its own)
+CROPS = {"round": 0, "floor": 1}                                         # -> the crop rule of tcl_clip_preprocess_ld_u8
 
 
 # ---- state dicts
@@ -60,6 +72,11 @@ def clip_param_shapes(embed_dim=512, image_resolution=224, vision_layers=12, vis
     sh["text_projection"] = (tw, embed_dim)
     sh["logit_scale"] = ()
     return sh
+
+
+def arch_shapes(arch):
+    """The entries of an architecture dictionary (VIT_B32, PICKSCORE_V1) that clip_param_shapes / seeded_state_dict take."""
+    return {k: arch[k] for k in VIT_B32 if k in arch}
 
 
 def seeded_state_dict(seed=6, **arch):
@@ -133,18 +150,20 @@ def to_hf_state(sd):
     return out
 
 
-def from_hf_state(sd):
-    """`transformers.CLIPModel` names -> OpenAI names (the inverse of to_hf_state; `position_ids` buffers of older checkpoints are dropped)."""
-    out = {oa: sd[hf] for oa, hf in _HF_TOP}
-    out["visual.proj"] = sd["visual_projection.weight"].t().contiguous()
-    out["text_projection"] = sd["text_projection.weight"].t().contiguous()
+def from_hf_state(sd, consume=False):
+    """`transformers.CLIPModel` names -> OpenAI names (the inverse of to_hf_state; `position_ids` buffers of older checkpoints are dropped).
+    consume: entries are removed from `sd` as they are used, so a large checkpoint is never held twice (q / k / v are copied into in_proj)."""
+    take = sd.pop if consume else sd.__getitem__
+    out = {oa: take(hf) for oa, hf in _HF_TOP}
+    out["visual.proj"] = take("visual_projection.weight").t().contiguous()
+    out["text_projection"] = take("text_projection.weight").t().contiguous()
     for oa, hf in _HF_TOWERS:
         for i in range(_layers(sd, hf)):
             a, h = f"{oa}{i}.", f"{hf}{i}."
             for kind in ("weight", "bias"):
-                out[a + "attn.in_proj_" + kind] = torch.cat([sd[h + f"self_attn.{n}_proj." + kind] for n in "qkv"]).contiguous()
+                out[a + "attn.in_proj_" + kind] = torch.cat([take(h + f"self_attn.{n}_proj." + kind) for n in "qkv"]).contiguous()
                 for x, y in _HF_BLOCK:
-                    out[a + x + kind] = sd[h + y + kind]
+                    out[a + x + kind] = take(h + y + kind)
     return out
 
 
@@ -157,6 +176,16 @@ def resize_geometry(H, W, side=224):
     new_long = int(side * long_ / short)
     oh, ow = (new_long, side) if W <= H else (side, new_long)
     return oh, ow, int(round((oh - side) / 2.0)), int(round((ow - side) / 2.0))
+
+
+def resize_geometry_rule(H, W, side=224, crop="round"):
+    """resize_geometry with the crop rule named: "round" is clip's CenterCrop above; "floor" is transformers' `center_crop` (image_transforms.py:
+    top = (size - side) // 2), the rule of the processor PickScore is fed by.  The resize is the same; the two crops differ by one row or column
+    when size - side is 2 (mod 4), e.g. 227 -> 224.  (tcl_clip_resize_geometry_rule is the same on the C side.)"""
+    if crop not in CROPS:
+        raise ValueError(f"crop must be one of {sorted(CROPS)}, got {crop!r}")
+    oh, ow, top, left = resize_geometry(H, W, side)
+    return (oh, ow, top, left) if crop == "round" else (oh, ow, (oh - side) // 2, (ow - side) // 2)
 
 
 def _stand_in_ids(text, room):
@@ -186,6 +215,22 @@ def tokenize(prompt, tokenizer, context=77, allow_random=False):
     return out
 
 
+def tokenize_truncated(prompt, tokenizer, context=77, allow_random=False):
+    """`processor(text=prompt, padding=True, truncation=True, max_length=context)` on one prompt (eval_utils.py:163-176 pick_score_func): int64
+    [1, n + 2] = [SOT] + ids[:context - 2] + [EOT], unpadded (one prompt is its own longest) and truncated, so nothing is "too long".  tokenizer None:
+    as in `tokenize`."""
+    if tokenizer is None:
+        if not allow_random:
+            raise FileNotFoundError("no CLIP tokenizer (models.pick_tokenizer / --pick_tokenizer); set models.allow_random / "
+                                    "TCL_ALLOW_RANDOM_WEIGHTS=1 for deterministic stand-in token ids")
+        warnings.warn("CLIP tokenizer not found -> deterministic text-seeded stand-in token ids (allow_random)")
+        ids, sot, eot = _stand_in_ids(prompt, 10 ** 9), SOT, EOT
+    else:
+        ids = list(tokenizer(prompt, truncation=False, add_special_tokens=False)["input_ids"])
+        sot, eot = int(tokenizer.bos_token_id), int(tokenizer.eos_token_id)
+    return torch.tensor([[sot] + ids[:max(0, context - 2)] + [eot]], dtype=torch.int64)
+
+
 def load_tokenizer(tok_dir):
     """A CLIPTokenizer from a local directory (the directory itself or its `tokenizer` sub-directory), or None when there is none."""
     import os
@@ -198,7 +243,7 @@ def load_tokenizer(tok_dir):
 
 # ---- the engine
 class _Tower:
-    def __init__(self, sd, prefix, dev):
+    def __init__(self, sd, prefix, dev, heads=None):
         self.layers = []
         for i in range(_layers(sd, prefix)):
             p = f"{prefix}{i}."
@@ -206,13 +251,23 @@ class _Tower:
                 "ln_1.weight", "ln_1.bias", "attn.in_proj_weight", "attn.in_proj_bias", "attn.out_proj.weight", "attn.out_proj.bias",
                 "ln_2.weight", "ln_2.bias", "mlp.c_fc.weight", "mlp.c_fc.bias", "mlp.c_proj.weight", "mlp.c_proj.bias")})
         self.width = self.layers[0]["ln_1.weight"].numel()
-        self.heads = self.width // HEAD_DIM
+        self.heads = self.width // HEAD_DIM if heads is None else int(heads)
+        if self.heads <= 0 or self.width % self.heads or (self.width // self.heads) % 16 or self.width // self.heads > 128:
+            raise ValueError(f"{prefix}: {heads} heads on width {self.width} (tcl_clip_attention_f16 takes a head_dim that is a multiple of 16 up to 128)")
 
 
 class CLIPEngine:
-    """clip/model.py's CLIP (VisionTransformer image tower) in inference on the device."""
+    """clip/model.py's CLIP (VisionTransformer image tower) in inference on the device.  The keyword arguments are what the tensors of a
+    transformers.CLIPModel checkpoint do not say (its config.json does): the head counts (None: width // 64, OpenAI's rule), the MLP's activation
+    ("quick_gelu", or "gelu" = erf, in c_fc's GEMM epilogue) and the centre-crop rule of the preprocessing ("round": clip's _transform, "floor":
+    transformers' image processor).  The defaults are OpenAI's CLIP."""
 
-    def __init__(self, state_dict, device):
+    def __init__(self, state_dict, device, vision_heads=None, text_heads=None, act="quick_gelu", crop="round"):
+        if act not in ACTS:
+            raise ValueError(f"act must be one of {sorted(ACTS)}, got {act!r}")
+        if crop not in CROPS:
+            raise ValueError(f"crop must be one of {sorted(CROPS)}, got {crop!r}")
+        self.act, self.crop = act, crop
         missing = [k for k in ("visual.conv1.weight", "visual.proj", "token_embedding.weight", "text_projection", "ln_final.weight") if k not in state_dict]
         if missing:
             raise KeyError(f"CLIP state dict lacks {missing} (OpenAI key names; a transformers checkpoint goes through from_hf_state)")
@@ -225,29 +280,34 @@ class CLIPEngine:
 
         w = sd["visual.conv1.weight"]
         self.vwidth, self.patch = w.shape[0], w.shape[-1]
-        self.conv1 = w.reshape(self.vwidth, -1).to(H16).contiguous().to(d)                          # [width, 3 * P * P]: (channel, row, column)
+        self.kpatch = 3 * self.patch * self.patch
+        self.ldp = (self.kpatch + 63) // 64 * 64                                                    # patch-row stride: tcl_gemm_f16 needs K % 64 == 0
+        conv1 = torch.zeros(self.vwidth, self.ldp, dtype=H16)                                       # columns kpatch .. ldp-1 zero, as the patch rows'
+        conv1[:, :self.kpatch] = w.reshape(self.vwidth, -1).to(H16)                                 # [width, 3 * P * P]: (channel, row, column)
+        self.conv1 = conv1.to(d)
         self.grid = int(round(math.sqrt(sd["visual.positional_embedding"].shape[0] - 1)))
         self.side = self.grid * self.patch
         self.cls, self.vpos = h("visual.class_embedding"), h("visual.positional_embedding")
         self.ln_pre = (h("visual.ln_pre.weight"), h("visual.ln_pre.bias"))
         self.ln_post = (h("visual.ln_post.weight"), h("visual.ln_post.bias"))
         self.vproj = sd["visual.proj"].t().to(H16).contiguous().to(d)                               # [embed, width]
-        self.visual = _Tower(sd, "visual.transformer.resblocks.", d)
+        self.visual = _Tower(sd, "visual.transformer.resblocks.", d, vision_heads)
         self.table, self.tpos = h("token_embedding.weight"), h("positional_embedding")
         self.vocab, self.twidth = self.table.shape
         self.context = self.tpos.shape[0]
         self.ln_final = (h("ln_final.weight"), h("ln_final.bias"))
         self.tproj = sd["text_projection"].t().to(H16).contiguous().to(d)
-        self.text = _Tower(sd, "transformer.resblocks.", d)
+        self.text = _Tower(sd, "transformer.resblocks.", d, text_heads)
         self.embed_dim = self.vproj.shape[0]
-        if (3 * self.patch * self.patch) % 64 or self.vwidth % 64 or self.twidth % 64:
-            raise ValueError(f"widths {self.vwidth} / {self.twidth} and 3 * patch^2 = {3 * self.patch ** 2} must be multiples of 64 (tcl_gemm_f16's K)")
+        self.logit_scale = float(sd["logit_scale"]) if "logit_scale" in sd else None               # the log, as stored (CLIP.logit_scale)
+        if self.vwidth % 64 or self.twidth % 64:
+            raise ValueError(f"widths {self.vwidth} / {self.twidth} must be multiples of 64 (tcl_gemm_f16's K)")
 
     # ---- building blocks
-    def _gemm(self, x, w, bias, resid, M):
+    def _gemm(self, x, w, bias, resid, M, act=0):
         N, K = w.shape
         y = torch.empty(M, N, dtype=H16, device=self.dev)
-        self.L.tcl_gemm_f16(x, w, bias if bias is not None else 0, resid if resid is not None else 0, y, M, N, K, K, K, N, N, 0, stream())
+        self.L.tcl_gemm_f16(x, w, bias if bias is not None else 0, resid if resid is not None else 0, y, M, N, K, K, K, N, N, act, stream())
         return y
 
     def _ln(self, x, wb, M, C):
@@ -268,23 +328,29 @@ class CLIPEngine:
         for p in tower.layers:
             qkv = self._gemm(self._ln(x, (p["ln_1.weight"], p["ln_1.bias"]), M, W), p["attn.in_proj_weight"], p["attn.in_proj_bias"], None, M)
             x = self._gemm(self.attention(qkv, B, T, tower.heads, causal), p["attn.out_proj.weight"], p["attn.out_proj.bias"], x, M)
-            u = self._gemm(self._ln(x, (p["ln_2.weight"], p["ln_2.bias"]), M, W), p["mlp.c_fc.weight"], p["mlp.c_fc.bias"], None, M)
-            self.L.tcl_clip_quick_gelu_f16(u, u, u.numel(), stream())
+            u = self._gemm(self._ln(x, (p["ln_2.weight"], p["ln_2.bias"]), M, W), p["mlp.c_fc.weight"], p["mlp.c_fc.bias"], None, M, ACTS[self.act])
+            if self.act == "quick_gelu":
+                self.L.tcl_clip_quick_gelu_f16(u, u, u.numel(), stream())
             x = self._gemm(u, p["mlp.c_proj.weight"], p["mlp.c_proj.bias"], x, M)
         return x
 
     # ---- the two encoders
     def preprocess(self, frames_u8, want_crop=False):
-        """frames uint8 [N,H,W,3] (device) -> (patch rows [N*grid^2, 3*P*P] f16, the uint8 crop [N,side,side,3] or None)."""
+        """frames uint8 [N,H,W,3] (device) -> (patch rows [N*grid^2, ldp] f16 with ldp = 3*P*P rounded up to a multiple of 64 and the columns past
+        3*P*P zero, the uint8 crop [N,side,side,3] or None)."""
         N, H, W = frames_u8.shape[:3]
-        patches = torch.empty(N * self.grid * self.grid, 3 * self.patch * self.patch, dtype=H16, device=self.dev)
+        patches = torch.empty(N * self.grid * self.grid, self.ldp, dtype=H16, device=self.dev)
         crop = torch.empty(N, self.side, self.side, 3, dtype=torch.uint8, device=self.dev) if want_crop else None
-        self.L.tcl_clip_preprocess_u8(frames_u8, crop if want_crop else 0, patches, N, H, W, self.side, self.patch, stream())
+        if self.crop == "round" and self.ldp == self.kpatch:
+            self.L.tcl_clip_preprocess_u8(frames_u8, crop if want_crop else 0, patches, N, H, W, self.side, self.patch, stream())
+        else:
+            self.L.tcl_clip_preprocess_ld_u8(frames_u8, crop if want_crop else 0, patches, N, H, W, self.side, self.patch, self.ldp, CROPS[self.crop],
+                                             stream())
         return patches, crop
 
     @torch.no_grad()
     def encode_patches(self, patches, B):
-        """VisionTransformer.forward from the patch rows on: [B*grid^2, 3*P*P] f16 -> features [B, embed_dim] f32."""
+        """VisionTransformer.forward from the patch rows on: [B*grid^2, ldp] f16 -> features [B, embed_dim] f32."""
         T, W = self.grid * self.grid + 1, self.vwidth
         emb = self._gemm(patches, self.conv1, None, None, B * (T - 1))
         x = torch.empty(B * T, W, dtype=H16, device=self.dev)
@@ -308,13 +374,14 @@ class CLIPEngine:
 
     @torch.no_grad()
     def encode_text(self, ids):
-        """CLIP.encode_text: ids int [B, context] (clip.tokenize's layout) -> [B, embed_dim] f32 on the device."""
+        """CLIP.encode_text: ids int [B, T], 1 <= T <= context (clip.tokenize's padded layout, or tokenize_truncated's unpadded row, which uses the
+        first T positional rows) -> [B, embed_dim] f32 on the device: the row of the end-of-text token, the largest id of its row."""
         ids = torch.as_tensor(ids)
-        if ids.dim() != 2 or ids.shape[1] != self.context:
-            raise ValueError(f"token ids must be [B, {self.context}], got {tuple(ids.shape)}")
+        if ids.dim() != 2 or not 1 <= ids.shape[1] <= self.context:
+            raise ValueError(f"token ids must be [B, T] with 1 <= T <= {self.context}, got {tuple(ids.shape)}")
         if int(ids.min()) < 0 or int(ids.max()) >= self.vocab:
             raise ValueError(f"token ids outside the vocabulary [0, {self.vocab})")
-        B, T, W = ids.shape[0], self.context, self.twidth
+        B, T, W = ids.shape[0], ids.shape[1], self.twidth
         i32 = ids.to(self.dev).to(torch.int32).contiguous()
         x = torch.empty(B * T, W, dtype=H16, device=self.dev)
         self.L.tcl_clip_embed_f16(0, 0, i32, self.table, self.tpos, 0, 0, x, B, T, W, self.vocab, 1e-5, stream())
@@ -339,8 +406,78 @@ def scores(feats, text=None):
     return o[0], (o[1] if t is not None else None)
 
 
+def pick_scores(feats, text, logit_scale):
+    """pick_score_func (eval_utils.py:163-176): feats [N,D] f32 (device), text [D] f32, logit_scale (the log) -> (the mean score as a Python float,
+    the per-image scores exp(logit_scale) cos(text, feat_i) as a float64 numpy array).  tcl_pick_scores: f64, fixed order."""
+    f = feats.float().contiguous()
+    N, D = f.shape
+    t = text.float().contiguous().view(-1)
+    if t.numel() != D:
+        raise ValueError(f"text feature must have {D} elements, got {t.numel()}")
+    out = torch.empty(N + 1, dtype=torch.float64, device=f.device)
+    lib().tcl_pick_scores(f, t.to(f.device), N, D, float(logit_scale), out, stream())
+    o = out.cpu().numpy()
+    return float(o[0]), o[1:]
+
+
+_HF_DEFAULTS = dict(num_attention_heads=(12, 8), hidden_act="quick_gelu", layer_norm_eps=1e-5, patch_size=32)     # transformers' CLIP*Config
+
+
+def pick_options(config=None, vision_width=None, text_width=None, patch=None):
+    """CLIPEngine's keyword arguments for the PickScore model: from `config`, the dictionary of a transformers config.json (vision_config /
+    text_config: num_attention_heads, hidden_act, layer_norm_eps, patch_size; a field that is absent has transformers' default), else PICKSCORE_V1.
+    ValueError, naming the field, for what the kernels do not cover: an activation other than quick_gelu / gelu, a head_dim outside {64, 80}, a
+    LayerNorm eps other than 1e-5, and a patch_size that is not the checkpoint's.  Host-side: no device is touched."""
+    A = PICKSCORE_V1
+    vw, tw = vision_width or A["vision_width"], text_width or A["transformer_width"]
+    if config is None:
+        heads, acts, eps, psz = (A["vision_heads"], A["text_heads"]), (A["act"], A["act"]), (A["eps"], A["eps"]), A["vision_patch_size"]
+    else:
+        vc, tc = config.get("vision_config") or {}, config.get("text_config") or {}
+        D = _HF_DEFAULTS
+        heads = (vc.get("num_attention_heads", D["num_attention_heads"][0]), tc.get("num_attention_heads", D["num_attention_heads"][1]))
+        acts = (vc.get("hidden_act", D["hidden_act"]), tc.get("hidden_act", D["hidden_act"]))
+        eps = (vc.get("layer_norm_eps", D["layer_norm_eps"]), tc.get("layer_norm_eps", D["layer_norm_eps"]))
+        psz = vc.get("patch_size", D["patch_size"])
+    if acts[0] != acts[1] or acts[0] not in ACTS:
+        raise ValueError(f"hidden_act {acts[0]!r} (vision) / {acts[1]!r} (text): the engine runs one of {sorted(ACTS)} in both towers")
+    for tower, w, h in (("vision", vw, heads[0]), ("text", tw, heads[1])):
+        if not isinstance(h, int) or h <= 0 or w % h or w // h not in (64, 80):
+            raise ValueError(f"num_attention_heads {h!r} on the {tower} width {w}: head_dim must be 64 or 80 (what tcl_clip_attention_f16 is tested at)")
+    for tower, e in zip(("vision", "text"), eps):
+        if abs(float(e) - 1e-5) > 1e-12:
+            raise ValueError(f"layer_norm_eps {e!r} ({tower}): the engine's LayerNorms run at 1e-5")
+    if patch is not None and int(psz) != int(patch):
+        raise ValueError(f"patch_size {psz!r} of the config, but the checkpoint's patch embedding is {patch} x {patch}")
+    return dict(vision_heads=int(heads[0]), text_heads=int(heads[1]), act=acts[0], crop="floor")
+
+
+def to_hf_config(arch, vision_layers=None, text_layers=None):
+    """An architecture dictionary (PICKSCORE_V1) as the dictionary of a transformers config.json (`CLIPConfig(**to_hf_config(arch))`): the inverse of
+    pick_options' reading, used by the goldens and the tests.  The layer counts can be overridden for small models of the same widths."""
+    act, eps = arch.get("act", "quick_gelu"), arch.get("eps", 1e-5)
+    vision = dict(hidden_size=arch["vision_width"], intermediate_size=4 * arch["vision_width"], image_size=arch["image_resolution"],
+                  num_hidden_layers=vision_layers or arch["vision_layers"], patch_size=arch["vision_patch_size"], projection_dim=arch["embed_dim"],
+                  num_attention_heads=arch.get("vision_heads", arch["vision_width"] // HEAD_DIM), hidden_act=act, layer_norm_eps=eps)
+    text = dict(hidden_size=arch["transformer_width"], intermediate_size=4 * arch["transformer_width"], vocab_size=arch["vocab_size"],
+                num_hidden_layers=text_layers or arch["transformer_layers"], max_position_embeddings=arch["context_length"],
+                projection_dim=arch["embed_dim"], num_attention_heads=arch.get("text_heads", arch["transformer_width"] // HEAD_DIM), hidden_act=act,
+                layer_norm_eps=eps, bos_token_id=SOT, eos_token_id=EOT)
+    return dict(vision_config=vision, text_config=text, projection_dim=arch["embed_dim"], logit_scale_init_value=math.log(1 / 0.07))
+
+
+def pick_engine(state, device, config=None):
+    """The CLIPEngine of PickScore_v1 from a state dict in OpenAI's key names (model_utils.load_pick_state) and, when there is one, the checkpoint's
+    config.json dictionary: GELU, 16 heads per tower, the transformers processor's crop.  See pick_options for what is refused."""
+    if "visual.conv1.weight" not in state or "positional_embedding" not in state:
+        raise KeyError("PickScore state dict lacks visual.conv1.weight / positional_embedding (OpenAI key names; see from_hf_state)")
+    w = state["visual.conv1.weight"]
+    return CLIPEngine(state, device, **pick_options(config, w.shape[0], state["positional_embedding"].shape[1], w.shape[-1]))
+
+
 def useful_flops(engine, n_images=1):
-    """Multiply-adds x 2 of encode_image for n images: the patch GEMM, the blocks (in_proj, QK^T and PV, out_proj, the MLP) and the projection."""
+    """Multiply-adds x 2 of encode_image for n images: the patch GEMM (its 3 P^2 real columns, not the zero padding), the blocks (in_proj, QK^T and
+    PV -- 4 T^2 W whatever the head count --, out_proj, the MLP) with T = grid^2 + 1, and the projection."""
     W, T, Lr = engine.vwidth, engine.grid ** 2 + 1, len(engine.visual.layers)
     per = 2 * (T - 1) * W * 3 * engine.patch ** 2 + Lr * (2 * T * W * 3 * W + 4 * T * T * W + 2 * T * W * W + 16 * T * W * W) + 2 * W * engine.embed_dim
     return per * n_images

@@ -1,6 +1,7 @@
 // OpenAI CLIP (ViT image tower + causal text tower) for the clip-frame / clip-text figures of evaluate.py (evaluate.py:119 clip.load("ViT-B/32");
 // utils/evaluation/eval_utils.py:129-161 clip_text / clip_frame).  The Linears and LayerNorms of the towers are tcl_gemm_f16 / tcl_layernorm_f16; this
-// file holds what they do not cover:
+// file holds what they do not cover.  pick-score (evaluate.py:52-56,120-121; eval_utils.py:163-176 pick_score_func) runs PickScore_v1, a CLIP ViT-H/14, on
+// the same kernels: its processor's crop rule and the padded patch rows are options of the preprocess, k_pick_* are its scores.
 //
 // k_clip_preprocess (one block per 32 x 32 tile of the cropped output of one frame): clip's _transform(n_px) = Resize(n_px, BICUBIC) on a PIL image,
 //   CenterCrop, ToTensor, Normalize.  PIL's resampler is integer arithmetic (Resample.c: precompute_coeffs, normalize_coeffs_8bpc,
@@ -9,7 +10,8 @@
 //   reads it.  The block computes the coefficient rows of its 32 output columns and 32 output rows (f64, no fma contraction: the operations PIL
 //   makes), resamples the input rows its vertical taps touch horizontally into LDS (uint8), and takes the vertical pass from there: only the cropped
 //   window is computed and every input byte is read about once.  Outputs: the uint8 crop and / or the normalised f16 patch rows in the column order
-//   of conv1.weight.reshape(width, 3 * P * P), so the patch embedding is a plain GEMM.
+//   of conv1.weight.reshape(width, 3 * P * P), so the patch embedding is a plain GEMM.  The rows may be padded to a stride ldp >= 3 P^2 (zeros), for
+//   a patch size whose 3 P^2 is not a multiple of the GEMM's K step, and the crop offset follows clip's rounded or transformers' floored rule.
 // k_clip_attn<NKP> (one block per (sample, head), 4 waves): reads Q, K, V in place from the fused in_proj output [B*T, 3W].  K ([keys][d], rows
 //   padded by 8 halves) and V^T ([d][keys]) of the head sit in LDS, zero-padded to 32 * NKP keys.  A wave takes 16 queries at a time:
 //   S^T = K.Q^T with mfma_f32_16x16x32_f16 (lane l: query l & 15, keys 16 t + 4 (l >> 4) + r in accumulator t, register r), so the softmax of a query
@@ -19,6 +21,7 @@
 // k_clip_embed (one block per row): [class | patches] + positional embedding then ln_pre, or token gather + positional embedding; f32 up to the
 //   single f16 rounding.   k_quick_gelu: x * sigmoid(1.702 x).
 // k_scores_*: cosine statistics of the features in f64 with a fixed summation order (no atomics): repeated runs are bit-identical.
+// k_pick_*: PickScore, exp(logit_scale) cos(text, image) per image and the mean, the same way.
 #include "common.h"
 #include "../../include/tclight_hip.h"
 
@@ -80,7 +83,7 @@ __device__ void pil_coeffs(const Axis ax, int xx, int* bounds, int* kk) {
 __device__ __forceinline__ int clip8(int v) { return min(max(v >> PBITS, 0), 255); }
 
 __global__ __launch_bounds__(256) void k_clip_preprocess(const uint8_t* __restrict__ frames, uint8_t* __restrict__ crop, _Float16* __restrict__ patches,
-                                                         int H, int W, int S, int P, const Axis ax, const Axis ay, int max_rows) {
+                                                         int H, int W, int S, int P, int ldp, const Axis ax, const Axis ay, int max_rows) {
 #pragma clang fp contract(off)
     extern __shared__ __align__(16) unsigned char smem[];
     int* kx = (int*)smem;                            // [PT][ax.ksize]
@@ -123,7 +126,10 @@ __global__ __launch_bounds__(256) void k_clip_preprocess(const uint8_t* __restri
             // ToTensor (uint8 -> f32 / 255) and Normalize ((x - mean) / std), f32, then one rounding to f16
             const float x = ((float)v / 255.f - mean[c]) / stdv[c];
             const long prow = (long)n * npw * npw + (oy / P) * npw + ox / P;
-            patches[prow * (3 * P * P) + (c * P + oy % P) * P + ox % P] = (_Float16)x;
+            patches[prow * ldp + (c * P + oy % P) * P + ox % P] = (_Float16)x;
+            // the K padding of the row (ldp > 3 P^2: ViT-H/14's 588 -> 640) is zeroed by the thread that holds the patch's first pixel
+            if (c == 0 && oy % P == 0 && ox % P == 0)
+                for (int j = 3 * P * P; j < ldp; ++j) patches[prow * ldp + j] = (_Float16)0.f;
         }
     }
 }
@@ -346,34 +352,66 @@ __global__ __launch_bounds__(64) void k_scores_final(const double* __restrict__ 
     }
 }
 
-}  // namespace
-
-extern "C" {
-
-int tcl_clip_resize_geometry(int H, int W, int side, int* geom) {
-    TCL_CHECK_ARG(geom && H > 0 && W > 0 && side > 0);
-    const int shrt = W <= H ? W : H, lng = W <= H ? H : W;
-    const int nl = (int)((double)((long)side * lng) / (double)shrt);
-    const int ow = W <= H ? side : nl, oh = W <= H ? nl : side;
-    geom[0] = oh; geom[1] = ow;
-    geom[2] = (int)nearbyint((oh - side) / 2.0);        // round half to even, as Python's round()
-    geom[3] = (int)nearbyint((ow - side) / 2.0);
-    return TCL_OK;
+// PickScore (eval_utils.py:163-176): out[1 + i] = exp(logit_scale) <text / |text|, f_i / |f_i|>, one wave per image
+__global__ __launch_bounds__(64) void k_pick_row(const float* __restrict__ f, const float* __restrict__ text, int D, double scale, double* __restrict__ out) {
+    const int i = blockIdx.x;
+    const float* fi = f + (long)i * D;
+    const double ff = wave_dot(fi, fi, D, threadIdx.x), tt = wave_dot(text, text, D, threadIdx.x), ft = wave_dot(fi, text, D, threadIdx.x);
+    if (threadIdx.x == 0) out[1 + i] = scale * (ft / (sqrt(ff) * sqrt(tt)));
 }
 
-int tcl_clip_preprocess_u8(const void* frames, void* crop, void* patches, int N, int H, int W, int side, int patch, hipStream_t st) {
+// out[0] = the mean of out[1 .. N], summed in index order by one thread
+__global__ __launch_bounds__(64) void k_pick_mean(int N, double* __restrict__ out) {
+    if (threadIdx.x != 0) return;
+    double s = 0.0;
+    for (int i = 0; i < N; ++i) s += out[1 + i];
+    out[0] = s / (double)N;
+}
+
+int preprocess_launch(const void* frames, void* crop, void* patches, int N, int H, int W, int side, int patch, int ldp, int rule, hipStream_t st) {
     TCL_CHECK_ARG(frames && (crop || patches) && N > 0 && N <= 65535 && H > 0 && W > 0 && side > 0 && patch > 0 && (long)H * W < (1L << 28));
     TCL_CHECK_ARG(!patches || side % patch == 0);
     int g[4];
-    tcl_clip_resize_geometry(H, W, side, g);
+    if (tcl_clip_resize_geometry_rule(H, W, side, rule, g) != TCL_OK) return TCL_EINVAL;
     const Axis ay = make_axis(H, g[0], g[2]), ax = make_axis(W, g[1], g[3]);
     const int max_rows = (int)((PT - 1) * ay.scale + 2.0 * ay.support) + 3;
     const size_t lds = (size_t)(PT * (ax.ksize + ay.ksize) + 4 * PT) * sizeof(int) + (size_t)max_rows * PT * 3;
     TCL_CHECK_ARG(lds <= 64 * 1024);                    // down-scale factors up to about 17
     const int tiles = cdiv(side, PT);
     hipLaunchKernelGGL(k_clip_preprocess, dim3(tiles, tiles, N), dim3(256), lds, st, (const uint8_t*)frames, (uint8_t*)crop, (_Float16*)patches, H, W,
-                       side, patch, ax, ay, max_rows);
+                       side, patch, ldp, ax, ay, max_rows);
     TCL_LAUNCH_RET();
+}
+
+}  // namespace
+
+extern "C" {
+
+int tcl_clip_resize_geometry(int H, int W, int side, int* geom) { return tcl_clip_resize_geometry_rule(H, W, side, 0, geom); }
+
+int tcl_clip_resize_geometry_rule(int H, int W, int side, int rule, int* geom) {
+    TCL_CHECK_ARG(geom && H > 0 && W > 0 && side > 0 && (rule == 0 || rule == 1));
+    const int shrt = W <= H ? W : H, lng = W <= H ? H : W;
+    const int nl = (int)((double)((long)side * lng) / (double)shrt);
+    const int ow = W <= H ? side : nl, oh = W <= H ? nl : side;
+    geom[0] = oh; geom[1] = ow;
+    if (rule == 0) {
+        geom[2] = (int)nearbyint((oh - side) / 2.0);    // round half to even, as Python's round()
+        geom[3] = (int)nearbyint((ow - side) / 2.0);
+    } else {
+        geom[2] = (oh - side) / 2;                      // transformers center_crop: (size - side) // 2; oh, ow >= side
+        geom[3] = (ow - side) / 2;
+    }
+    return TCL_OK;
+}
+
+int tcl_clip_preprocess_u8(const void* frames, void* crop, void* patches, int N, int H, int W, int side, int patch, hipStream_t st) {
+    return preprocess_launch(frames, crop, patches, N, H, W, side, patch, 3 * patch * patch, 0, st);
+}
+
+int tcl_clip_preprocess_ld_u8(const void* frames, void* crop, void* patches, int N, int H, int W, int side, int patch, int ldp, int rule, hipStream_t st) {
+    TCL_CHECK_ARG(patch > 0 && patch <= 1024 && ldp >= 3 * patch * patch && (ldp % 64 == 0 || ldp == 3 * patch * patch) && (rule == 0 || rule == 1));
+    return preprocess_launch(frames, crop, patches, N, H, W, side, patch, ldp, rule, st);
 }
 
 int tcl_clip_attention_f16(const void* qkv, void* out, int B, int T, int H, int d, float scale, int causal, hipStream_t st) {
@@ -411,6 +449,13 @@ int tcl_clip_scores(const float* feats, const float* text, int N, int D, double*
     hipLaunchKernelGGL(k_scores_norm, dim3(N + (text ? 1 : 0)), dim3(64), 0, st, feats, text, N, D, norm);
     hipLaunchKernelGGL(k_scores_row, dim3(N), dim3(256), 0, st, feats, text, N, D, (const double*)norm, part, tpart);
     hipLaunchKernelGGL(k_scores_final, dim3(1), dim3(64), 0, st, (const double*)part, (const double*)tpart, N, text ? 1 : 0, out2);
+    TCL_LAUNCH_RET();
+}
+
+int tcl_pick_scores(const float* feats, const float* text, int N, int D, float logit_scale, double* out, hipStream_t st) {
+    TCL_CHECK_ARG(feats && text && out && N > 0 && N <= 65535 && D > 0);
+    hipLaunchKernelGGL(k_pick_row, dim3(N), dim3(64), 0, st, feats, text, D, exp((double)logit_scale), out);
+    hipLaunchKernelGGL(k_pick_mean, dim3(1), dim3(64), 0, st, N, out);
     TCL_LAUNCH_RET();
 }
 

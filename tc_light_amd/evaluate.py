@@ -9,7 +9,12 @@ score of the pair is the SSIM of the two uint8 images.  The metric is the mean o
 clip-frame and clip-text (evaluate.py:39-49, eval_utils.py:129-161) are computed when a CLIP checkpoint is configured (`models.clip` / --clip): the
 frames go through `clip.CLIPEngine.encode_image`, clip-frame is the mean off-diagonal cosine between the frame features and clip-text the mean cosine
 of the frame features to the prompt's text feature (tcl_clip_scores).  With no CLIP path nothing of it is loaded and the two figures are listed as not
-computed, as before.  PickScore and FrameLPIPS are not computed (their models are not part of this project).
+computed, as before.
+
+pick-score (evaluate.py:52-56, eval_utils.py:163-176) is computed when a PickScore_v1 checkpoint is configured (`models.pick` / --pick): the same
+engine at CLIP ViT-H/14 (`clip.pick_engine`: 16 heads per tower, erf GELU, patch rows padded from 588 to 640 columns, the transformers processor's
+floored centre crop), the prompt tokenised as the processor does (truncated to 77, unpadded), and exp(logit_scale) cos(text, frame) averaged over the
+frames (tcl_pick_scores).  FrameLPIPS is not computed: the reference's evaluate.py never calls it.
 """
 import math
 import os
@@ -27,9 +32,9 @@ VIDEO_EXTS = (".mp4", ".avi")                   # .avi: what dataparser.save_vid
 NOT_COMPUTED = ("clip-frame", "clip-text", "pick-score")
 
 
-def not_computed(clip_on):
-    """The figures of the reference's table this run leaves out: all of NOT_COMPUTED without a CLIP checkpoint, pick-score alone with one."""
-    return tuple(m for m in NOT_COMPUTED if not (clip_on and m.startswith("clip-")))
+def not_computed(clip_on, pick_on=False):
+    """The figures of the reference's table this run leaves out: the two clip-* figures without a CLIP checkpoint, pick-score without a PickScore one."""
+    return tuple(m for m in NOT_COMPUTED if not (clip_on and m.startswith("clip-")) and not (pick_on and m == "pick-score"))
 
 
 def clip_settings(models, clip_arg=None, tokenizer_arg=None):
@@ -39,6 +44,17 @@ def clip_settings(models, clip_arg=None, tokenizer_arg=None):
     models = models or {}
     path = clip_arg or models.get("clip") or None
     tok = tokenizer_arg or models.get("clip_tokenizer") or models.get("text_encoder") or None
+    return path, (tok if path else None)
+
+
+def pick_settings(models, pick_arg=None, tokenizer_arg=None):
+    """-> (PickScore checkpoint path or None, tokenizer directory or None).  The path is --pick, else `models.pick`; None switches pick-score off
+    (allow_random alone never switches it on).  The tokenizer directory is --pick_tokenizer, else `models.pick_tokenizer`, else the checkpoint
+    directory itself when it holds a vocab.json, else `models.clip_tokenizer`, else `models.text_encoder` (one BPE vocabulary serves them all)."""
+    models = models or {}
+    path = pick_arg or models.get("pick") or None
+    own = path if path and os.path.isfile(os.path.join(path, "vocab.json")) else None
+    tok = tokenizer_arg or models.get("pick_tokenizer") or own or models.get("clip_tokenizer") or models.get("text_encoder") or None
     return path, (tok if path else None)
 
 
@@ -169,6 +185,19 @@ def clip_text(edit_u8, prompt, engine, tokenizer, allow_random=False, batch=64, 
     if not rows:
         raise ValueError(f"empty prompt {prompt!r}: nothing to score")
     return float(np.mean([_text_score(feats, ids, engine) for ids in rows]))
+
+
+# ---- pick-score
+@torch.no_grad()
+def pick_score(edit_u8, prompt, engine, tokenizer, allow_random=False, batch=64, features=None):
+    """eu.pick_score_func (eval_utils.py:163-176) averaged over the frames (evaluate.py:52-56): exp(logit_scale) times the cosine of the prompt's
+    text embedding to every frame's image embedding.  `engine` is clip.pick_engine's; `features` are its image features when already computed."""
+    from . import clip
+    if engine.logit_scale is None:
+        raise ValueError("pick-score needs the checkpoint's logit_scale, which this state dict lacks")
+    feats = engine.encode_image(_nhwc_u8(edit_u8), batch=batch) if features is None else features
+    ids = clip.tokenize_truncated(prompt, tokenizer, engine.context, allow_random)
+    return clip.pick_scores(feats, engine.encode_text(ids)[0], engine.logit_scale)[0]
 
 
 # ---- files

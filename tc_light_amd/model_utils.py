@@ -120,6 +120,43 @@ def load_clip_state(path=None, seed=6, allow=False):
     return clip.from_hf_state(sd) if "visual_projection.weight" in sd else sd
 
 
+def load_pick_state(path=None, seed=7, allow=False):
+    """PickScore_v1 (evaluate.py:120-121 AutoModel.from_pretrained("pickapic-anonymous/PickScore_v1"), a transformers.CLIPModel at CLIP ViT-H/14) ->
+    (state dict in OpenAI's key names, the config.json dictionary or None).  `path` is a snapshot directory (config.json + model.safetensors, or
+    the shards model-0000x-of-0000y.safetensors with model.safetensors.index.json, or pytorch_model.bin) or a single .safetensors / .bin file.  The
+    tensors keep their stored dtype and the transformers-named ones are released as they are renamed: the 3.9 GB f32 checkpoint is held once."""
+    import glob
+    import json
+    from . import clip
+    if not (path and os.path.exists(path)):
+        _missing("PickScore", path, allow)
+        return clip.seeded_state_dict(seed, **clip.arch_shapes(clip.PICKSCORE_V1)), None
+    config, files = None, [path]
+    if os.path.isdir(path):
+        cfg = os.path.join(path, "config.json")
+        if os.path.isfile(cfg):
+            with open(cfg) as f:
+                config = json.load(f)
+        index = os.path.join(path, "model.safetensors.index.json")
+        if os.path.isfile(index):
+            with open(index) as f:
+                files = [os.path.join(path, n) for n in sorted(set(json.load(f)["weight_map"].values()))]
+        else:
+            files = [p for p in (os.path.join(path, "model.safetensors"), os.path.join(path, "pytorch_model.bin")) if os.path.isfile(p)][:1] \
+                or sorted(glob.glob(os.path.join(path, "model-*-of-*.safetensors")))
+        absent = [p for p in files if not os.path.isfile(p)]
+        if absent or not files:
+            raise FileNotFoundError(f"PickScore snapshot {path!r}: " + (f"shards {absent} of its index are missing" if absent else
+                                                                       "no model.safetensors, shards or pytorch_model.bin"))
+    raw = {}
+    for p in files:
+        part = _load_safetensors(p) if p.endswith(".safetensors") else torch.load(p, map_location="cpu", weights_only=True)
+        raw.update(part.get("state_dict", part) if not p.endswith(".safetensors") and isinstance(part, dict) else part)
+    if "visual_projection.weight" not in raw:
+        raise KeyError(f"{path!r} does not hold a transformers.CLIPModel (no visual_projection.weight)")
+    return clip.from_hf_state(raw, consume=True), config
+
+
 def load_rmbg_state(path=None, seed=3, allow=False):
     """briaai/RMBG-1.4 weights (`model.safetensors` / `model.pth` with the reference module's keys, generate.py:149)."""
     from . import rmbg
