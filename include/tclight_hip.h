@@ -239,7 +239,7 @@ int tcl_tome_normalize_f16(const void* x, void* y, long rows, int C, hipStream_t
  *          unm[position] = merged slot each input position is restored from (merge.py:135-155).
  * ws: tcl_tome_match_workspace_bytes(na) bytes, ZEROED ONCE by the caller before the first call and then only passed to this function
  * (one stream; may be re-used for any smaller na): every call leaves it all-zero again except two result words at a fixed offset (layout:
- * 4 KiB control | 65 536 score-histogram bins | keys).  Per call: the score kernel + two small launches (threshold select, maps). */
+ * 4 KiB control | 256 KiB unused, formerly score-histogram bins | keys).  Per call: the score kernel + two small launches (threshold select, maps). */
 size_t tcl_tome_match_workspace_bytes(int na);
 /* 1: C = 640 affine matches take the strip-resident kernel too (same maps; faster alone, slower beside the flash kernel: off by default; TCL_TOME640). */
 int tcl_tome_strip640(int enable);

@@ -215,14 +215,16 @@ __global__ __launch_bounds__(256, 3) void k_tome_match(const _Float16* __restric
 // (no index loads in the loop, so the counted vmcnt only ever sees the LDS-DMA).  XCD x sweeps dst split x % nsplit: its L2 holds one range.
 // LDS image of a stage: row R at R * 128, its 16-B chunk g stored at position g ^ ((R >> 1) & 7): the 16-lane groups of a ds_read_b128
 // (MI355X_MICROARCH.md, LDS table) then touch 16 distinct slots of the 256-B bank window.
-// Round 6 -- NS = 2, TR = 64: the LDS bound of this kernel.  Every wave of a block reads the SAME dst rows from LDS as the A operand of its MFMAs: 1 KiB per 32x32x16 MFMA, and a CU
+// NS = 2, TR = 64 (round 6; the C = 320 form): the LDS bound of this kernel.  Every wave of a block reads the SAME dst rows from LDS as the A operand of its MFMAs: 1 KiB per 32x32x16 MFMA, and a CU
 // that issues one MFMA per 8 clocks (its four matrix pipes' rate) needs exactly the LDS's 128 B/clk -- the 54 % the matrix pipe showed (profiles/r2_tome_match320_sq_counters.txt) is that
 // bound at ~2/3 LDS efficiency, and the flash kernel the chain runs beside lives on the same LDS.  With TWO src sub-tiles per wave (2 x 80 VGPRs of strip) every A fragment feeds two
 // MFMAs: half the LDS reads and half the dst DMA per MFMA; the dst tile shrinks to 64 rows so the accumulators stay at 64 VGPRs.  Same MFMA, same K order, same tile order: same keys.
-template <int NW, int C = 320, int NS = 1, int TR = 128>        // waves per block: 4 (128-src strip, two blocks per CU) or 8 (256-src strip, one block per CU: half the dst DMA per MFMA); C = 640 (round 4): the level-1 matches, 160 VGPRs of strip
-__global__ __launch_bounds__(64 * NW, (NW == 4 && NS == 1) ? 2 : 1) void k_tome_match320(const _Float16* __restrict__ metric, long bstride, int Bt, int a_split, int a_gap, int na,
+// Two instantiations: <320, 2, 64> (every affine C = 320 match) and <640, 1, 128> (round 4: the level-1 matches, 160 VGPRs of strip; opt-in, see tome_match_impl).
+// Four waves per block.  What else was built and measured (one sub-tile per wave at C = 320, 8-wave blocks) is in DESIGN 4.5 / 4.14 and profiles/r6_ab_tome_x2_*.txt.
+template <int C, int NS, int TR>
+__global__ __launch_bounds__(256, NS == 1 ? 2 : 1) void k_tome_match320(const _Float16* __restrict__ metric, long bstride, int Bt, int a_split, int a_gap, int na,
                                                           int b0, int nb, int tiles_dst, int nsplit, unsigned long long* __restrict__ keys) {
-    constexpr int NST = C / 64, STAGE = TR * 128, SW = 32 * NW * NS, NP = (TR / 8) / NW, NA = TR / 32;       // src strip width, DMA pieces per wave and stage
+    constexpr int NW = 4, NST = C / 64, STAGE = TR * 128, SW = 32 * NW * NS, NP = (TR / 8) / NW, NA = TR / 32;       // src strip width, DMA pieces per wave and stage
     extern __shared__ __attribute__((aligned(16))) char smem[];
     __attribute__((address_space(3))) char* const lds0 = (__attribute__((address_space(3))) char*)smem;
     const int bid = blockIdx.x, x = bid & 7, per = 8 / nsplit;
@@ -348,79 +350,21 @@ __global__ __launch_bounds__(64 * NW, (NW == 4 && NS == 1) ? 2 : 1) void k_tome_
     }
 }
 
-// Top-r selection and map construction without a sort, in TWO launches per match (round 4; rounds 2-3: five -- two histogram passes, two
-// single-block picks, the map kernel -- ~650 k launches per 300-frame pass).  The r src tokens with the highest f16 score are merged, ties at the
+// Top-r selection and map construction without a sort, in TWO launches per match.  The r src tokens with the highest f16 score are merged, ties at the
 // threshold go to the lowest src index (= the order a stable descending sort would produce); the reference orders the remaining (unmerged) src
 // slots by score as well, but that order is immaterial -- the merged sequence only feeds a permutation-invariant attention and is mapped back by
 // `unm` -- so they keep their src index order here.  Maps of SURVEY 8(a) A12/A13:
 //  mrg[p]  (p in [0, na-r+nb))  = input position feeding merged slot p          (merge, mode "replace")
 //  unm[pos] (pos in input seq)  = merged slot that input position pos is restored from (unmerge)
-// k_thr_select: ONE histogram over all 65 536 sortable-f16 scores (global atomics, one per src token: the 256 KiB of bins live at a fixed offset
-//   of the workspace and are all-zero between matches); the block that draws the last ticket (guide: "last arriver" hand-off -- writers drain their
-//   atomics, release fence, ticket; the last arriver acquires) scans the bins from the top, finds the threshold score and how many of its ties
-//   are taken, and zeroes the bins again.  Small blocks (256 threads, no LDS to speak of): in the pipeline this chain runs on a side stream beside
-//   the flash kernel, whose two blocks per CU leave only a register / LDS remainder.
+// k_thr_select1: ONE block, no global bins -- a two-pass radix select over the high / low byte of the 16-bit sortable score with 256-bin LDS histograms
+//   (the keys are <= 64 k x 8 B in L2: read twice).  thr = the largest score with #(score > thr) < r <= #(score >= thr), take = r - #(score > thr).
+//   One block because the chain runs on a side stream beside the flash kernel and the score kernels, where every block of a launch waits for a CU slot:
+//   the multi-block histogram form of round 4 took 60 us per launch in the pass against ~10 alone (profiles/r6_ab_thr_select1.txt).
 // k_tome_maps2: one thread per src / dst token.  A src block needs the number of ties / lower scores BEFORE its first token: it simply counts them
 //   over the preceding keys (<= 64 k keys of 8 B, L2-resident: 3.6 M key reads in total at na = 43 200 -- less than one pass of the score kernel's
-//   epilogue), in-block prefixes by ballot / popcount.  The last block to finish clears the key array for the next match (last-arriver ticket
-//   again), so the workspace is all-zero between matches except the two result words at a fixed offset -- rounds 2-3 left per-chunk scan words
-//   behind the keys, which a later match with a LARGER src count then met as initial keys (harmless in practice: they sat below any real
-//   threshold; gone now).
-#define THR_BS 256
-#define THR_CTRL_INTS 8      // ws ints [768, 776): ticket of k_thr_select, ticket of k_tome_maps2, thr, take
-__global__ __launch_bounds__(THR_BS) void k_thr_select(const unsigned long long* __restrict__ keys, int na, int r, int* __restrict__ hist16, int* __restrict__ ctrl) {
-    __shared__ int sc[THR_BS];
-    __shared__ int s_last, s_who;
-    const int tid = threadIdx.x;
-    for (int i = blockIdx.x * THR_BS + tid; i < na; i += gridDim.x * THR_BS)
-        __hip_atomic_fetch_add(hist16 + (int)((keys[i] >> 32) & 0xFFFFu), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        s_last = __hip_atomic_fetch_add(ctrl + 0, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (int)gridDim.x - 1;
-        if (s_last) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        s_who = -1;
-    }
-    __syncthreads();
-    if (!s_last) return;
-    // thread t owns the 256 bins [65535 - 256 t - 255, 65535 - 256 t]: descending score order over t.  Plain 16-B loads behind the acquire (the
-    // guide's last-arriver recipe; an agent-scope atomic load per bin made this scan a chain of 256 dependent round trips: 97 us per match in
-    // the first profiled pass of the round, more than the five launches it replaced)
-    const int hi = 65535 - 256 * tid;
-    typedef int i32x4 __attribute__((ext_vector_type(4)));
-    const i32x4* bins = (const i32x4*)(hist16 + hi - 255);                   // ascending addresses: bins hi-255 .. hi
-    int cnt = 0;
-#pragma unroll 8
-    for (int q = 0; q < 64; ++q) { const i32x4 v = bins[q]; cnt += v[0] + v[1] + v[2] + v[3]; }
-    sc[tid] = cnt;
-    __syncthreads();
-    for (int off = 1; off < THR_BS; off <<= 1) { const int v = tid >= off ? sc[tid - off] : 0; __syncthreads(); sc[tid] += v; __syncthreads(); }
-    const int incl = sc[tid], excl = incl - cnt;
-    if (r > 0 && excl < r && r <= incl) s_who = tid;
-    __syncthreads();
-    if (r <= 0) { if (tid == 0) { ctrl[2] = 0x10000; ctrl[3] = 0; } }        // nothing merged
-    else if (tid == s_who) {
-        int above = excl, thr = hi;
-        for (int q = 0; q < 256; ++q) {
-            const int c = hist16[hi - q];
-            if (above + c >= r) { thr = hi - q; break; }
-            above += c;
-        }
-        ctrl[2] = thr; ctrl[3] = r - above;                                   // threshold score; ties taken (lowest src index first)
-    }
-    __syncthreads();
-    i32x4* zb = (i32x4*)(hist16 + hi - 255);
-    const i32x4 z4 = {0, 0, 0, 0};
-#pragma unroll 8
-    for (int q = 0; q < 64; ++q) zb[q] = z4;                                  // bins back to zero for the next match
-    if (tid == 0) ctrl[0] = 0;
-}
-// Round 6: the same selection in ONE block without global bins -- a two-pass radix select over the high / low byte of the 16-bit sortable score with 256-bin LDS
-// histograms (the keys are <= 64 k x 8 B in L2: read twice).  k_thr_select needs 2-64 blocks resident at once, and beside the flash kernel and the score kernels every
-// block of a side-stream launch waits for a CU slot: 60 us per launch in the pass against ~10 alone (profiles/r6_bench_kernel_stats.txt).  One block waits once.
-// Same threshold and tie count: thr = the largest score with #(score > thr) < r <= #(score >= thr), take = r - #(score > thr).
+//   epilogue), in-block prefixes by ballot / popcount.  The last block to finish clears the key array for the next match ("last arriver" ticket:
+//   writers drain, release fence, ticket; the last arriver clears), so the workspace is all-zero between matches except the two result words at a
+//   fixed offset.
 __global__ __launch_bounds__(1024) void k_thr_select1(const unsigned long long* __restrict__ keys, int na, int r, int* __restrict__ ctrl) {
     __shared__ int h[256], s_b, s_above;
     const int tid = threadIdx.x;
@@ -580,53 +524,37 @@ static int tome_match_impl(const void* metric, long bstride, int Bt, int C, cons
                            int* mrg, int* unm, void* ws, int affine, int a_split, int a_gap, int b0, hipStream_t st) {
     TCL_CHECK_ARG(metric && a_pos && b_pos && mrg && unm && ws && Bt > 0 && na > 0 && nb > 0 && r >= 0 && r <= na && na <= 64 * 1024 && C % 64 == 0);
     TclProfScope ps(TCL_PROF_MATCH, st, 2.0 * na * nb * C * Bt);
-    // ws: [4 KiB control: ints 768.. = tickets, thr, take | 65 536 histogram bins | keys na x 8 B]; bins, tickets and keys are all-zero on entry
+    // ws: [4 KiB control: ints 768.. = ticket of k_tome_maps2 (int 769), thr, take | 256 KiB unused (the histogram bins of the retired multi-block
+    // selection; the layout is kept so that callers and their zeroing do not change) | keys na x 8 B]; ticket and keys are all-zero on entry
     // (the caller zeroes the workspace once) and are left all-zero; every region sits at a fixed offset or behind everything else, so a
     // workspace re-used for another na never shows a match a previous match's scratch
     int* ctrl = (int*)ws + 768;
-    int* hist16 = (int*)((char*)ws + 4096);
     unsigned long long* keys = (unsigned long long*)((char*)ws + 4096 + 65536 * 4);
     const int ts = cdiv(na, 128), td = cdiv(nb, 128);
-    const size_t lds = (size_t)3 * 256 * 64, lds320 = (size_t)4 * 128 * 128;
+    const size_t lds = (size_t)3 * 256 * 64, lds320 = (size_t)4 * 64 * 128, lds640 = (size_t)4 * 128 * 128;
     static bool set = false;
     if (!set) {
         (void)hipFuncSetAttribute((const void*)k_tome_match, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute((const void*)k_tome_match320<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds320);
-        (void)hipFuncSetAttribute((const void*)k_tome_match320<8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds320);
-        (void)hipFuncSetAttribute((const void*)(k_tome_match320<4, 640>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds320);
+        (void)hipFuncSetAttribute((const void*)(k_tome_match320<320, 2, 64>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds320);
+        (void)hipFuncSetAttribute((const void*)(k_tome_match320<640, 1, 128>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds640);
         set = true;
     }
-    // tuning / A-B hook: 0 = always the tile-epilogue kernel, 4 / 8 = one src sub-tile per wave (rounds 2-5; 4- / 8-wave blocks), 2 (default since round 6) = two src
-    // sub-tiles per wave on 64-row dst tiles.  Round 6, same box (profiles/r6_ab_tome_x2_alone.txt, r6_ab_tome_x2_inpass.txt): ALONE the 2-sub-tile form is 4-27 % SLOWER
-    // (276 unified registers: one wave per SIMD where the old form ran two; 43 200 x 14 400: 946 -> 1 070 us) -- and IN THE PASS, where its neighbour on the SIMD is a flash
-    // wave either way and the LDS is shared with that kernel, the 60-frame denoise phase is 0.8 % faster in both interleaved pairs (33.26 / 33.31 -> 33.02 / 33.04 s).
-    // The pass is what counts.  Same keys bit for bit (test_tome_match_strip_kernel_equals_tile_kernel passes under TCL_TOME320=2 and =4).
-    static const int use320 = getenv("TCL_TOME320") ? atoi(getenv("TCL_TOME320")) : 2;
     // C = 640 (level 1) on the strip kernel: built in round 4 (VERDICT r3 #3a), bit-identical, 5-24 % faster per call alone (tools/micro/bench_tome.py:
     // 7 920 x 7 920: 269 -> 205 us) -- and 0.3 % SLOWER in the pass (same-box A/B, profiles/r4_ab_tome640.txt): its strip takes 160 of a wave's 256
     // registers, so a block only starts on a SIMD with 256 free registers, i.e. not beside two flash waves.  Off by default; TCL_TOME640=1 selects it.
     if (g_tome640 < 0) g_tome640 = getenv("TCL_TOME640") ? atoi(getenv("TCL_TOME640")) : 0;
-    const int use640 = g_tome640;
-    if (affine && (C == 320 || (C == 640 && use640)) && nb >= 128 && use320) {
-        // 4-wave blocks by default.  The 8-wave form (256-src strips, one block per CU, half the dst DMA per MFMA) is 3-6 % faster with the GPU
-        // to itself from ~13k x 13k tokens up, but in the pipeline the matching chain runs on a side stream beside the flash kernel: a 512-thread
-        // block (352 VGPRs per SIMD lane, 64 KiB LDS) only starts on a CU that holds NO flash block, where a 4-wave block shares one with a flash
-        // block -- in the profiled pass the 8-wave launches took 2.2 ms on average against 0.9 alone.  use320 = 8 selects it (tools/micro/bench_tome.py).
-        const int nw = (use320 == 8 && C == 320) ? 8 : 4;
-        const bool x2 = use320 == 2 && C == 320;             // round 6: two src sub-tiles per wave, 64-row dst tiles (half the LDS reads and dst DMA per MFMA)
-        const int tsw = cdiv(na, x2 ? 256 : 32 * nw), slots = (nw == 8 || x2) ? 256 : 512, tdx = x2 ? cdiv(nb, 64) : td;
+    if (affine && (C == 320 || (C == 640 && g_tome640)) && nb >= 128) {
+        // C = 320: two src sub-tiles per wave on 64-row dst tiles (256-src strips).  Alone it is 4-27 % slower than one sub-tile per wave (276 unified
+        // registers: one wave per SIMD instead of two); in the pass, beside the flash kernel and on its LDS, the denoise phase is 0.8 % faster, and the
+        // pass is what counts (profiles/r6_ab_tome_x2_alone.txt, r6_ab_tome_x2_inpass.txt).  C = 640: one sub-tile, 128-row dst tiles (128-src strips).
+        const bool x2 = C == 320;
+        const int tsw = cdiv(na, x2 ? 256 : 128), slots = x2 ? 256 : 512, tdx = x2 ? cdiv(nb, 64) : td;
         int nsplit = 1;
         while (nsplit < 8 && (long)tsw * nsplit < slots * 3 / 2) nsplit *= 2;
         while (nsplit > 1 && cdiv(tdx, nsplit) < 2) nsplit /= 2;
         const int per = 8 / nsplit, groups = cdiv(tsw, per);
-        if (x2) {
-            static bool set2 = false;
-            if (!set2) { (void)hipFuncSetAttribute((const void*)(k_tome_match320<4, 320, 2, 64>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 64 * 128); set2 = true; }
-            hipLaunchKernelGGL((k_tome_match320<4, 320, 2, 64>), dim3(groups * 8), dim3(256), (size_t)4 * 64 * 128, st, (const _Float16*)metric, bstride, Bt, a_split, a_gap, na, b0, nb, tdx, nsplit, keys);
-        } else
-        if (C == 640) hipLaunchKernelGGL((k_tome_match320<4, 640>), dim3(groups * 8), dim3(256), lds320, st, (const _Float16*)metric, bstride, Bt, a_split, a_gap, na, b0, nb, td, nsplit, keys);
-        else if (nw == 8) hipLaunchKernelGGL(k_tome_match320<8>, dim3(groups * 8), dim3(512), lds320, st, (const _Float16*)metric, bstride, Bt, a_split, a_gap, na, b0, nb, td, nsplit, keys);
-        else hipLaunchKernelGGL(k_tome_match320<4>, dim3(groups * 8), dim3(256), lds320, st, (const _Float16*)metric, bstride, Bt, a_split, a_gap, na, b0, nb, td, nsplit, keys);
+        if (x2) hipLaunchKernelGGL((k_tome_match320<320, 2, 64>), dim3(groups * 8), dim3(256), lds320, st, (const _Float16*)metric, bstride, Bt, a_split, a_gap, na, b0, nb, tdx, nsplit, keys);
+        else hipLaunchKernelGGL((k_tome_match320<640, 1, 128>), dim3(groups * 8), dim3(256), lds640, st, (const _Float16*)metric, bstride, Bt, a_split, a_gap, na, b0, nb, tdx, nsplit, keys);
     } else {
     // each block keeps one dst tile and streams a run of src tiles; runs as long as possible while ~4 blocks per slot (256 CUs x 3) remain
     int spb = (int)((long)ts * td * Bt / 3072);
@@ -636,12 +564,7 @@ static int tome_match_impl(const void* metric, long bstride, int Bt, int C, cons
     hipLaunchKernelGGL(k_tome_match, dim3(cdiv(td, 8) * 8 * nrange, Bt), dim3(256), lds, st, (const _Float16*)metric, bstride, C, a_pos, na, b_pos, nb, ts, td,
                        spb, keys);
     }
-    static const int thr1 = getenv("TCL_THR1") ? atoi(getenv("TCL_THR1")) : 1;      // 0 = the multi-block histogram kernel of round 4
-    if (thr1) hipLaunchKernelGGL(k_thr_select1, dim3(1), dim3(1024), 0, st, keys, na, r, ctrl);
-    else {
-        const int hg = na >= 16384 ? 64 : (na >= 2048 ? 16 : 2);
-        hipLaunchKernelGGL(k_thr_select, dim3(hg), dim3(THR_BS), 0, st, keys, na, r, hist16, ctrl);
-    }
+    hipLaunchKernelGGL(k_thr_select1, dim3(1), dim3(1024), 0, st, keys, na, r, ctrl);
     const int nsb = cdiv(na, TOME_MAPS_BS);
     hipLaunchKernelGGL(k_tome_maps2, dim3(nsb + cdiv(nb, TOME_MAPS_BS)), dim3(TOME_MAPS_BS), 0, st, keys, ctrl, na, nb, r, nsb, a_pos, b_pos, mrg, unm);
     TCL_LAUNCH_RET();

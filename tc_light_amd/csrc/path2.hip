@@ -217,8 +217,8 @@ __global__ void k_gather_codebook(const float* __restrict__ feat, const int* __r
 // d(loss)/d(codebook): cat row j0 + blockIdx.y.  ATOMIC == false: the ids of one frame are distinct, so a launch over ONE row is a conflict-free
 // read-modify-write and the rows of a mini-batch are launched one after the other (fixed order: deterministic, and no atomic unit in the way);
 // ATOMIC == true (ids that repeat inside a frame): all rows in one launch, float atomics, order not reproducible.
-// cmask != null (lazy schedule, round 5): the clamp test of the gathered value comes from the mask byte the lazy gather wrote (bit c: channel c
-// inside [0, 1]) -- the codebook row in memory may still be steps behind, and the mask saves this kernel's three feat reads per pixel.
+// cmask != null (round 5): the clamp test of the gathered value comes from the mask byte the gather wrote (bit c: channel c inside [0, 1]) -- the
+// mask saves this kernel's three feat reads per pixel.
 // The run-time-uniform choices (image or pre-image gradient, clamp mask or codebook read) are template parameters of the body: a per-load select on a
 // run-time condition, even a wave-uniform one, makes hipcc branch around each load and wait for it (cdna_hip_programming.md, trap (c)).
 template <bool ATOMIC, bool PRE, bool HASCM>
@@ -821,66 +821,6 @@ __global__ void k_adam_touched_frame(const int* __restrict__ inv, const int* __r
         for (int c = 0; c < 3; ++c) { p[c * K + id] = pp[c]; m[c * K + id] = mm[c]; v[c * K + id] = vv[c]; g[c * K + id] = 0.f; }
     }
 }
-// ---- round 5: ONE visit per row and iteration with a write.  The catch-up launch is gone: the gather replays a row's skipped steps in REGISTERS
-// (read-only: p, m, v, t_last) and hands the clamp mask on; the step kernel replays them again (the same instruction sequence: same bits) and
-// applies the gradient.  Per row 156 B instead of 208 B of traffic, one launch less per iteration.
-__global__ void k_gather_codebook_lazy(const float* __restrict__ feat, const float* __restrict__ m, const float* __restrict__ v,
-                                       const int* __restrict__ t_last, const int* __restrict__ inv, const int* __restrict__ fidx,
-                                       float* __restrict__ out, unsigned char* __restrict__ cmask, int P, size_t K, int upto, float lr, float b1,
-                                       float b2, float eps, const float* __restrict__ bc1, const float* __restrict__ bc2) {
-    const int j = blockIdx.y, f = fidx[j];
-    const int* iv = inv + (size_t)f * P; float* o = out + (size_t)j * 3 * P; unsigned char* cm = cmask + (size_t)j * P;
-    for (int px = blockIdx.x * blockDim.x + threadIdx.x; px < P; px += gridDim.x * blockDim.x) {
-        const size_t id = (size_t)iv[px];
-        const int tl = TL_STEP(t_last[id]);
-        float pp[3], mm[3], vv[3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) pp[c] = feat[c * K + id];
-        if (tl < upto) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) { mm[c] = m[c * K + id]; vv[c] = v[c * K + id]; }
-            adam_replay(pp, mm, vv, tl + 1, upto, lr, b1, b2, eps, bc1, bc2);
-        }
-        int mk = 0;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const float val = pp[c] * SH_C0 + 0.5f;
-            mk |= (val >= 0.f && val <= 1.f) ? (1 << c) : 0;
-            o[c * P + px] = fminf(fmaxf(val, 0.f), 1.f);
-        }
-        cm[px] = (unsigned char)mk;
-    }
-}
-// rows of the cat rows blockIdx.y: whatever step they stand at (< step), replay up to step - 1 without gradient, then apply `step` with the
-// (complete) gradient and clear it.  One thread per row wins the atomicMax of the step counter and learns where the row stood.
-__global__ void k_adam_step_rows_lazy(const int* __restrict__ inv, const int* __restrict__ fidx, int P, size_t K, int* __restrict__ t_last,
-                                      float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, int step, float lr,
-                                      float b1, float b2, float eps, const float* __restrict__ bc1, const float* __restrict__ bc2) {
-    // a frame can sit in the cat list twice (as a current frame and as the previous frame of another slot): only its FIRST occurrence walks its pixels --
-    // with the unshared rows no longer claimed by an atomic, two blocks on the same pixel would both step its row
-    for (int q = 0; q < (int)blockIdx.y; ++q) if (fidx[q] == fidx[blockIdx.y]) return;
-    const int* iv = inv + (size_t)fidx[blockIdx.y] * P;
-    const float c1 = bc1[step], c2 = bc2[step];
-    for (int px = blockIdx.x * blockDim.x + threadIdx.x; px < P; px += gridDim.x * blockDim.x) {
-        const size_t id = (size_t)iv[px];
-        const int raw = t_last[id];
-        if (TL_STEP(raw) >= step) continue;
-        int tl = TL_STEP(raw);
-        if (raw & TL_SHARED) {
-            tl = TL_STEP(atomicMax(t_last + id, TL_SHARED | step));
-            if (tl >= step) continue;                              // stepped by another frame of this mini-batch
-        } else t_last[id] = step;
-        float pp[3], mm[3], vv[3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) { pp[c] = p[c * K + id]; mm[c] = m[c * K + id]; vv[c] = v[c * K + id]; }
-        if (tl < step - 1) adam_replay(pp, mm, vv, tl + 1, step - 1, lr, b1, b2, eps, bc1, bc2);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            adam_elem(pp[c], mm[c], vv[c], g[c * K + id], lr, b1, b2, eps, c1, c2);
-            p[c * K + id] = pp[c]; m[c * K + id] = mm[c]; v[c * K + id] = vv[c]; g[c * K + id] = 0.f;
-        }
-    }
-}
 // end of the stage: every row to the last step
 __global__ void k_adam_catchup_all(size_t K, int* __restrict__ t_last, float* __restrict__ p, float* __restrict__ m, float* __restrict__ v, int upto,
                                    float lr, float b1, float b2, float eps, const float* __restrict__ bc1, const float* __restrict__ bc2) {
@@ -1076,7 +1016,7 @@ static StageWs carve_stage(char* base, int b, int h, int w) {
     S.cat = (float*)take(2 * b * 3 * P * 4); S.gimg = (float*)take(b * 3 * P * 4); S.gpre = (fxq_t*)take(b * 3 * P * sizeof(fxq_t));
     S.acc = (fx_t*)take(ACC_SLOTS * 4 * sizeof(fx_t)); S.efx = (fx_t*)take((size_t)2 * b * 12 * sizeof(fx_t));
     S.cidx = (int*)take(2 * b * 4);
-    S.cmask = (unsigned char*)take(2 * b * P);          // lazy stage 2: clamp mask of the gathered pixels (k_gather_codebook_lazy)
+    S.cmask = (unsigned char*)take(2 * b * P);          // stage 2: clamp mask of the gathered pixels (k_gather_codebook -> k_codebook_bwd)
     size_t msb = carve_ms(nullptr, b * 3, h, w).bytes;
     char* mp = take(msb);
     S.ms = carve_ms(mp, b * 3, h, w);
@@ -1125,19 +1065,9 @@ int tcl_exposure_grad(const float* edited, const float* flows, const float* mask
     TCL_LAUNCH_RET();
 }
 
-struct LazyGather { const float *m, *v, *bc1, *bc2; const int* t_last; int upto; float lr; };      // the lazy schedule's gather (rows may be behind)
-static int unique_tensor_grad_impl(const float* target, const float* flows, const float* masks, const int* flow_shift, const int* unq_inv, int N, int H, int W, size_t K,
-                                   int ids_unique, const int* d_cidx, int b_loc, int b_glob, int nvalid_glob, float lambda_dssim, float lambda_flow,
-                                   float lambda_tv, const float* feat, float* g, float* loss_part, void* ws, const LazyGather* lz, hipStream_t st);
 int tcl_unique_tensor_grad(const float* target, const float* flows, const float* masks, const int* flow_shift, const int* unq_inv, int N, int H, int W, size_t K,
                            int ids_unique, const int* d_cidx, int b_loc, int b_glob, int nvalid_glob, float lambda_dssim, float lambda_flow,
                            float lambda_tv, const float* feat, float* g, float* loss_part, void* ws, hipStream_t st) {
-    return unique_tensor_grad_impl(target, flows, masks, flow_shift, unq_inv, N, H, W, K, ids_unique, d_cidx, b_loc, b_glob, nvalid_glob, lambda_dssim,
-                                   lambda_flow, lambda_tv, feat, g, loss_part, ws, nullptr, st);
-}
-static int unique_tensor_grad_impl(const float* target, const float* flows, const float* masks, const int* flow_shift, const int* unq_inv, int N, int H, int W, size_t K,
-                                   int ids_unique, const int* d_cidx, int b_loc, int b_glob, int nvalid_glob, float lambda_dssim, float lambda_flow,
-                                   float lambda_tv, const float* feat, float* g, float* loss_part, void* ws, const LazyGather* lz, hipStream_t st) {
     TCL_CHECK_ARG(target && flows && masks && flow_shift && unq_inv && d_cidx && feat && g && loss_part && ws);
     TCL_CHECK_ARG(N > 0 && b_loc > 0 && b_loc <= 64 && b_glob >= b_loc && nvalid_glob >= 0 && H > 160 && W > 160 && K > 0);
     StageWs S = carve_stage((char*)ws, b_loc, H, W);
@@ -1145,9 +1075,7 @@ static int unique_tensor_grad_impl(const float* target, const float* flows, cons
     const int b = b_loc;
     S.cidx = const_cast<int*>(d_cidx);
     if (hipMemsetAsync(S.acc, 0, ACC_SLOTS * 4 * sizeof(fx_t), st) != hipSuccess) return TCL_ELAUNCH;
-    if (lz) hipLaunchKernelGGL(k_gather_codebook_lazy, pgrid(P, 2 * b), dim3(256), 0, st, feat, lz->m, lz->v, lz->t_last, unq_inv, S.cidx, S.cat, S.cmask, (int)P,
-                               K, lz->upto, lz->lr, 0.9f, 0.999f, 1e-15f, lz->bc1, lz->bc2);
-    else hipLaunchKernelGGL(k_gather_codebook, pgrid(P, 2 * b), dim3(256), 0, st, feat, unq_inv, S.cidx, S.cat, (int)P, K, S.cmask);
+    hipLaunchKernelGGL(k_gather_codebook, pgrid(P, 2 * b), dim3(256), 0, st, feat, unq_inv, S.cidx, S.cat, (int)P, K, S.cmask);
     const unsigned char* cmask = S.cmask;
     // loss = (1-lf)*ld*(1-msssim) + lf*flow + tv  -> fold (1-lf) into the ms-ssim lambda
     int rc = msssim_chain(S.cat, target, S.cidx, b * 3, H, W, (1.f - lambda_flow) * lambda_dssim, S.ms, true, st, b_glob * 3);
@@ -1247,23 +1175,15 @@ int tcl_unique_tensor_opt(const float* target, const float* flows, const float* 
         while (b < batch && bi[b] >= 0) { nvalid += bi[b] > 0; ++b; }
         TCL_CHECK_ARG(b > 0);
         const int* cidx = d_cat + (size_t)it * 2 * batch;
-        // lazy, default (rounds 3-5): a catch-up launch brings the mini-batch's rows to step `it` (writes them), the gather reads them, the step kernel
-        // applies step it + 1.  TCL_ADAM_LAZY_V1=0 (round 5, opt-in): ONE visit with a write -- the gather replays the skipped steps in registers and the step
-        // kernel replays them again before the gradient step.  Same bits; 208 -> 156 B of traffic per row, but the replay ARITHMETIC doubles: with the bench's
-        // ~19 skipped steps per visit (one visit per epoch) the two kernels take 2.2 ms against 2.0 for catch-up + gather + step
-        // (profiles/r5_bench_kernel_stats.txt vs r4), while on a 60-iteration run (short replays) it wins 5 % (profiles/r5_ab_path2_lazy_single_visit.txt).
-        static const bool v1 = !(getenv("TCL_ADAM_LAZY_V1") && atoi(getenv("TCL_ADAM_LAZY_V1")) == 0);
-        const LazyGather lz = {m, v, bc1, bc2, t_last, it, lr};
-        if (lazy && v1)
+        // lazy: a catch-up launch brings the mini-batch's rows to step `it` (writes them), the gather reads them, the step kernel applies step it + 1.
+        // (What a single visit without the catch-up launch measured: DESIGN 4.12, profiles/r5_ab_path2_lazy_single_visit.txt.)
+        if (lazy)
             hipLaunchKernelGGL(k_adam_catchup_frame, pgrid(P, 2 * b), dim3(256), 0, st, unq_inv, cidx, (int)P, K, t_last, feat, m, v, it, lr, 0.9f, 0.999f,
                                1e-15f, bc1, bc2);
-        int rc = unique_tensor_grad_impl(target, flows, masks, flow_shift, unq_inv, N, H, W, K, ids_unique, cidx, b, b, nvalid, lambda_dssim,
-                                         lambda_flow, lambda_tv, feat, g, losses + it, ws, (lazy && !v1) ? &lz : nullptr, st);
+        int rc = tcl_unique_tensor_grad(target, flows, masks, flow_shift, unq_inv, N, H, W, K, ids_unique, cidx, b, b, nvalid, lambda_dssim,
+                                        lambda_flow, lambda_tv, feat, g, losses + it, ws, st);
         if (rc) return rc;
-        if (lazy && !v1) {
-            hipLaunchKernelGGL(k_adam_step_rows_lazy, pgrid(P, 2 * b), dim3(256), 0, st, unq_inv, cidx, (int)P, K, t_last, feat, g, m, v, it + 1, lr, 0.9f,
-                               0.999f, 1e-15f, bc1, bc2);
-        } else if (lazy) {
+        if (lazy) {
             const float c1 = (float)(1.0 - pow((double)0.9f, it + 1)), c2 = (float)sqrt(1.0 - pow((double)0.999f, it + 1));
             AheadArg ah;
             for (int j = 0; j < 2 * b; ++j) ah.v[j] = ahead_tab[(size_t)it * 2 * batch + j];

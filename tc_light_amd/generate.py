@@ -119,26 +119,7 @@ class Generator:
         return groups
 
     def _run_groups(self, groups, Hh, Ww, t, text, pack, unpack):
-        """The UNet passes of one list of chunk groups.  pack(grp) -> (xin, idx, n); unpack(eps, idx, n).  TCL_SKEW=1: the groups go through
-        two at a time, half a transformer block apart (unet.py forward_pair) -- a lone group of several chunks is cut in two first; same bits."""
-        mode = os.environ.get("TCL_SKEW", "0")                  # "cut": the same groups, one after the other (the A/B and parity partner of "1")
-        if mode != "0":
-            cut = []
-            for grp in groups:
-                if len(grp) < 2:
-                    cut.append(grp)
-                    continue
-                tot = sum(len(c) for c in grp)
-                heads = [sum(len(c) for c in grp[:k]) for k in range(1, len(grp))]
-                k = 1 + min(range(len(heads)), key=lambda i: abs(2 * heads[i] - tot))         # the chunk boundary nearest to half the frames
-                cut += [grp[:k], grp[k:]]
-            groups = cut
-            while mode != "cut" and len(groups) >= 2:
-                ga, gb = groups[0], groups[1]
-                groups = groups[2:]
-                (xa, ia, na), (xb, ib, nb) = pack(ga), pack(gb)
-                ea, eb = self.unet.forward_pair(xa, [len(c) for c in ga], xb, [len(c) for c in gb], Hh, Ww, t, text, cfg_pair=True)
-                unpack(ea, ia, na); unpack(eb, ib, nb)
+        """One block-major UNet pass per group of chunks.  pack(grp) -> (xin, idx, n); unpack(eps, idx, n)."""
         for grp in groups:
             xin, idx, n = pack(grp)
             eps = self.unet.forward_many(xin, [len(c) for c in grp], Hh, Ww, t, text, cfg_pair=True)     # the pack kernel wrote both halves

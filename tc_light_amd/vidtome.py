@@ -78,13 +78,11 @@ class VidToMe:
                 randfs = self.round_frames(F)[1]
                 coin = float(self.rng.random())
             self._chunks.append((F, randfs, coin))
-        return self._chunks
 
-    def select_chunk(self, i, chunks=None):
-        """chunks: a list begin_step returned earlier (two groups of chunks in flight: unet.py forward_pair); default the last begin_step's."""
-        lst = chunks if chunks is not None else self._chunks
-        self._cur = (lst, i)
-        self.F, self.randfs, self.coin = lst[i]
+    def select_chunk(self, i):
+        """Make chunk i of the last begin_step the current one."""
+        self._cur = (self._chunks, i)
+        self.F, self.randfs, self.coin = self._chunks[i]
         self.randf = self.randfs[0] if self.randfs else -1
 
     def end_forward(self):
