@@ -199,7 +199,9 @@ int tcl_adain_fuse_f16(void* noises_t, void* noises, int planes, int hw, float a
  * x <- ca*x + cb0*m0 + cb1*m1 + cc*z (coefficients from tc_light_amd/scheduler.py; f32 math; m1/z may be NULL). */
 int tcl_dpm_sde_step_f16(void* x, const void* eps, float* m0, const float* m1, const void* z, long n, float sigma_t, float alpha_t, float ca,
                          float cb0, float cb1, float cc, hipStream_t st);
-/* layout conversions around the VAE (generate_utils.py:140-172): 2*img-1 -> NHWC8 f16; clamp(y/2+0.5) -> [B,3,H,W] f32. */
+/* layout conversions around the VAE (generate_utils.py:140-172): 2*img-1 -> NHWC8 f16; clamp(y/2+0.5) -> [B,3,H,W] f32.
+ * ldc = row stride in halves, >= the channels read or written (tcl_nchw_to_nhwc_f16 zeroes columns C..ldc-1); empty batches and narrower strides
+ * return TCL_EINVAL.  tcl_transpose_f16: in [batch,R,ldi] -> out [batch,Cc,ldo], ldi >= Cc, ldo >= R, padding columns of out are left untouched. */
 int tcl_img_to_nhwc8_f16(const float* img, void* out, int B, int HW, hipStream_t st);
 int tcl_nhwc_to_img_f32(const void* y, int ldc, float* img, int B, int HW, hipStream_t st);
 int tcl_nhwc_to_nchw_f16(const void* y, int ldc, void* out, int B, int C, int HW, float scale, hipStream_t st);
@@ -330,6 +332,8 @@ int tcl_resize_bilinear_f32(const float* x, float* y, int BC, int H, int W, int 
  * tcl_conv7x7s2_c3_f16: Conv2d(3, 64, 7, stride 2, padding 3) on x [B,3,H,W] f32 NCHW -> y [B,Ho,Wo,64] f16 NHWC; w_t [147,64] f32 with
  *   row c*49 + ky*7 + kx (an eval BatchNorm may be folded into w_t / bias), optional ReLU.
  * tcl_instnorm_f16: InstanceNorm2d (affine=False, biased variance, eps) over [B,HW,C] f16 NHWC, optional ReLU; deterministic.
+ *   C % 8 == 0, C <= 256, C / 8 a divisor of 256.  One pass of f32 sums of x - (the channel's value in the sample's first row): a channel whose mean is
+ *   large against its spread keeps its variance, an all-zero channel gives exactly 0.
  * tcl_add_act_f16: y = act(a + b), act 0 none / 3 ReLU / 4 GELU(erf); n elements (n % 8 == 0).
  * tcl_subsample2_nhwc_f16: y[b][i][j] = x[b][2i][2j] (the pixel selection of a stride-2 1x1 convolution). */
 int tcl_conv7x7s2_c3_f16(const float* x, const float* w_t, const float* bias, void* y, int B, int H, int W, int relu, hipStream_t st);

@@ -503,7 +503,7 @@ static void launch_layernorm(const void* x, const void* gamma, const void* beta,
 extern "C" {
 
 int tcl_conv1x1_small_f16(const void* x, int ldi, const void* W, const void* b, void* y, int ldo, long M, int Ci, int Co, hipStream_t st) {
-    TCL_CHECK_ARG(x && W && b && y && Ci > 0 && Ci <= 8 && Co > 0 && Co <= ldo && M > 0);
+    TCL_CHECK_ARG(x && W && b && y && Ci > 0 && Ci <= 8 && Ci <= ldi && Co > 0 && Co <= ldo && M > 0);
     hipLaunchKernelGGL(k_conv1x1_small, dim3(stream_grid(M, 256, 1)), dim3(256), 0, st, (const _Float16*)x, ldi, (const _Float16*)W, (const _Float16*)b,
                        (_Float16*)y, ldo, M, Ci, Co);
     TCL_LAUNCH_RET();
@@ -564,12 +564,12 @@ int tcl_softmax_rows_f16(void* x, long rows, int T, int ld, float scale, hipStre
     TCL_LAUNCH_RET();
 }
 int tcl_concat_channels_f16(const void* x1, int C1, const void* x2, int C2, void* y, long rows, hipStream_t st) {
-    TCL_CHECK_ARG(x1 && x2 && y && C1 % 8 == 0 && C2 % 8 == 0);
+    TCL_CHECK_ARG(x1 && x2 && y && rows > 0 && C1 >= 0 && C2 >= 0 && C1 + C2 > 0 && C1 % 8 == 0 && C2 % 8 == 0);
     hipLaunchKernelGGL(k_concat, dim3(stream_grid(rows * ((C1 + C2) / 8), 256, 2)), dim3(256), 0, st, (const _Float16*)x1, C1, (const _Float16*)x2, C2, (_Float16*)y, rows);
     TCL_LAUNCH_RET();
 }
 int tcl_im2col3x3_small_f16(const void* x, void* out, int B, int H, int W, int Cin, int Kpad, hipStream_t st) {
-    TCL_CHECK_ARG(x && out && Kpad >= 9 * Cin && Kpad % 64 == 0);
+    TCL_CHECK_ARG(x && out && B > 0 && H > 0 && W > 0 && Cin > 0 && Kpad >= 9 * Cin && Kpad % 64 == 0);
     hipLaunchKernelGGL(k_im2col_small, dim3(stream_grid((long)B * H * W * Kpad, 256, 4)), dim3(256), 0, st, (const _Float16*)x, (_Float16*)out, B, H, W, Cin, Kpad);
     TCL_LAUNCH_RET();
 }
@@ -609,27 +609,27 @@ int tcl_dpm_sde_step_f16(void* x, const void* eps, float* m0, const float* m1, c
     TCL_LAUNCH_RET();
 }
 int tcl_img_to_nhwc8_f16(const float* img, void* out, int B, int HW, hipStream_t st) {
-    TCL_CHECK_ARG(img && out);
+    TCL_CHECK_ARG(img && out && B > 0 && HW > 0);
     hipLaunchKernelGGL(k_img_to_nhwc, dim3(stream_grid((long)B * HW, 256, 1)), dim3(256), 0, st, img, (_Float16*)out, B, HW);
     TCL_LAUNCH_RET();
 }
 int tcl_nhwc_to_img_f32(const void* y, int ldc, float* img, int B, int HW, hipStream_t st) {
-    TCL_CHECK_ARG(y && img);
+    TCL_CHECK_ARG(y && img && B > 0 && HW > 0 && ldc >= 3);
     hipLaunchKernelGGL(k_nhwc_to_img, dim3(stream_grid((long)B * HW, 256, 1)), dim3(256), 0, st, (const _Float16*)y, ldc, img, B, HW);
     TCL_LAUNCH_RET();
 }
 int tcl_nhwc_to_nchw_f16(const void* y, int ldc, void* out, int B, int C, int HW, float scale, hipStream_t st) {
-    TCL_CHECK_ARG(y && out);
+    TCL_CHECK_ARG(y && out && B > 0 && HW > 0 && C > 0 && ldc >= C);
     hipLaunchKernelGGL(k_nhwc_to_nchw, dim3(stream_grid((long)B * HW, 256, 1)), dim3(256), 0, st, (const _Float16*)y, ldc, (_Float16*)out, B, C, HW, scale);
     TCL_LAUNCH_RET();
 }
 int tcl_nchw_to_nhwc_f16(const void* x, void* out, int ldc, int B, int C, int HW, float scale, hipStream_t st) {
-    TCL_CHECK_ARG(x && out);
+    TCL_CHECK_ARG(x && out && B > 0 && HW > 0 && C > 0 && ldc >= C);
     hipLaunchKernelGGL(k_nchw_to_nhwc, dim3(stream_grid((long)B * HW, 256, 1)), dim3(256), 0, st, (const _Float16*)x, (_Float16*)out, ldc, B, C, HW, scale);
     TCL_LAUNCH_RET();
 }
 int tcl_transpose_f16(const void* in, void* out, int batch, int R, int Cc, int ldi, int ldo, hipStream_t st) {
-    TCL_CHECK_ARG(in && out);
+    TCL_CHECK_ARG(in && out && batch > 0 && R > 0 && Cc > 0 && ldi >= Cc && ldo >= R);
     hipLaunchKernelGGL(k_transpose, dim3(cdiv(Cc, 32), cdiv(R, 32), batch), dim3(32, 8), 0, st, (const _Float16*)in, (_Float16*)out, R, Cc, ldi, ldo);
     TCL_LAUNCH_RET();
 }

@@ -314,7 +314,10 @@ __global__ __launch_bounds__(256) void k_conv7x7s2(const float* __restrict__ x, 
     }
 }
 
-// InstanceNorm2d (affine=False, biased variance) statistics, deterministic: per-block partial (sum, sumsq) per channel
+// InstanceNorm2d (affine=False, biased variance) statistics, deterministic: per-block partial (sum, sumsq) per channel of x - shift, where shift is the
+// channel's value in row 0 of the sample.  One pass stays, but E[d^2] - E[d]^2 is taken of values centred near the mean: a channel whose mean is large
+// against its spread (mean 6, std 0.05: the plain E[x^2] - mean^2 is 36.0025 - 36 at f32's 4e-6 resolution there) keeps its digits, and an all-zero
+// channel still gives mean 0, var 0 exactly.
 __global__ __launch_bounds__(256) void k_in_stats(const _Float16* __restrict__ x, int HW, int C, int rows_per_block, float* __restrict__ part) {
     __shared__ float ps[256][16];
     const int b = blockIdx.y, nchunk = C / 8;                           // C <= 256 -> nchunk <= 32
@@ -323,12 +326,14 @@ __global__ __launch_bounds__(256) void k_in_stats(const _Float16* __restrict__ x
     float s[8], q[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) s[j] = q[j] = 0.f;
-    if (tr < rp)
+    if (tr < rp) {
+        const h8 k = *(const h8*)(x + (long)b * HW * C + tc * 8);
         for (int row = r0 + tr; row < r1; row += rp) {
             const h8 v = *(const h8*)(x + ((long)b * HW + row) * C + tc * 8);
 #pragma unroll
-            for (int j = 0; j < 8; ++j) { const float f = (float)v[j]; s[j] += f; q[j] += f * f; }
+            for (int j = 0; j < 8; ++j) { const float f = (float)v[j] - (float)k[j]; s[j] += f; q[j] += f * f; }
         }
+    }
 #pragma unroll
     for (int j = 0; j < 8; ++j) { ps[threadIdx.x][j] = s[j]; ps[threadIdx.x][8 + j] = q[j]; }
     __syncthreads();
@@ -339,13 +344,13 @@ __global__ __launch_bounds__(256) void k_in_stats(const _Float16* __restrict__ x
         part[(((long)b * gridDim.x + blockIdx.x) * 2 + k) * C + c] = t;
     }
 }
-__global__ void k_in_reduce(const float* __restrict__ part, int nblk, int C, float inv_n, float eps, float* __restrict__ stat) {
+__global__ void k_in_reduce(const _Float16* __restrict__ x, const float* __restrict__ part, int nblk, int HW, int C, float inv_n, float eps, float* __restrict__ stat) {
     const int b = blockIdx.y, c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= C) return;
     float s = 0.f, q = 0.f;
     for (int i = 0; i < nblk; ++i) { s += part[(((long)b * nblk + i) * 2 + 0) * C + c]; q += part[(((long)b * nblk + i) * 2 + 1) * C + c]; }
-    const float mean = s * inv_n, var = fmaxf(q * inv_n - mean * mean, 0.f);
-    stat[((long)b * C + c) * 2] = mean; stat[((long)b * C + c) * 2 + 1] = rsqrtf(var + eps);
+    const float dm = s * inv_n, var = fmaxf(q * inv_n - dm * dm, 0.f);      // moments of x - shift
+    stat[((long)b * C + c) * 2] = (float)x[(long)b * HW * C + c] + dm; stat[((long)b * C + c) * 2 + 1] = rsqrtf(var + eps);
 }
 __global__ void k_in_apply(const _Float16* __restrict__ x, const float* __restrict__ stat, _Float16* __restrict__ y, int HW, int C, int relu) {
     const int b = blockIdx.y, nchunk = C / 8;
@@ -402,7 +407,7 @@ int tcl_instnorm_f16(const void* x, void* y, int B, int HW, int C, float eps, in
     const int rpb = cdiv(HW, blocks); blocks = cdiv(HW, rpb);
     float* part = (float*)ws; float* stat = part + (size_t)B * 256 * 2 * C;
     hipLaunchKernelGGL(k_in_stats, dim3(blocks, B), dim3(256), 0, st, (const _Float16*)x, HW, C, rpb, part);
-    hipLaunchKernelGGL(k_in_reduce, dim3(cdiv(C, 64), B), dim3(64), 0, st, part, blocks, C, 1.f / (float)HW, eps, stat);
+    hipLaunchKernelGGL(k_in_reduce, dim3(cdiv(C, 64), B), dim3(64), 0, st, (const _Float16*)x, part, blocks, HW, C, 1.f / (float)HW, eps, stat);
     const long chunks = (long)HW * (C / 8);
     hipLaunchKernelGGL(k_in_apply, dim3(stream_grid(chunks, 256, 2) > 2048 ? 2048 : stream_grid(chunks, 256, 2), B), dim3(256), 0, st,
                        (const _Float16*)x, stat, (_Float16*)y, HW, C, relu);
