@@ -239,6 +239,8 @@ int tcl_tome_normalize_f16(const void* x, void* y, long rows, int C, hipStream_t
  * reference orders them by score, which only permutes the tokens of a permutation-invariant attention).
  * Outputs: mrg[na-r+nb] = input position feeding each merged slot ([unmerged src | dst], mode "replace");
  *          unm[position] = merged slot each input position is restored from (merge.py:135-155).
+ * Exactly the entries named above are written: mrg[0 .. na-r+nb) and unm[p] for every p in a_pos or b_pos; unm at a position that neither list names is
+ * left as the caller had it.  a_pos and b_pos are read while the maps are written: mrg / unm must not overlap them (nor each other).
  * ws: tcl_tome_match_workspace_bytes(na) bytes, ZEROED ONCE by the caller before the first call and then only passed to this function
  * (one stream; may be re-used for any smaller na): every call leaves it all-zero again except two result words at a fixed offset (layout:
  * 4 KiB control | 256 KiB unused, formerly score-histogram bins | keys).  Per call: the score kernel + two small launches (threshold select, maps). */
