@@ -435,6 +435,30 @@ int tcl_clip_scores(const float* feats, const float* text, int N, int D, double*
  *   input gives the same bits. */
 int tcl_pick_scores(const float* feats, const float* text, int N, int D, float logit_scale, double* out, hipStream_t st);
 
+/* ===================================================================== spatio-temporal Unique Video Tensor (sceneflow scenes); csrc/voxel.hip */
+/* SceneFlowDataParser.rgbd2pcd  utils/dataparsers/sceneflow_dataparsers.py:257-274.  depth [N,H,W], c2w [N,4,4] row-major -> p_world [N,3,H,W]
+ *   (planar, so process_frames applies directly).  Per pixel, without fma contraction: x = (px - cx) * d / fx (product, then quotient), y likewise,
+ *   p_world[j] = ((x * c2w[j][0] + (-y) * c2w[j][1]) + (-d) * c2w[j][2]) + c2w[j][3].  N in 1..65535, H, W > 0, H * W < 2^31, else TCL_EINVAL. */
+int tcl_unproject_sceneflow(const float* depth, const float* c2w, int N, int H, int W, float fx, float fy, float cx, float cy, float* p_world,
+                            hipStream_t st);
+/* torch_scatter.scatter(values, ids, dim=0, reduce='mean')  utils/general_utils.py:237,239.  values [N,C,H,W] (C <= 3), ids [N,H,W] in [0, K)
+ *   (entries outside are skipped) -> mean [K,C], cnt [K] (f32 counts).  PRECONDITION: the ids of every frame are pairwise distinct
+ *   (tcl_track_ids_unique == 1).  f32 sums one frame after the other, no atomics, then ONE division by max(cnt, 1): exactly a sequential scatter in
+ *   row order, bit for bit. */
+int tcl_track_mean_f32(const float* values, const int* ids, int N, int C, int H, int W, size_t K, float* mean, float* cnt, hipStream_t st);
+/* The quantisation of utils/general_utils.py:238,243-250: keys [K,6] int32 = (floor_div(xyz - xyz_min, voxel_size) | floor_div(rgb, rgb_vox_size)) in
+ *   the order (x, y, z, r, g, b) of torch.cat([coord, rgb]).  mean_rgb, mean_xyz [K,3]; xyz_min: 3 floats (device).  floor_div restates
+ *   c10::div_floor_floating (torch div(rounding_mode='floor')) without fma contraction; the float result is converted saturating, NaN -> 0. */
+int tcl_voxel_keys(const float* mean_rgb, const float* mean_xyz, const float* xyz_min, float voxel_size, float rgb_vox_size, size_t K, int* keys,
+                   hipStream_t st);
+/* torch.unique(keys, dim=0, return_inverse=True)  utils/general_utils.py:230,251.  keys [n,C] int32, 1 <= C <= 6 -> inv [n] int32, *count (device
+ *   int) = number of distinct rows.  Ids are numbered in order of FIRST APPEARANCE in row order (the reference: lexicographic rank; the same
+ *   partition, a permutation of the numbering) and are bit-identical from run to run.  ws: tcl_unique_rows_workspace_bytes(n) bytes; the call
+ *   clears what it needs itself, so a workspace may be reused across calls without the caller clearing it.  n > 2^30 or C outside 1..6 returns
+ *   TCL_EINVAL (the workspace size is then 0). */
+size_t tcl_unique_rows_workspace_bytes(size_t n);
+int tcl_unique_rows_i32(const int* keys, size_t n, int C, int* inv, int* count, void* ws, hipStream_t st);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,4 +1,6 @@
 """Entry point with the reference's surface (run.py:8-32): python run.py --config Y | -i video -p prompt [-n neg] [--multi_axis].
+data.scene_type picks the parser (generate.py:84-95): video (VideoDataParser) or sceneflow (SceneFlowDataParser: ground-truth depth, poses and
+flows -> voxelised Unique Video Tensor ids); carla and interiornet are not built.
 
 load_config -> seed_everything -> init_iclight -> Generator -> output.mp4 (frames / .npy when the image has no encoder), output_gt, loss
 curves and config.yaml with the reference's metric keys (total_time, sec_per_frame, max_memory_allocated, total_number_of_frames;
@@ -33,6 +35,11 @@ def main(argv=None):
     if config.generation.prompt is None:          # checked before models, video and flow estimation are paid for
         raise NotImplementedError("generation.prompt is null: the Cosmos/Pixtral prompt up-sampler (generate.py:538-549) is outside this "
                                   "engine -- give a prompt (-p ... or generation.prompt)")
+    scene_type = str(config.data.get("scene_type", "video")).lower()      # generate.py:84-95; checked before any model is loaded
+    if scene_type in ("carla", "interiornet"):
+        raise NotImplementedError(f"data.scene_type '{scene_type}': this dataparser is not yet built in tc_light_amd (video and sceneflow are)")
+    if scene_type not in ("video", "sceneflow"):
+        raise NotImplementedError(f"Scene type '{scene_type}' is not supported.")
     world, rank, local = (int(os.environ.get(k, d)) for k, d in (("WORLD_SIZE", 1), ("RANK", 0), ("LOCAL_RANK", 0)))
     dev = torch.device("cuda", local)
     torch.cuda.set_device(dev)
@@ -43,15 +50,22 @@ def main(argv=None):
     ok_random = allow_random(models)
     pipe, scheduler, config.model_key = init_iclight(dev, models, seed=config.seed)
     config.max_memory_allocated, config.total_time = 0, 0
-    parser = VideoDataParser(config.data, dev)
+    if scene_type == "sceneflow":
+        from tc_light_amd.sceneflow import SceneFlowDataParser
+        parser = SceneFlowDataParser(config.data, dev)
+    else:
+        parser = VideoDataParser(config.data, dev)
     g = config.generation
     frame_ids = get_frame_ids(g.frame_range, parser.n_frames, g.frame_ids)
     config.total_number_of_frames = len(frame_ids)
     d = Dist(rank, world)
     lo, hi = d.range(len(frame_ids))
     frames_all = parser.load_video(frame_ids)
-    flows = None
-    if config.post_opt.apply_opt:
+    flows = scene = None
+    if config.post_opt.apply_opt and scene_type == "sceneflow":
+        # every rank reads the files itself: ground-truth (or RAFT) flows, masks and the voxelised ids all come from load_data
+        scene = parser.load_data(frame_ids, models=models, allow_random=ok_random)
+    elif config.post_opt.apply_opt:
         # rank 0 owns the flow cache (read, or estimated with MemFlowNet / RAFT (data.flow_model) and written: video_dataparser.py:63-110); the other ranks
         # receive the tensors.  A failure on rank 0 (e.g. missing MemFlow weights) is announced before the payload so that every
         # rank raises instead of waiting in the broadcast until the collective times out.
@@ -88,7 +102,9 @@ def main(argv=None):
         conds = encode_prompt_pair(prompt, g.negative_prompt, dev, models.get("text_encoder"), allow_random=ok_random)
         conds_t = encode_prompt_pair(g.prompt_t, g.negative_prompt_t, dev, models.get("text_encoder"), allow_random=ok_random)
         masks = inv = k = past = None
-        if config.post_opt.apply_opt:
+        if scene is not None:
+            masks, inv, k, past = scene["masks"], scene["inv"], scene["k"], scene["past_flows"]
+        elif config.post_opt.apply_opt:
             from tc_light_amd.flow_ids import soft_masks_and_ids
             fut, past = flows
             masks, inv, k = soft_masks_and_ids(frames_all, fut, past, alpha=parser.alpha)

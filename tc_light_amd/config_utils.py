@@ -88,7 +88,9 @@ def load_config(argv=None, print_config=True):
         cfg.generation.negative_prompt = a.negative_prompt
     if a.prompt is not None or isinstance(cfg.generation.prompt, str):
         prompt = cfg.generation.prompt if a.prompt is None else a.prompt
-        video = os.path.splitext(os.path.basename(cfg.data.rgb_path))[0]
+        # the reference names the run after data.rgb_path; a scene without one (sceneflow) is named after its scene_path
+        src = cfg.data.get("rgb_path") or str(cfg.data.get("scene_path", cfg.data.scene_type)).replace("/", "_")
+        video = os.path.splitext(os.path.basename(src))[0]
         cfg.work_dir = os.path.join(cfg.work_dir, datetime.now().strftime("%m-%d-%Y"), video)
         os.makedirs(cfg.work_dir, exist_ok=True)
         prev = [int(x[-5:]) for x in os.listdir(cfg.work_dir) if x[-5:].isdigit()]
