@@ -111,7 +111,7 @@ int tcl_gemm_f16(const void* A, const void* W, const void* bias, const void* res
 /* Register caller-owned device scratch for split-K partial sums (used by tcl_gemm_f16 / tcl_conv3x3_f16 when the tile grid
  * would leave most CUs idle).  NULL disables split-K.  All calls that use it must be issued on one stream. */
 int tcl_set_workspace(void* ws, size_t bytes);
-/* Tuning / test hook: force the kernel configuration (cfg ids in csrc/gemm.hip; 0 = automatic choice) and the number of K
+/* Tuning / test hook: force the kernel configuration (cfg ids: the tile table g_tiles in csrc/gemm.hip; 0 = automatic choice) and the number of K
  * splits (0/1 = none) for every following tcl_gemm_f16 / tcl_conv3x3_f16 call; calls the forced configuration cannot serve
  * return TCL_EINVAL.  Process-global, not thread-safe. */
 int tcl_gemm_tune(int cfg, int splits);
@@ -127,6 +127,13 @@ int tcl_gemm_autotune(int enable);
 int tcl_gemm_tune_save(const char* path);
 int tcl_gemm_tune_load(const char* path);
 size_t tcl_gemm_tune_size(void);
+/* Host-only query: which tile configuration (*cfg, an id of the table in csrc/gemm.hip) and how many K splits (*splits) a tcl_gemm_f16 /
+ * tcl_conv3x3_f16 call with these scalar arguments gets under the current workspace, forced configuration, table and autotune mode.  resid: 0 = none,
+ * 1 = a separate tensor, 2 = in place (resid == C / Y).  *cfg = 0: the tuner would time the shape on first use.  It is the dispatcher's own choice
+ * function, asked without operands: nothing is launched and no device memory is touched, so it runs on a machine without a GPU.  TCL_EINVAL where the
+ * call itself would return it. */
+int tcl_gemm_plan(int M, int N, int K, int lda, int ldw, int ldc, int ldr, int act, int resid, int* cfg, int* splits);
+int tcl_conv3x3_plan(int B, int Hin, int Win, int Cin, int Cout, int stride, int pad, int Hup, int Wup, int act, int resid, int* cfg, int* splits);
 /* 3x3 Conv2d as implicit GEMM on NHWC: X [B,Hin,Win,Cin], W [Cout, 9*Cin] (tap-major: (ky*3+kx)*Cin + c), Y [B,Hout,Wout,Cout].
  * pad=1: padding 1 (UNet ResnetBlock2D / Downsample2D stride 2); pad=0 with stride 2: the VAE encoder's (0,1,0,1) padding.
  * Hup/Wup > 0: the input is first nearest-upsampled to Hup x Wup (Upsample2D with explicit output size), fused in the gather. */

@@ -21,6 +21,7 @@
 #include "../../include/tclight_hip.h"
 #include <stdlib.h>
 #include <math.h>
+#include <limits.h>
 #include <unordered_map>
 #include "gemm_conv.h"
 #include "prof.h"
@@ -497,24 +498,23 @@ __global__ void k_splitk_finalize(const float* __restrict__ part, int splits, co
                                   _Float16* __restrict__ C, int M, int N, int ldc, int ldr, int act);
 
 template <int BM, int BN, int WM, int WN, int STAGES>
-static int launch_gemm_dma(const _Float16* A, const _Float16* W, const _Float16* bias, const _Float16* resid, _Float16* C, int M, int N,
-                           int K, int lda, int ldw, int ldc, int ldr, int act, const ConvP& cp, hipStream_t st, int splits = 1) {
-    const int tm = cdiv(M, BM), tn = cdiv(N, BN), nk = K / 32;
+static int launch_gemm_dma(const GemmCall& c, int splits) {
+    const int tm = cdiv(c.M, BM), tn = cdiv(c.N, BN), nk = c.K / 32;
     const size_t ops = (size_t)STAGES * (BM + BN) * 64, cs = (size_t)BM * (BN + 8) * 2, lds = ops > cs ? ops : cs;
     static bool attr_set = false;
     if (!attr_set) { (void)hipFuncSetAttribute((const void*)k_gemm_dma<BM, BN, WM, WN, STAGES>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr_set = true; }
     if (splits > nk / 4) splits = nk / 4 > 0 ? nk / 4 : 1;
-    while (splits > 1 && (!g_ws || (size_t)splits * M * N * 4 > g_ws_bytes)) --splits;
-    if (act == 2) splits = 1;
+    while (splits > 1 && (!g_ws || (size_t)splits * c.M * c.N * 4 > g_ws_bytes)) --splits;
+    if (c.act == 2) splits = 1;
     const int nk_per = cdiv(nk, splits);
     splits = cdiv(nk, nk_per);
     float* part = splits > 1 ? g_ws : nullptr;
     static const int xcd_mode = getenv("TCL_GEMM_XCDN") ? atoi(getenv("TCL_GEMM_XCDN")) : -1;      // -1 auto, 0/1 forced (experiments)
-    const int xcd_n = xcd_mode < 0 ? (N > M) : xcd_mode;
+    const int xcd_n = xcd_mode < 0 ? (c.N > c.M) : xcd_mode;
     const int grid = (xcd_n ? cdiv(tn, 8) * 8 * tm : cdiv(tm, 8) * 8 * tn) * splits;
-    hipLaunchKernelGGL((k_gemm_dma<BM, BN, WM, WN, STAGES>), dim3(grid), dim3(256), lds, st, A, W, bias, resid, C, M, N, K, lda, ldw, ldc, ldr,
-                       act, cp, tm, tn, nk_per, part, xcd_n, QkvPanel{});
-    if (part) hipLaunchKernelGGL(k_splitk_finalize, dim3(stream_grid((long)M * N, 256, 4)), dim3(256), 0, st, part, splits, bias, resid, C, M, N, ldc, ldr, act);
+    hipLaunchKernelGGL((k_gemm_dma<BM, BN, WM, WN, STAGES>), dim3(grid), dim3(256), lds, c.st, c.A, c.W, c.bias, c.resid, c.C, c.M, c.N, c.K, c.lda, c.ldw,
+                       c.ldc, c.ldr, c.act, c.cp, tm, tn, nk_per, part, xcd_n, QkvPanel{});
+    if (part) hipLaunchKernelGGL(k_splitk_finalize, dim3(stream_grid((long)c.M * c.N, 256, 4)), dim3(256), 0, c.st, part, splits, c.bias, c.resid, c.C, c.M, c.N, c.ldc, c.ldr, c.act);
     return hipPeekAtLastError() == hipSuccess ? TCL_OK : TCL_ELAUNCH;
 }
 
@@ -549,9 +549,8 @@ __global__ void k_splitk_finalize(const float* __restrict__ part, int splits, co
 }
 
 template <int BM, int BN, int WM, int WN, int PF>
-static int launch_gemm(const _Float16* A, const _Float16* W, const _Float16* bias, const _Float16* resid, _Float16* C, int M, int N,
-                       int K, int lda, int ldw, int ldc, int ldr, int act, const ConvP& cp, hipStream_t st) {
-    const int tm = cdiv(M, BM), tn = cdiv(N, BN);
+static int launch_gemm(const GemmCall& c, int /* splits: this family splits K by the rule below */) {
+    const int tm = cdiv(c.M, BM), tn = cdiv(c.N, BN);
     const int grid = cdiv(tm, 8) * 8 * tn;
     const size_t lds = (size_t)(BM + BN) * LDS_STRIDE * 2;
     static_assert((size_t)BM * (BN + 8) * 2 <= (size_t)(BM + BN) * LDS_STRIDE * 2, "C staging must fit");
@@ -559,82 +558,72 @@ static int launch_gemm(const _Float16* A, const _Float16* W, const _Float16* bia
     if (!attr_set) { (void)hipFuncSetAttribute((const void*)k_gemm<BM, BN, WM, WN, PF>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr_set = true; }
     // small-M / deep-K problems (the 1280-channel levels, yt-plane chunks) leave most of the 256 CUs idle: split K so that
     // ~2 blocks per CU exist, partials in f32, deterministic second pass.
-    const int nk = K / BK;
+    const int nk = c.K / BK;
     int splits = 1;
     const int sk_tiles = 700, sk_target = 1024;
-    if (tm * tn < sk_tiles && nk >= 32 && g_ws && act != 2) {     // measured: splitting K < 2048 loses to the extra pass
+    if (tm * tn < sk_tiles && nk >= 32 && g_ws && c.act != 2) {     // measured: splitting K < 2048 loses to the extra pass
         splits = min(nk / 8, cdiv(sk_target, tm * tn));
-        while (splits > 1 && (size_t)splits * M * N * 4 > g_ws_bytes) --splits;
+        while (splits > 1 && (size_t)splits * c.M * c.N * 4 > g_ws_bytes) --splits;
     }
     const int nk_per = cdiv(nk, splits);
     splits = cdiv(nk, nk_per);
     float* part = splits > 1 ? g_ws : nullptr;
-    hipLaunchKernelGGL((k_gemm<BM, BN, WM, WN, PF>), dim3(grid * splits), dim3(256), lds, st, A, W, bias, resid, C, M, N, K, lda, ldw, ldc, ldr, act, cp,
-                       tm, tn, nk_per, part);
-    if (part) hipLaunchKernelGGL(k_splitk_finalize, dim3(stream_grid((long)M * N, 256, 4)), dim3(256), 0, st, part, splits, bias, resid, C, M, N, ldc, ldr, act);
+    hipLaunchKernelGGL((k_gemm<BM, BN, WM, WN, PF>), dim3(grid * splits), dim3(256), lds, c.st, c.A, c.W, c.bias, c.resid, c.C, c.M, c.N, c.K, c.lda, c.ldw, c.ldc,
+                       c.ldr, c.act, c.cp, tm, tn, nk_per, part);
+    if (part) hipLaunchKernelGGL(k_splitk_finalize, dim3(stream_grid((long)c.M * c.N, 256, 4)), dim3(256), 0, c.st, part, splits, c.bias, c.resid, c.C, c.M, c.N, c.ldc, c.ldr, c.act);
     return hipPeekAtLastError() == hipSuccess ? TCL_OK : TCL_ELAUNCH;
 }
 
-// ---- configuration choice.  cfg ids (also the tcl_gemm_tune ids):
-//   1 dma 128x128   2 dma 64x128   3 dma 128x64   4 dma 64x64   11 dma 256x128      (k_gemm_dma, 3 stages, optional split-K)
-//   5 g8 256x320    6 g8 128x320   7 g8 256x256   8 g8 128x256                      (gemm8.hip, 8-wave ping-pong)
-//   9 reg 128x128   10 reg 128x64                                                    (k_gemm, register-staged; any N / ld)
-//   12 strip-resident K = 320 Linear (linstrip.hip: 128 activation rows in registers, weight rows swept through LDS)
-//   13 q8 256x256   14 q8 256x320   15 q8 512x128                                                    (gemm8q.hip, 8-phase 256-row kernels, round 4)
-static int g_tune_cfg = 0, g_tune_splits = 0;
+// ---- The tile configurations: g_tiles is the one place that says what a cfg id means.  The ids are the tcl_gemm_tune ids and what the persistent table
+// (gemm_tune_gfx950.txt) stores, so they stay put.  Families: dma = k_gemm_dma (3 stages, optional split-K), g8 = gemm8.hip (8-wave ping-pong), q8 =
+// gemm8q.hip (8-phase 256-row kernels), strip = linstrip.hip (128 activation rows in registers, weight rows swept through LDS), reg = k_gemm (register-
+// staged; any N / ld).  tabled: a persistent table may name the tile; timed: the tuner may time it, in the order of the array (the first of equally fast
+// candidates wins); ok: can the kernel serve this call at all (alignment, epilogue, addressing); worth: is the tile a candidate at this size -- also asked
+// of a table entry (a stale or hand-edited table must not route a shape to a tile that does not divide N or that drops the K split).
+struct TileCfg {
+    int id; const char* name; bool tabled, timed;
+    bool (*ok)(const GemmCall&);
+    bool (*worth)(int M, int N, int K, int splits);
+    int (*run)(const GemmCall&, int splits);
+};
+enum { DMA_128x128 = 1, DMA_128x64 = 3, REG_128x128 = 9, REG_128x64 = 10, STRIP = 12 };      // the ids the choice below names
 
-static int run_cfg(int cfg, int splits, const _Float16* A, const _Float16* W, const _Float16* bias, const _Float16* resid, _Float16* C, int M, int N,
-                   int K, int lda, int ldw, int ldc, int ldr, int act, const ConvP& cp, hipStream_t st) {
-    switch (cfg) {
-        case 1: return launch_gemm_dma<128, 128, 2, 2, 3>(A, W, bias, resid, C, M, N, K, lda, ldw, ldc, ldr, act, cp, st, splits);
-        case 2: return launch_gemm_dma<64, 128, 2, 2, 3>(A, W, bias, resid, C, M, N, K, lda, ldw, ldc, ldr, act, cp, st, splits);
-        case 3: return launch_gemm_dma<128, 64, 2, 2, 3>(A, W, bias, resid, C, M, N, K, lda, ldw, ldc, ldr, act, cp, st, splits);
-        case 4: return launch_gemm_dma<64, 64, 2, 2, 3>(A, W, bias, resid, C, M, N, K, lda, ldw, ldc, ldr, act, cp, st, splits);
-        case 11: return launch_gemm_dma<256, 128, 2, 2, 3>(A, W, bias, resid, C, M, N, K, lda, ldw, ldc, ldr, act, cp, st, splits);
-        case 5: case 6: case 7: case 8: return gemm8_dispatch(cfg - 4, A, W, bias, resid, C, M, N, K, lda, ldw, ldc, ldr, act, cp, st);
-        case 9: return launch_gemm<128, 128, 2, 2, 1>(A, W, bias, resid, C, M, N, K, lda, ldw, ldc, ldr, act, cp, st);
-        case 10: return launch_gemm<128, 64, 4, 1, 1>(A, W, bias, resid, C, M, N, K, lda, ldw, ldc, ldr, act, cp, st);
-        case 13: case 14: case 15: return gemm8q_dispatch(cfg - 12, A, W, bias, resid, C, M, N, K, lda, ldw, ldc, ldr, act, cp, st);
-        case 12:
-            // the strip kernel's last weight tile is moved back when N % 128 != 0 and re-reads the residual of the overlapped columns: with an
-            // in-place residual (resid == C) those columns would get it twice -> such a call takes the tiled kernel
-            if (resid == C && N % 128 != 0) return run_cfg((N % 128 == 0 || N > 192) ? 1 : 3, splits, A, W, bias, resid, C, M, N, K, lda, ldw, ldc, ldr, act, cp, st);
-            return lin_strip_dispatch(A, W, bias, resid, C, M, N, K, lda, ldw, ldc, ldr, act, st);
-    }
-    return TCL_EINVAL;
-}
+static bool vec_ok(const GemmCall& c) { return (c.N & 7) == 0 && (c.ldc & 7) == 0 && (!c.has_resid() || (c.ldr & 7) == 0) && (c.K % 32) == 0; }
+static bool g8_ok(const GemmCall& c) { return vec_ok(c) && c.K % 64 == 0 && (!c.cp.conv || c.cp.Cin % 64 == 0); }
+static bool g8_320_ok(const GemmCall& c) { return c.act != 2 && g8_ok(c); }      // GEGLU: 64-column wave strips only
+template <int BN> static bool q8_ok(const GemmCall& c) { return vec_ok(c) && gemm8q_ok(BN, c); }
+static bool strip_ok(const GemmCall& c) { return vec_ok(c) && lin_strip_ok(c); }
+static bool any_ok(const GemmCall&) { return true; }
+static bool no_geglu_ok(const GemmCall& c) { return c.act != 2; }
+template <int LO, int HI> static bool t128_worth(int M, int N, int, int) { const int t = cdiv(M, 128) * cdiv(N, 128); return t >= LO && t < HI; }
+// the 8-wave / 8-phase tiles: no K split, K deep enough, whole tiles along N and enough of them to occupy the CUs
+template <int BM, int BN, int KMIN> static bool wide_worth(int M, int N, int K, int splits) { return splits == 1 && K >= KMIN && N % BN == 0 && cdiv(M, BM) * (N / BN) >= 96; }
+static bool q8_128_worth(int M, int N, int K, int splits) { return N % 256 != 0 && wide_worth<512, 128, 320>(M, N, K, splits); }
+static bool strip_worth(int M, int N, int K, int splits) { return splits == 1 && K == 320 && N >= 128 && M >= 16384; }
+static bool never_worth(int, int, int, int) { return false; }
+template <int (*F)(const GemmCall&)> static int unsplit(const GemmCall& c, int) { return F(c); }      // families without a K split
+static int run_strip(const GemmCall& c, int) { return lin_strip_dispatch(c); }
 
-static bool cfg_ok(int cfg, int M, int N, int K, int ldc, int ldr, bool has_resid, int act, const ConvP& cp) {
-    const bool vec_ok = (N & 7) == 0 && (ldc & 7) == 0 && (!has_resid || (ldr & 7) == 0) && (K % 32) == 0;
-    if (cfg == 9 || cfg == 10) return act != 2 || cfg == 9;
-    if (!vec_ok) return false;
-    if (cfg == 12) return lin_strip_ok(M, N, K, 8, 8, ldc, ldr, has_resid, act, cp);     // lda / ldw: multiples of 8 by tcl_gemm_f16's argument check
-    if (cfg >= 13 && cfg <= 15) return gemm8q_ok(cfg - 12, M, N, K, 8, 8, ldc, ldr, has_resid, act, cp);
-    if (cfg >= 5 && cfg <= 8) return (act != 2 || cfg >= 7) && K % 64 == 0 && (!cp.conv || cp.Cin % 64 == 0);   // GEGLU: 64-column wave strips only
-    if (act == 2) return true;                                          // GEGLU epilogue: 64-column [value | gate] groups, every BN is a multiple
-    return true;
-}
-
-// Which tiles the tuner may time for a shape -- and which a persistent table entry may name (a stale or hand-edited table must
-// not route a shape to a tile that does not divide N or that drops the K split its candidates were measured with).
-static bool tile_ok(int cfg, int M, int N, int K, int splits) {
-    const int t128 = cdiv(M, 128) * cdiv(N, 128);
-    switch (cfg) {
-        case 1: return true;
-        case 2: case 3: return t128 < 4096;
-        case 4: return t128 < 1024;
-        case 11: return t128 >= 256;
-        case 5: return splits == 1 && K >= 512 && N % 320 == 0 && cdiv(M, 256) * (N / 320) >= 96;
-        case 6: return splits == 1 && K >= 512 && N % 320 == 0 && cdiv(M, 128) * (N / 320) >= 96;
-        case 7: return splits == 1 && K >= 512 && N % 256 == 0 && cdiv(M, 256) * (N / 256) >= 96;
-        case 8: return splits == 1 && K >= 512 && N % 256 == 0 && cdiv(M, 128) * (N / 256) >= 96;
-        case 12: return splits == 1 && K == 320 && N >= 128 && M >= 16384;
-        case 13: return splits == 1 && K >= 320 && N % 256 == 0 && cdiv(M, 256) * (N / 256) >= 96;
-        case 14: return splits == 1 && K >= 320 && N % 320 == 0 && cdiv(M, 256) * (N / 320) >= 96;
-        case 15: return splits == 1 && K >= 320 && N % 128 == 0 && N % 256 != 0 && cdiv(M, 512) * (N / 128) >= 96;
-    }
-    return false;
-}
+static const TileCfg g_tiles[] = {
+    {DMA_128x128, "dma 128x128", true, true, vec_ok, t128_worth<0, INT_MAX>, launch_gemm_dma<128, 128, 2, 2, 3>},
+    {2, "dma 64x128", true, true, vec_ok, t128_worth<0, 4096>, launch_gemm_dma<64, 128, 2, 2, 3>},
+    {DMA_128x64, "dma 128x64", true, true, vec_ok, t128_worth<0, 4096>, launch_gemm_dma<128, 64, 2, 2, 3>},
+    {4, "dma 64x64", true, true, vec_ok, t128_worth<0, 1024>, launch_gemm_dma<64, 64, 2, 2, 3>},
+    {11, "dma 256x128", true, true, vec_ok, t128_worth<256, INT_MAX>, launch_gemm_dma<256, 128, 2, 2, 3>},
+    {5, "g8 256x320", true, true, g8_320_ok, wide_worth<256, 320, 512>, unsplit<gemm8_256x320>},
+    {6, "g8 128x320", true, true, g8_320_ok, wide_worth<128, 320, 512>, unsplit<gemm8_128x320>},
+    {7, "g8 256x256", true, true, g8_ok, wide_worth<256, 256, 512>, unsplit<gemm8_256x256>},
+    {8, "g8 128x256", true, true, g8_ok, wide_worth<128, 256, 512>, unsplit<gemm8_128x256>},
+    {STRIP, "strip K=320", true, true, strip_ok, strip_worth, run_strip},
+    {13, "q8 256x256", true, true, q8_ok<256>, wide_worth<256, 256, 320>, unsplit<gemm8q_256x256>},
+    {14, "q8 256x320", true, true, q8_ok<320>, wide_worth<256, 320, 320>, unsplit<gemm8q_256x320>},
+    {15, "q8 512x128", true, true, q8_ok<128>, q8_128_worth, unsplit<gemm8q_512x128>},
+    // the register-staged kernels serve what the vector epilogues cannot (odd N / ld): never tabled or timed, chosen by heuristic_cfg alone
+    {REG_128x128, "reg 128x128", false, false, any_ok, never_worth, launch_gemm<128, 128, 2, 2, 1>},
+    {REG_128x64, "reg 128x64", false, false, no_geglu_ok, never_worth, launch_gemm<128, 64, 4, 1, 1>},
+};
+static const TileCfg* tile(int id) { for (const TileCfg& t : g_tiles) if (t.id == id) return &t; return nullptr; }
+static bool usable(int id, const GemmCall& c, int splits) { const TileCfg* t = tile(id); return t && t->ok(c) && t->worth(c.M, c.N, c.K, splits); }
 
 // ---- automatic choice: a per-process cache keyed by the problem shape, filled on first use by timing the valid candidates on the
 // caller's stream (hipEvents; the tuning call synchronises the stream, later calls are a hash lookup).  Numerics do not depend
@@ -643,10 +632,7 @@ static bool tile_ok(int cfg, int M, int N, int K, int splits) {
 // the shape (split_rule), identical for all candidates.
 struct TuneKey {
     int conv, M, N, K, act, hasr, Hin, Win, Cin, stride, Hup;
-    bool operator==(const TuneKey& o) const {
-        return conv == o.conv && M == o.M && N == o.N && K == o.K && act == o.act && hasr == o.hasr && Hin == o.Hin && Win == o.Win && Cin == o.Cin &&
-               stride == o.stride && Hup == o.Hup;
-    }
+    bool operator==(const TuneKey& o) const { return !memcmp(this, &o, sizeof *this); }      // eleven ints, no padding
 };
 struct TuneKeyHash {
     size_t operator()(const TuneKey& k) const {
@@ -656,10 +642,11 @@ struct TuneKeyHash {
         return h;
     }
 };
+static TuneKey tune_key(const GemmCall& c) { return {c.cp.conv, c.M, c.N, c.K, c.act, (int)c.has_resid(), c.cp.Hin, c.cp.Win, c.cp.Cin, c.cp.stride, c.cp.Hup}; }
 static std::unordered_map<TuneKey, int, TuneKeyHash> g_tune_cache;
 static std::unordered_map<TuneKey, int, TuneKeyHash> g_near_cache;      // un-tabled shapes -> the tile of their nearest-M twin (0 = none)
 #define TUNE_MAGIC "!tcl-gemm-table gfx950 v4"        // bump when tiles / schedules change: older tables are refused, not trusted
-static int g_autotune = 1;
+static int g_autotune = 1, g_tune_cfg = 0, g_tune_splits = 0;
 
 static int split_rule(int M, int N, int K, int act) {
     const int t128 = cdiv(M, 128) * cdiv(N, 128), nk = K / 32;
@@ -671,38 +658,32 @@ static int split_rule(int M, int N, int K, int act) {
     return s < 1 ? 1 : s;
 }
 
-static int heuristic_cfg(int M, int N, int K, int ldc, int ldr, bool has_resid, int act, const ConvP& cp) {
-    if (cfg_ok(1, M, N, K, ldc, ldr, has_resid, act, cp)) return (N % 128 == 0 || N > 192) ? 1 : 3;
-    return (N % 128 == 0 || N > 512) ? 9 : 10;
-}
+static int dma_tile(int N) { return (N % 128 == 0 || N > 192) ? DMA_128x128 : DMA_128x64; }
+static int heuristic_cfg(const GemmCall& c) { return vec_ok(c) ? dma_tile(c.N) : (c.N % 128 == 0 || c.N > 512) ? REG_128x128 : REG_128x64; }
 
 static int g_near_on = -1;      // un-tabled shapes take their nearest-M twin's tile (TCL_GEMM_NEAR, re-read by tcl_gemm_autotune / tcl_gemm_tune_load)
 static void read_near_env() { const char* e = getenv("TCL_GEMM_NEAR"); g_near_on = !(e && atoi(e) == 0); }
 
-static int dispatch(const _Float16* A, const _Float16* W, const _Float16* bias, const _Float16* resid, _Float16* C, int M, int N, int K,
-                    int lda, int ldw, int ldc, int ldr, int act, const ConvP& cp, hipStream_t st, TclProfScope* ps = nullptr) {
-    if (act == 2 && (N % 64 != 0 || (ldc & 7) || resid)) return TCL_EINVAL;      // GEGLU epilogue: 64-column [value | gate] groups
+// Which tile and how many K splits a call gets: host arithmetic and cache lookups only, so that the choice can be asked for without a GPU
+// (tcl_gemm_plan).  overlaps: the output overlaps an input.
+struct Plan { int cfg, splits; };      // cfg 0: the tuner has to time the shape first; cfg < 0: the call is refused (TCL_EINVAL)
+static Plan choose(const GemmCall& c, bool overlaps) {
+    if (c.act == 2 && (c.N % 64 != 0 || (c.ldc & 7) || c.resid)) return {-1, 0};      // GEGLU epilogue: 64-column [value | gate] groups
     if (g_tune_cfg) {
-        if (!cfg_ok(g_tune_cfg, M, N, K, ldc, ldr, resid != nullptr, act, cp)) return TCL_EINVAL;
-        return run_cfg(g_tune_cfg, g_tune_splits > 0 ? g_tune_splits : 1, A, W, bias, resid, C, M, N, K, lda, ldw, ldc, ldr, act, cp, st);
+        const TileCfg* t = tile(g_tune_cfg);
+        if (!t || !t->ok(c)) return {-1, 0};
+        // a forced strip tile with an in-place residual it would add twice takes the tiled kernel (the other paths never pair the two: in place = overlap)
+        return {t->id == STRIP && lin_strip_revisits_resid(c) ? dma_tile(c.N) : t->id, g_tune_splits > 0 ? g_tune_splits : 1};
     }
-    const bool hasr = resid != nullptr;
-    const int splits = split_rule(M, N, K, act);
-    const int fallback = heuristic_cfg(M, N, K, ldc, ldr, hasr, act, cp);
-    if (fallback >= 9) return run_cfg(fallback, 1, A, W, bias, resid, C, M, N, K, lda, ldw, ldc, ldr, act, cp, st);   // odd N / ld: register-staged kernel
+    const int splits = split_rule(c.M, c.N, c.K, c.act);
+    const int fallback = heuristic_cfg(c);
+    if (!vec_ok(c)) return {fallback, 1};      // odd N / ld: register-staged kernel
     // re-running the call must be idempotent: no tuning when the output overlaps an input
-    const char* c0 = (const char*)C; const char* c1 = c0 + ((size_t)(M - 1) * ldc + N) * 2;
-    auto overlaps = [&](const void* p, size_t bytes) { return p && (const char*)p < c1 && (const char*)p + bytes > c0; };
-    const size_t a_bytes = cp.conv ? (size_t)(M / (cp.Hout * cp.Wout)) * cp.Hin * cp.Win * cp.Cin * 2 : ((size_t)(M - 1) * lda + K) * 2;
-    if (!g_autotune || overlaps(A, a_bytes) || (resid && overlaps(resid, ((size_t)(M - 1) * ldr + N) * 2)))
-        return run_cfg(fallback, splits, A, W, bias, resid, C, M, N, K, lda, ldw, ldc, ldr, act, cp, st);
-    const TuneKey key = {cp.conv, M, N, K, act, (int)hasr, cp.Hin, cp.Win, cp.Cin, cp.stride, cp.Hup};
+    if (!g_autotune || overlaps) return {fallback, splits};
+    const TuneKey key = tune_key(c);
     auto it = g_tune_cache.find(key);
-    if (it != g_tune_cache.end()) {
-        // the key leaves the leading dimensions out: a cached (or file-loaded) tile is re-validated for this call's ldc / ldr
-        const int c = (cfg_ok(it->second, M, N, K, ldc, ldr, hasr, act, cp) && tile_ok(it->second, M, N, K, splits)) ? it->second : fallback;
-        return run_cfg(c, splits, A, W, bias, resid, C, M, N, K, lda, ldw, ldc, ldr, act, cp, st);
-    }
+    // the key leaves the leading dimensions out: a cached (or file-loaded) tile is re-validated for this call's ldc / ldr
+    if (it != g_tune_cache.end()) return {usable(it->second, c, splits) ? it->second : fallback, splits};
     // A shape the table does not hold, but whose twin with another row count it does (the same layer in a pass over another number of frames: a
     // group cut at a chunk boundary, the last window of a clip), takes the twin's tile when the row counts are within 2.5x of each other: the best
     // tile moves little with M at these sizes, timing costs a host sync and ~40 launches, and every tile yields the same bits.  The guess lives in
@@ -712,57 +693,101 @@ static int dispatch(const _Float16* A, const _Float16* W, const _Float16* bias, 
     if (g_near_on < 0) read_near_env();
     if (g_near_on) {
         auto nt = g_near_cache.find(key);
-        int c = nt != g_near_cache.end() ? nt->second : -1;
-        if (c < 0) {
+        int twin = nt != g_near_cache.end() ? nt->second : -1;
+        if (twin < 0) {
             double bd = 1e30;
-            c = 0;
+            twin = 0;
             for (const auto& kv : g_tune_cache) {
                 TuneKey k = kv.first;
                 const int m = k.M;
-                k.M = M;
+                k.M = c.M;
                 if (!(k == key)) continue;
-                const double dd = fabs(log((double)m / (double)M));
-                if (dd < bd) { bd = dd; c = kv.second; }
+                const double dd = fabs(log((double)m / (double)c.M));
+                if (dd < bd) { bd = dd; twin = kv.second; }
             }
-            if (bd > log(2.5)) c = 0;
-            g_near_cache[key] = c;
+            if (bd > log(2.5)) twin = 0;
+            g_near_cache[key] = twin;
         }
-        if (c > 0 && cfg_ok(c, M, N, K, ldc, ldr, hasr, act, cp) && tile_ok(c, M, N, K, splits))
-            return run_cfg(c, splits, A, W, bias, resid, C, M, N, K, lda, ldw, ldc, ldr, act, cp, st);
+        if (twin > 0 && usable(twin, c, splits)) return {twin, splits};
     }
-    if (g_autotune == 2)      // table-only mode: shapes the loaded table does not know take the static heuristic (no timing, no host sync)
-        return run_cfg(fallback, splits, A, W, bias, resid, C, M, N, K, lda, ldw, ldc, ldr, act, cp, st);
-    // candidates: LDS-DMA tiles always; the 8-wave kernels when there is no K split and enough tiles to occupy the CUs (tile_ok)
+    // table-only mode: shapes the loaded table does not know take the static heuristic (no timing, no host sync)
+    return {g_autotune == 2 ? fallback : 0, splits};
+}
+
+// The timed tuner: every tile worth trying at this size (the LDS-DMA tiles always; the wide ones when there is no K split and enough tiles to occupy
+// the CUs) runs the call itself; the fastest goes into the cache.
+static int tune(const GemmCall& c, int splits, TclProfScope* ps) {
     if (ps) ps->cancel();         // a tuned call is not a launch: keep its ~40 timed runs and host syncs out of the roofline brackets
-    int cand[13], nc = 0;
-    static const int all_cfgs[13] = {1, 2, 3, 4, 11, 5, 6, 7, 8, 12, 13, 14, 15};
-    for (int c : all_cfgs)
-        if (tile_ok(c, M, N, K, splits)) cand[nc++] = c;
-    hipEvent_t e0, e1;
-    (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
+    constexpr int NT = sizeof g_tiles / sizeof *g_tiles;
+    const TileCfg* cand[NT]; int nc = 0;
+    for (const TileCfg& t : g_tiles)
+        if (t.timed && t.worth(c.M, c.N, c.K, splits)) cand[nc++] = &t;
+    hipEvent_t e0, e1; (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
     // two interleaved rounds, minimum per candidate: one disturbed measurement (clock ramp, a profiler attached) must not pick the tile
-    float t_ms[13]; bool ok[13];
+    float t_ms[NT]; bool ok[NT];
     for (int i = 0; i < nc; ++i) {
         t_ms[i] = 1e30f;
-        ok[i] = cfg_ok(cand[i], M, N, K, ldc, ldr, hasr, act, cp) &&
-                run_cfg(cand[i], splits, A, W, bias, resid, C, M, N, K, lda, ldw, ldc, ldr, act, cp, st) == TCL_OK;                 // warm-up
+        ok[i] = cand[i]->ok(c) && cand[i]->run(c, splits) == TCL_OK;                 // warm-up
     }
     for (int round = 0; round < 2; ++round)
         for (int i = 0; i < nc; ++i) {
             if (!ok[i]) continue;
-            (void)hipEventRecord(e0, st);
-            for (int r = 0; r < 3; ++r) run_cfg(cand[i], splits, A, W, bias, resid, C, M, N, K, lda, ldw, ldc, ldr, act, cp, st);
-            (void)hipEventRecord(e1, st);
+            (void)hipEventRecord(e0, c.st);
+            for (int r = 0; r < 3; ++r) cand[i]->run(c, splits);
+            (void)hipEventRecord(e1, c.st);
             (void)hipEventSynchronize(e1);
             float ms = 0.f;
             (void)hipEventElapsedTime(&ms, e0, e1);
             t_ms[i] = fminf(t_ms[i], ms);
         }
-    int best = fallback; float best_ms = 1e30f;
-    for (int i = 0; i < nc; ++i) if (ok[i] && t_ms[i] < best_ms) { best_ms = t_ms[i]; best = cand[i]; }
+    int best = heuristic_cfg(c); float best_ms = 1e30f;
+    for (int i = 0; i < nc; ++i) if (ok[i] && t_ms[i] < best_ms) { best_ms = t_ms[i]; best = cand[i]->id; }
     (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    g_tune_cache[key] = best;
+    g_tune_cache[tune_key(c)] = best;
     return hipPeekAtLastError() == hipSuccess ? TCL_OK : TCL_ELAUNCH;      // the timed runs already produced C
+}
+
+static bool output_overlaps_input(const GemmCall& c) {
+    const char* c0 = (const char*)c.C; const char* c1 = c0 + ((size_t)(c.M - 1) * c.ldc + c.N) * 2;
+    auto overlaps = [&](const void* p, size_t bytes) { return p && (const char*)p < c1 && (const char*)p + bytes > c0; };
+    return overlaps(c.A, c.a_bytes()) || (c.resid && overlaps(c.resid, ((size_t)(c.M - 1) * c.ldr + c.N) * 2));
+}
+
+static int dispatch(const GemmCall& c, TclProfScope* ps = nullptr) {
+    const Plan p = choose(c, output_overlaps_input(c));
+    if (p.cfg < 0) return TCL_EINVAL;
+    return p.cfg ? tile(p.cfg)->run(c, p.splits) : tune(c, p.splits, ps);
+}
+
+static bool dense_args_ok(int M, int N, int K, int lda, int ldw, int act) {
+    return M > 0 && N > 0 && K > 0 && K % BK == 0 && lda % 8 == 0 && lda >= K && ldw % 8 == 0 && ldw >= K && act >= 0 && act <= 5;
+}
+// a 3x3 convolution as an implicit GEMM: fills c.cp and the GEMM's M N K and leading dimensions; false = unsupported arguments
+static bool conv_problem(GemmCall& c, int B, int Hin, int Win, int Cin, int Cout, int stride, int pad, int Hup, int Wup) {
+    if (!(B > 0 && Cin % BK == 0 && Cout > 0 && (stride == 1 || stride == 2) && (pad == 0 || pad == 1))) return false;
+    ConvP& cp = c.cp;
+    cp.conv = 1; cp.Hin = Hin; cp.Win = Win; cp.Cin = Cin;
+    cp.Hup = Hup > 0 ? Hup : Hin; cp.Wup = Wup > 0 ? Wup : Win;
+    cp.stride = stride; cp.pad = pad;
+    // pad=1: k3 s1|s2 p1 (UNet);  pad=0 & stride 2: the VAE encoder's asymmetric (0,1,0,1) padding
+    cp.Hout = pad ? (cp.Hup + 2 - 3) / stride + 1 : (cp.Hup + 1 - 3) / stride + 1;
+    cp.Wout = pad ? (cp.Wup + 2 - 3) / stride + 1 : (cp.Wup + 1 - 3) / stride + 1;
+    cp.sy = (float)Hin / (float)cp.Hup; cp.sx = (float)Win / (float)cp.Wup;
+    c.M = B * cp.Hout * cp.Wout; c.N = Cout; c.K = 9 * Cin;
+    c.lda = 0; c.ldw = 9 * Cin; c.ldc = c.ldr = Cout;
+    return c.M > 0;
+}
+
+// tcl_gemm_plan / tcl_conv3x3_plan: the answer of the very choose() that dispatch calls, for a call described by its scalars alone.  The operand
+// pointers are stand-ins that say only whether there is a residual and whether it is the output; nothing is dereferenced or launched.
+static int plan(GemmCall& c, int resid, int* cfg, int* splits) {
+    TCL_CHECK_ARG(cfg && splits && resid >= 0 && resid <= 2);
+    static _Float16 out, other;
+    c.C = &out; c.resid = resid == 2 ? &out : (resid == 1 ? &other : nullptr);
+    const Plan p = choose(c, resid == 2);
+    TCL_CHECK_ARG(p.cfg >= 0);
+    *cfg = p.cfg; *splits = p.splits;
+    return TCL_OK;
 }
 
 extern "C" {
@@ -797,7 +822,7 @@ int tcl_gemm_tune_load(const char* path) {
         if (line[0] == '#') continue;
         if (!versioned) { fclose(f); return TCL_EINVAL; }          // a table of another kernel generation / architecture: measured with other tiles
         if (sscanf(line, "%d %d %d %d %d %d %d %d %d %d %d %d", &k.conv, &k.M, &k.N, &k.K, &k.act, &k.hasr, &k.Hin, &k.Win, &k.Cin, &k.stride, &k.Hup, &cfg) != 12) continue;
-        if (!((cfg >= 1 && cfg <= 8) || (cfg >= 11 && cfg <= 15))) continue;         // only ids the cached path may run
+        if (!tile(cfg) || !tile(cfg)->tabled) continue;         // only ids the cached path may run
         g_tune_cache[k] = cfg;
     }
     fclose(f);
@@ -809,28 +834,29 @@ size_t tcl_gemm_tune_size(void) { return g_tune_cache.size(); }
 
 int tcl_gemm_f16(const void* A, const void* W, const void* bias, const void* resid, void* C, int M, int N, int K, int lda, int ldw,
                  int ldc, int ldr, int act, hipStream_t st) {
-    TCL_CHECK_ARG(A && W && C && M > 0 && N > 0 && K > 0 && K % BK == 0 && lda % 8 == 0 && lda >= K && ldw % 8 == 0 && ldw >= K && act >= 0 && act <= 5);
-    ConvP cp = {};
+    TCL_CHECK_ARG(A && W && C && dense_args_ok(M, N, K, lda, ldw, act));
+    const GemmCall c = {(const _Float16*)A, (const _Float16*)W, (const _Float16*)bias, (const _Float16*)resid, (_Float16*)C, M, N, K, lda, ldw, ldc, ldr, act, ConvP{}, st};
     TclProfScope ps(TCL_PROF_GEMM, st, 2.0 * M * N * K);
-    return dispatch((const _Float16*)A, (const _Float16*)W, (const _Float16*)bias, (const _Float16*)resid, (_Float16*)C, M, N, K, lda,
-                    ldw, ldc, ldr, act, cp, st, &ps);
+    return dispatch(c, &ps);
 }
 
 int tcl_conv3x3_f16(const void* X, const void* W, const void* bias, const void* resid, void* Y, int B, int Hin, int Win, int Cin,
                     int Cout, int stride, int pad, int Hup, int Wup, int act, hipStream_t st) {
-    TCL_CHECK_ARG(X && W && Y && B > 0 && Cin % BK == 0 && Cout > 0 && (stride == 1 || stride == 2) && (pad == 0 || pad == 1));
-    ConvP cp;
-    cp.conv = 1; cp.Hin = Hin; cp.Win = Win; cp.Cin = Cin;
-    cp.Hup = Hup > 0 ? Hup : Hin; cp.Wup = Wup > 0 ? Wup : Win;
-    cp.stride = stride; cp.pad = pad;
-    // pad=1: k3 s1|s2 p1 (UNet);  pad=0 & stride 2: the VAE encoder's asymmetric (0,1,0,1) padding
-    cp.Hout = pad ? (cp.Hup + 2 - 3) / stride + 1 : (cp.Hup + 1 - 3) / stride + 1;
-    cp.Wout = pad ? (cp.Wup + 2 - 3) / stride + 1 : (cp.Wup + 1 - 3) / stride + 1;
-    cp.sy = (float)Hin / (float)cp.Hup; cp.sx = (float)Win / (float)cp.Wup;
-    const int M = B * cp.Hout * cp.Wout;
-    TclProfScope ps(TCL_PROF_GEMM, st, 2.0 * M * Cout * 9.0 * Cin);
-    return dispatch((const _Float16*)X, (const _Float16*)W, (const _Float16*)bias, (const _Float16*)resid, (_Float16*)Y, M, Cout,
-                    9 * Cin, 0, 9 * Cin, Cout, Cout, act, cp, st, &ps);
+    GemmCall c = {(const _Float16*)X, (const _Float16*)W, (const _Float16*)bias, (const _Float16*)resid, (_Float16*)Y, 0, 0, 0, 0, 0, 0, 0, act, ConvP{}, st};
+    TCL_CHECK_ARG(X && W && Y && conv_problem(c, B, Hin, Win, Cin, Cout, stride, pad, Hup, Wup));
+    TclProfScope ps(TCL_PROF_GEMM, st, 2.0 * c.M * Cout * 9.0 * Cin);
+    return dispatch(c, &ps);
+}
+
+int tcl_gemm_plan(int M, int N, int K, int lda, int ldw, int ldc, int ldr, int act, int resid, int* cfg, int* splits) {
+    TCL_CHECK_ARG(dense_args_ok(M, N, K, lda, ldw, act));
+    GemmCall c = {nullptr, nullptr, nullptr, nullptr, nullptr, M, N, K, lda, ldw, ldc, ldr, act, ConvP{}, nullptr};
+    return plan(c, resid, cfg, splits);
+}
+int tcl_conv3x3_plan(int B, int Hin, int Win, int Cin, int Cout, int stride, int pad, int Hup, int Wup, int act, int resid, int* cfg, int* splits) {
+    GemmCall c = {nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0, 0, 0, 0, act, ConvP{}, nullptr};
+    TCL_CHECK_ARG(conv_problem(c, B, Hin, Win, Cin, Cout, stride, pad, Hup, Wup));
+    return plan(c, resid, cfg, splits);
 }
 
 }  // extern "C"

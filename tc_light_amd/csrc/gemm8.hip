@@ -528,10 +528,10 @@ static int gemm8_sched() {
 }
 
 template <int MT, int NT, int WM, int WN>
-static int launch8(const _Float16* A, const _Float16* W, const _Float16* bias, const _Float16* resid, _Float16* C, int M, int N, int K, int lda,
-                   int ldw, int ldc, int ldr, int act, const ConvP& cp, hipStream_t st) {
+static int launch8(const GemmCall& c) {
     constexpr int BM = WM * MT * 32, BN = WN * NT * 32;
-    const int tm = cdiv(M, BM), tn = cdiv(N, BN);
+    const ConvP& cp = c.cp;
+    const int tm = cdiv(c.M, BM), tn = cdiv(c.N, BN);
     const size_t ring = (size_t)4 * (BM + BN) * 64 + 1024, epi = (size_t)8 * 32 * (NT * 32 + 8) * 2, lds = ring > epi ? ring : epi;
     static bool attr_set = false;
     if (!attr_set) {
@@ -544,27 +544,20 @@ static int launch8(const _Float16* A, const _Float16* W, const _Float16* bias, c
     const dim3 grid(cdiv(tm, 8) * 8 * tn);
     int sched = gemm8_sched();
     // k_gemm8p addresses its operands with 32-bit offsets and has no nearest-upsample gather: those calls take k_gemm8s
-    const size_t a_bytes = cp.conv ? (size_t)(M / (cp.Hout * cp.Wout)) * cp.Hin * cp.Win * cp.Cin * 2 : ((size_t)(M - 1) * lda + K) * 2;
-    const size_t w_bytes = ((size_t)(N - 1) * ldw + K) * 2;
+    const size_t a_bytes = c.a_bytes(), w_bytes = c.w_bytes();
     if (sched == 2 && (a_bytes >= 0xffffff00ull || w_bytes >= 0xffffff00ull || (cp.conv && (cp.Hup != cp.Hin || cp.Wup != cp.Win)))) sched = 1;
-#define G8_LAUNCH(KERN, ...) hipLaunchKernelGGL((KERN), grid, dim3(512), lds, st, A, W, bias, resid, C, M, N, K, lda, ldw, ldc, ldr, act, cp, tm, tn, ##__VA_ARGS__)
+#define G8_LAUNCH(KERN, ...) hipLaunchKernelGGL((KERN), grid, dim3(512), lds, c.st, c.A, c.W, c.bias, c.resid, c.C, c.M, c.N, c.K, c.lda, c.ldw, c.ldc, c.ldr, c.act, cp, tm, tn, ##__VA_ARGS__)
     if (sched == 2) { if (cp.conv) G8_LAUNCH((k_gemm8p<MT, NT, WM, WN, true>), (unsigned)a_bytes, (unsigned)w_bytes); else G8_LAUNCH((k_gemm8p<MT, NT, WM, WN, false>), (unsigned)a_bytes, (unsigned)w_bytes); }
     else { if (cp.conv) G8_LAUNCH((k_gemm8s<MT, NT, WM, WN, true>)); else G8_LAUNCH((k_gemm8s<MT, NT, WM, WN, false>)); }
 #undef G8_LAUNCH
     return hipPeekAtLastError() == hipSuccess ? TCL_OK : TCL_ELAUNCH;
 }
 
-// cfg: 1 = 256x320 (N % 320 == 0), 2 = 128x320, 3 = 256x256 (N % 256 == 0), 4 = 128x256.  Preconditions (checked by the caller):
+// One entry per tile (256x320 and 128x320: N % 320 == 0; 256x256 and 128x256: N % 256 == 0).  Preconditions (checked by the caller):
 // K % 64 == 0 (pairs of K steps share 128-B lines; conv: Cin % 64 == 0), N % 8 == 0, ldc % 8 == 0, (ldr % 8 == 0), act in {0, 1};
-// act 2 (GEGLU, 64-column [value | gate] groups) on cfg 3 / 4 only.
-int gemm8_dispatch(int cfg, const _Float16* A, const _Float16* W, const _Float16* bias, const _Float16* resid, _Float16* C, int M, int N, int K,
-                   int lda, int ldw, int ldc, int ldr, int act, const ConvP& cp, hipStream_t st) {
-    switch (cfg) {
-        case 1: return launch8<2, 5, 4, 2>(A, W, bias, resid, C, M, N, K, lda, ldw, ldc, ldr, act, cp, st);
-        case 2: return launch8<1, 5, 4, 2>(A, W, bias, resid, C, M, N, K, lda, ldw, ldc, ldr, act, cp, st);
-        case 3: return launch8<4, 2, 2, 4>(A, W, bias, resid, C, M, N, K, lda, ldw, ldc, ldr, act, cp, st);
-        case 4: return launch8<2, 2, 2, 4>(A, W, bias, resid, C, M, N, K, lda, ldw, ldc, ldr, act, cp, st);
-    }
-    return TCL_EINVAL;
-}
+// act 2 (GEGLU, 64-column [value | gate] groups) on the 256-column tiles only.
+int gemm8_256x320(const GemmCall& c) { return launch8<2, 5, 4, 2>(c); }
+int gemm8_128x320(const GemmCall& c) { return launch8<1, 5, 4, 2>(c); }
+int gemm8_256x256(const GemmCall& c) { return launch8<4, 2, 2, 4>(c); }
+int gemm8_128x256(const GemmCall& c) { return launch8<2, 2, 2, 4>(c); }
 #endif

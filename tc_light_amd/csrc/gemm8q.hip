@@ -373,10 +373,11 @@ __global__ __launch_bounds__(512) void k_gemm8q(const _Float16* __restrict__ A, 
 }
 
 template <int WM, int WN, int RI, int CJ>
-static int launch8q(const _Float16* A, const _Float16* W, const _Float16* bias, const _Float16* resid, _Float16* C, int M, int N, int K, int lda,
-                    int ldw, int ldc, int ldr, int act, const ConvP& cp, hipStream_t st) {
+static int launch8q(const GemmCall& c) {
     constexpr int QN = CJ * 16, BN = 2 * WN * QN, B_HALF = WN * QN * 128, BM = 2 * WM * RI * 16, A_HALF = WM * RI * 16 * 128;
-    const int tm = cdiv(M, BM), tn = N / BN;
+    if (!gemm8q_ok(BN, c)) return TCL_EINVAL;
+    const ConvP& cp = c.cp;
+    const int tm = cdiv(c.M, BM), tn = c.N / BN;
     const size_t lds = (size_t)2 * (2 * A_HALF + 2 * B_HALF) + (B_HALF % 8192 ? 4096 : 0);
     static bool attr_set = false;
     if (!attr_set) {
@@ -385,23 +386,23 @@ static int launch8q(const _Float16* A, const _Float16* W, const _Float16* bias, 
         (void)hipFuncSetAttribute((const void*)k_gemm8q<WM, WN, RI, CJ, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         attr_set = true;
     }
-    const size_t a_bytes = cp.conv ? (size_t)(M / (cp.Hout * cp.Wout)) * cp.Hin * cp.Win * cp.Cin * 2 : ((size_t)(M - 1) * lda + K) * 2;
-    const size_t w_bytes = ((size_t)(N - 1) * ldw + K) * 2;
-    if (cp.conv && (cp.Hup != cp.Hin || cp.Wup != cp.Win)) hipLaunchKernelGGL((k_gemm8q<WM, WN, RI, CJ, true, true>), dim3(tm * tn), dim3(512), lds, st, A, W, bias, resid, C, M, N, K, lda, ldw, ldc, ldr, act, cp, tm, tn, (unsigned long)a_bytes, (unsigned)w_bytes);
-    else if (cp.conv) hipLaunchKernelGGL((k_gemm8q<WM, WN, RI, CJ, true>), dim3(tm * tn), dim3(512), lds, st, A, W, bias, resid, C, M, N, K, lda, ldw, ldc, ldr, act, cp, tm, tn, (unsigned long)a_bytes, (unsigned)w_bytes);
-    else hipLaunchKernelGGL((k_gemm8q<WM, WN, RI, CJ, false>), dim3(tm * tn), dim3(512), lds, st, A, W, bias, resid, C, M, N, K, lda, ldw, ldc, ldr, act, cp, tm, tn, (unsigned long)a_bytes, (unsigned)w_bytes);
+#define G8Q_LAUNCH(...) hipLaunchKernelGGL((k_gemm8q<WM, WN, RI, CJ, __VA_ARGS__>), dim3(tm * tn), dim3(512), lds, c.st, c.A, c.W, c.bias, c.resid, c.C, c.M, c.N, c.K, c.lda, c.ldw, c.ldc, c.ldr, c.act, cp, tm, tn, (unsigned long)c.a_bytes(), (unsigned)c.w_bytes())
+    if (cp.conv && (cp.Hup != cp.Hin || cp.Wup != cp.Win)) G8Q_LAUNCH(true, true);
+    else if (cp.conv) G8Q_LAUNCH(true);
+    else G8Q_LAUNCH(false);
+#undef G8Q_LAUNCH
     return hipPeekAtLastError() == hipSuccess ? TCL_OK : TCL_ELAUNCH;
 }
 
-// Can the 8-phase kernel take this call?  cfg 1 = 256 x 256 (N % 256 == 0; GEGLU allowed), 2 = 256 x 320 (N % 320 == 0), 3 = 512 x 128 (N % 128 == 0:
+// Can the 8-phase kernel take this call?  Tile width BN = 256 (256 x 256, N % 256 == 0; GEGLU allowed), 320 (256 x 320, N % 320 == 0), 128 (512 x 128, N % 128 == 0:
 // the VAE's 128-channel convolutions at full resolution; WM 8, WN 1, quadrant 32 x 64, all 160 KiB of LDS).  K % 64 == 0 (conv:
 // Cin % 64 == 0), the weights and one tile's rows of A addressable with 32 bits (A as a whole may be larger), nearest up-sampling only by a factor <= 2 per axis (stride 1, pad 1), 16-B aligned rows.
-bool gemm8q_ok(int cfg, int M, int N, int K, int lda, int ldw, int ldc, int ldr, bool has_resid, int act, const ConvP& cp) {
-    const int BN = cfg == 1 ? 256 : (cfg == 2 ? 320 : 128);
-    if (N % BN || K % 64 || K < 64 || M < 1) return false;
-    if ((ldw & 7) || (ldc & 7) || (has_resid && (ldr & 7))) return false;
-    if (act == 2 && (cfg != 1 || has_resid)) return false;
-    if (act < 0 || act > 5) return false;
+bool gemm8q_ok(int BN, const GemmCall& c) {
+    const ConvP& cp = c.cp;
+    if (c.N % BN || c.K % 64 || c.K < 64 || c.M < 1) return false;
+    if ((c.ldw & 7) || (c.ldc & 7) || (c.has_resid() && (c.ldr & 7))) return false;
+    if (c.act == 2 && (BN != 256 || c.has_resid())) return false;
+    if (c.act < 0 || c.act > 5) return false;
     if (cp.conv) {
         if (cp.Cin % 64) return false;
         if (cp.Hup != cp.Hin || cp.Wup != cp.Win) {      // nearest up-sampling in the gather: stride 1, pad 1, scale in (0.5, 1] per axis (source-row deltas 0..2)
@@ -409,15 +410,11 @@ bool gemm8q_ok(int cfg, int M, int N, int K, int lda, int ldw, int ldc, int ldr,
         }
         if ((size_t)4 * cp.Hin * cp.Win * cp.Cin * 2 >= 0xffffff00ull) return false;      // a tile's rows touch <= 3 consecutive images (addressed relative to the first)
     } else {
-        if ((lda & 7) || (size_t)256 * 2 * lda * 2 >= 0xffffff00ull) return false;
+        if ((c.lda & 7) || (size_t)256 * 2 * c.lda * 2 >= 0xffffff00ull) return false;
     }
-    return ((size_t)(N - 1) * ldw + K) * 2 < 0xffffff00ull;
+    return c.w_bytes() < 0xffffff00ull;
 }
 
-int gemm8q_dispatch(int cfg, const _Float16* A, const _Float16* W, const _Float16* bias, const _Float16* resid, _Float16* C, int M, int N, int K,
-                    int lda, int ldw, int ldc, int ldr, int act, const ConvP& cp, hipStream_t st) {
-    if (!gemm8q_ok(cfg, M, N, K, lda, ldw, ldc, ldr, resid != nullptr, act, cp)) return TCL_EINVAL;
-    if (cfg == 1) return launch8q<2, 4, 4, 2>(A, W, bias, resid, C, M, N, K, lda, ldw, ldc, ldr, act, cp, st);
-    if (cfg == 3) return launch8q<8, 1, 2, 4>(A, W, bias, resid, C, M, N, K, lda, ldw, ldc, ldr, act, cp, st);
-    return launch8q<4, 2, 2, 5>(A, W, bias, resid, C, M, N, K, lda, ldw, ldc, ldr, act, cp, st);
-}
+int gemm8q_256x256(const GemmCall& c) { return launch8q<2, 4, 4, 2>(c); }
+int gemm8q_512x128(const GemmCall& c) { return launch8q<8, 1, 2, 4>(c); }
+int gemm8q_256x320(const GemmCall& c) { return launch8q<4, 2, 2, 5>(c); }

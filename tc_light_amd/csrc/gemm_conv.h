@@ -53,14 +53,25 @@ __device__ __forceinline__ float apply_act(float v, int act) {
 
 __device__ __forceinline__ float post_act(float v, int act) { return act == 5 ? gelu_erf(v) : v; }
 
-int gemm8_dispatch(int cfg, const _Float16* A, const _Float16* W, const _Float16* bias, const _Float16* resid, _Float16* C, int M, int N, int K,
-                   int lda, int ldw, int ldc, int ldr, int act, const ConvP& cp, hipStream_t st);
-// 8-phase 256-row kernels (gemm8q.hip): cfg 1 = 256 x 256, 2 = 256 x 320
-bool gemm8q_ok(int cfg, int M, int N, int K, int lda, int ldw, int ldc, int ldr, bool has_resid, int act, const ConvP& cp);
-int gemm8q_dispatch(int cfg, const _Float16* A, const _Float16* W, const _Float16* bias, const _Float16* resid, _Float16* C, int M, int N, int K,
-                    int lda, int ldw, int ldc, int ldr, int act, const ConvP& cp, hipStream_t st);
-// strip-resident K = 320 Linear (linstrip.hip), cfg 12
-bool lin_strip_ok(int M, int N, int K, int lda, int ldw, int ldc, int ldr, bool has_resid, int act, const ConvP& cp);
-int lin_strip_dispatch(const _Float16* A, const _Float16* W, const _Float16* bias, const _Float16* resid, _Float16* C, int M, int N, int K,
-                       int lda, int ldw, int ldc, int ldr, int act, hipStream_t st, const _Float16* gamma = nullptr, const _Float16* beta = nullptr,
-                       float eps = 0.f);
+// One GEMM / implicit-convolution call as every host function of the dispatch sees it: the operands, the problem, the epilogue and the stream.
+// The C-ABI entries build it once; launchers read the kernel arguments from it one by one.
+struct GemmCall {
+    const _Float16 *A, *W, *bias, *resid; _Float16* C;
+    int M, N, K, lda, ldw, ldc, ldr, act;
+    ConvP cp;
+    hipStream_t st;
+    bool has_resid() const { return resid != nullptr; }
+    // extents of A (dense, or the stored NHWC input of a convolution) and of W in bytes: what 32-bit offsets have to reach
+    size_t a_bytes() const { return cp.conv ? (size_t)(M / (cp.Hout * cp.Wout)) * cp.Hin * cp.Win * cp.Cin * 2 : ((size_t)(M - 1) * lda + K) * 2; }
+    size_t w_bytes() const { return ((size_t)(N - 1) * ldw + K) * 2; }
+};
+
+// 8-wave ping-pong kernels (gemm8.hip), by tile
+int gemm8_256x320(const GemmCall& c), gemm8_128x320(const GemmCall& c), gemm8_256x256(const GemmCall& c), gemm8_128x256(const GemmCall& c);
+// 8-phase 256-row kernels (gemm8q.hip), by tile; gemm8q_ok: can the tile of width BN (256, 320; 128 = the 512-row tile) take this call?
+bool gemm8q_ok(int BN, const GemmCall& c);
+int gemm8q_256x256(const GemmCall& c), gemm8q_256x320(const GemmCall& c), gemm8q_512x128(const GemmCall& c);
+// strip-resident K = 320 Linear (linstrip.hip); revisits_resid: an in-place residual on a call whose last weight tile is moved back -- not for this
+// kernel; gamma / beta: LayerNorm folded into the A load
+bool lin_strip_ok(const GemmCall& c), lin_strip_revisits_resid(const GemmCall& c);
+int lin_strip_dispatch(const GemmCall& c, const _Float16* gamma = nullptr, const _Float16* beta = nullptr, float eps = 0.f);

@@ -236,23 +236,19 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void k_lin_strip(const _F
 }
 
 
-int lin_strip_dispatch_q(const _Float16* A, const _Float16* W, const _Float16* bias, const _Float16* resid, _Float16* C, int M, int N, int K,
-                         int lda, int ldw, int ldc, int ldr, int act, hipStream_t st, const _Float16* gamma, const _Float16* beta, float eps, QPanel qp);
-// cfg 12 of csrc/gemm.hip.  Valid for dense A, K == 320, N >= 128 and N % 32 == 0 (GEGLU: N % 64 == 0), 16-B aligned rows.
-bool lin_strip_ok(int M, int N, int K, int lda, int ldw, int ldc, int ldr, bool has_resid, int act, const ConvP& cp) {
-    return !cp.conv && K == 320 && N >= 128 && N % (act == 2 ? 64 : 32) == 0 && N <= 8192 && (lda & 7) == 0 && (ldw & 7) == 0 && (ldc & 7) == 0 &&
-           (!has_resid || (ldr & 7) == 0) && (long)ldw * 2 * 8 < (1l << 30);
+// The strip-resident tile of csrc/gemm.hip's table.  Valid for dense A, K == 320, N >= 128 and N % 32 == 0 (GEGLU: N % 64 == 0), 16-B aligned rows.
+bool lin_strip_ok(const GemmCall& c) {
+    return !c.cp.conv && c.K == 320 && c.N >= 128 && c.N % (c.act == 2 ? 64 : 32) == 0 && c.N <= 8192 && (c.lda & 7) == 0 && (c.ldw & 7) == 0 &&
+           (c.ldc & 7) == 0 && (!c.has_resid() || (c.ldr & 7) == 0) && (long)c.ldw * 2 * 8 < (1l << 30);
 }
+// The last weight tile is moved back when N % 128 != 0 and re-reads the residual of the overlapped columns: with an in-place residual (resid == C)
+// those columns would get it twice.
+bool lin_strip_revisits_resid(const GemmCall& c) { return c.resid == c.C && c.N % 128 != 0; }
 
-int lin_strip_dispatch(const _Float16* A, const _Float16* W, const _Float16* bias, const _Float16* resid, _Float16* C, int M, int N, int K,
-                       int lda, int ldw, int ldc, int ldr, int act, hipStream_t st, const _Float16* gamma, const _Float16* beta, float eps) {
-    return lin_strip_dispatch_q(A, W, bias, resid, C, M, N, K, lda, ldw, ldc, ldr, act, st, gamma, beta, eps, QPanel{nullptr, 1, 1, 1.f});
-}
-int lin_strip_dispatch_q(const _Float16* A, const _Float16* W, const _Float16* bias, const _Float16* resid, _Float16* C, int M, int N, int K,
-                         int lda, int ldw, int ldc, int ldr, int act, hipStream_t st, const _Float16* gamma, const _Float16* beta, float eps, QPanel qp) {
-    if (K != 320) return TCL_EINVAL;
+static int lin_strip_launch(const GemmCall& c, const _Float16* gamma, const _Float16* beta, float eps, QPanel qp) {
+    if (c.K != 320) return TCL_EINVAL;
     constexpr int NW = 4;
-    const int tn = cdiv(N, 128), strips = cdiv(M, 32 * NW);
+    const int tn = cdiv(c.N, 128), strips = cdiv(c.M, 32 * NW);
     // enough blocks for ~3 rounds of the 512 slots (2 per CU); a split re-reads the strip (from L2) and sweeps its share of the weight tiles
     static const int force_split = getenv("TCL_LS_SPLIT") ? atoi(getenv("TCL_LS_SPLIT")) : 0;      // lab hook
     int nsplit = 1;
@@ -265,9 +261,14 @@ int lin_strip_dispatch_q(const _Float16* A, const _Float16* W, const _Float16* b
         (void)hipFuncSetAttribute((const void*)k_lin_strip<320, NW, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 128 * 128 + 64 * 128 * 2);
         set = true;
     }
-    if (gamma) hipLaunchKernelGGL((k_lin_strip<320, NW, true>), dim3(strips * nsplit), dim3(64 * NW), lds, st, A, W, bias, resid, C, M, N, lda, ldw, ldc, ldr, act, tn, nsplit, gamma, beta, eps, qp);
-    else hipLaunchKernelGGL((k_lin_strip<320, NW, false>), dim3(strips * nsplit), dim3(64 * NW), lds, st, A, W, bias, resid, C, M, N, lda, ldw, ldc, ldr, act, tn, nsplit, gamma, beta, eps, qp);
+#define LS_LAUNCH(LN) hipLaunchKernelGGL((k_lin_strip<320, NW, LN>), dim3(strips * nsplit), dim3(64 * NW), lds, c.st, c.A, c.W, c.bias, c.resid, c.C, c.M, c.N, c.lda, c.ldw, c.ldc, c.ldr, c.act, tn, nsplit, gamma, beta, eps, qp)
+    if (gamma) LS_LAUNCH(true);
+    else LS_LAUNCH(false);
+#undef LS_LAUNCH
     return hipPeekAtLastError() == hipSuccess ? TCL_OK : TCL_ELAUNCH;
+}
+int lin_strip_dispatch(const GemmCall& c, const _Float16* gamma, const _Float16* beta, float eps) {
+    return lin_strip_launch(c, gamma, beta, eps, QPanel{nullptr, 1, 1, 1.f});
 }
 
 extern "C" {
@@ -275,22 +276,19 @@ extern "C" {
 int tcl_ln_gemm_f16(const void* x, const void* gamma, const void* beta, float eps, const void* W, const void* bias, const void* resid, void* C,
                     int M, int N, int K, int ldx, int ldw, int ldc, int ldr, int act, hipStream_t st) {
     TCL_CHECK_ARG(x && gamma && beta && W && C && M > 0 && act >= 0 && act <= 5 && (act != 2 || !resid));
-    ConvP cp = {};
-    TCL_CHECK_ARG(lin_strip_ok(M, N, K, ldx, ldw, ldc, ldr, resid != nullptr, act, cp) && ldx >= K && ldw >= K);
-    TCL_CHECK_ARG(!(resid == C && N % 128 != 0));      // no in-place residual when the last weight tile is moved back (its columns are visited twice)
+    const GemmCall c = {(const _Float16*)x, (const _Float16*)W, (const _Float16*)bias, (const _Float16*)resid, (_Float16*)C, M, N, K, ldx, ldw, ldc, ldr, act, ConvP{}, st};
+    TCL_CHECK_ARG(lin_strip_ok(c) && !lin_strip_revisits_resid(c) && ldx >= K && ldw >= K);
     TclProfScope ps(TCL_PROF_GEMM, st, 2.0 * M * N * K);
-    return lin_strip_dispatch((const _Float16*)x, (const _Float16*)W, (const _Float16*)bias, (const _Float16*)resid, (_Float16*)C, M, N, K, ldx, ldw, ldc,
-                              ldr, act, st, (const _Float16*)gamma, (const _Float16*)beta, eps);
+    return lin_strip_dispatch(c, (const _Float16*)gamma, (const _Float16*)beta, eps);
 }
 int tcl_ln_gemm_qpanel_f16(const void* x, const void* gamma, const void* beta, float eps, const void* W, int M, int H, int d, int Tq, int ldx, int ldw,
                            float scale, void* ws_q, hipStream_t st) {
     TCL_CHECK_ARG(x && gamma && beta && W && ws_q && M > 0 && H > 0 && d == 40 && Tq > 0 && M % Tq == 0);
     const int N = H * d, K = N;
-    ConvP cp = {};
-    TCL_CHECK_ARG(lin_strip_ok(M, N, K, ldx, ldw, N, N, false, 0, cp) && ldx >= K && ldw >= K);
+    const GemmCall c = {(const _Float16*)x, (const _Float16*)W, nullptr, nullptr, (_Float16*)ws_q, M, N, K, ldx, ldw, N, N, 0, ConvP{}, st};
+    TCL_CHECK_ARG(lin_strip_ok(c) && ldx >= K && ldw >= K);
     TclProfScope ps(TCL_PROF_GEMM, st, 2.0 * M * N * K);
     const QPanel qp = {(_Float16*)ws_q, Tq, (Tq + 255) / 256 * 256, scale * 1.4426950408889634f};
-    return lin_strip_dispatch_q((const _Float16*)x, (const _Float16*)W, nullptr, nullptr, (_Float16*)ws_q, M, N, K, ldx, ldw, N, N, 0, st,
-                                (const _Float16*)gamma, (const _Float16*)beta, eps, qp);
+    return lin_strip_launch(c, (const _Float16*)gamma, (const _Float16*)beta, eps, qp);
 }
 }

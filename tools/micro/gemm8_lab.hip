@@ -2,7 +2,7 @@
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -Wno-comment tools/micro/gemm8_lab.hip -o gpurun_out/gemm8_lab && gpurun_out/gemm8_lab
 // For every shape: each valid tile configuration x schedule (1 = k_gemm8s, DMA in the MFMA segment; 2 = k_gemm8p, half-step pipeline) is
 // (a) compared bit for bit with schedule 1 of the same tile, (b) checked on 8192 sampled outputs against an f32 reference kernel,
-// (c) timed in interleaved rounds (median and best of 5 x 4 launches).  Output: one line per (shape, cfg, schedule) with TFLOP/s.
+// (c) timed in interleaved rounds (median and best of 5 x 4 launches).  Output: one line per (shape, tile, schedule) with TFLOP/s.
 #ifdef LAB_PROF
 #define G8_PROF
 #endif
@@ -115,11 +115,13 @@ int main(int argc, char** argv) {
         CK(hipStreamSynchronize(st));
         const double flop = 2.0 * M * N * K;
         printf("== %s: M=%d N=%d K=%d  %.1f GFLOP\n", s.name, M, N, K, flop / 1e9);
-        std::vector<int> cfgs;
-        if (N % 320 == 0) { cfgs.push_back(1); cfgs.push_back(2); }
-        if (N % 256 == 0) { cfgs.push_back(3); cfgs.push_back(4); }
+        struct Tile { const char* name; int (*run)(const GemmCall&); };
+        std::vector<Tile> cfgs;
+        if (N % 320 == 0) { cfgs.push_back({"256x320", gemm8_256x320}); cfgs.push_back({"128x320", gemm8_128x320}); }
+        if (N % 256 == 0) { cfgs.push_back({"256x256", gemm8_256x256}); cfgs.push_back({"128x256", gemm8_128x256}); }
         const int lda = s.conv ? 0 : K;
-        for (int cfg : cfgs) {
+        auto call = [&](_Float16* C) { return GemmCall{A, Wt, nullptr, nullptr, C, M, N, K, lda, K, N, N, 0, cp, st}; };
+        for (const Tile& cfg : cfgs) {
             double med[3], best[3];
             std::vector<float> t[3];
             for (int sched = 1; sched < 3; ++sched) {
@@ -127,7 +129,7 @@ int main(int argc, char** argv) {
                 g_gemm8_sched = sched;
                 _Float16* C = sched == 1 ? C0 : C1;
                 CK(hipMemsetAsync(C, 0xff, (size_t)M * N * 2, st));
-                if (gemm8_dispatch(cfg, A, Wt, nullptr, nullptr, C, M, N, K, lda, K, N, N, 0, cp, st) != TCL_OK) { printf("launch failed cfg %d\n", cfg); exit(1); }
+                if (cfg.run(call(C)) != TCL_OK) { printf("launch failed %s\n", cfg.name); exit(1); }
                 CK(hipStreamSynchronize(st));
                 hipLaunchKernelGGL(k_ref, dim3(32), dim3(256), 0, st, A, Wt, C, M, N, K, cp, 8192, derr);
                 std::vector<float> herr(8192);
@@ -139,14 +141,14 @@ int main(int argc, char** argv) {
                     hipLaunchKernelGGL(k_diff, dim3(2048), dim3(256), 0, st, (const unsigned*)C0, (const unsigned*)C1, (size_t)M * N / 2, dcnt);
                     CK(hipMemcpyAsync(&nd, dcnt, 4, hipMemcpyDeviceToHost, st)); CK(hipStreamSynchronize(st));
                 }
-                if (mx > 2e-2f || nd) printf("   !!! cfg %d sched %d: max rel err vs f32 reference %.3e, words differing from sched 1: %u\n", cfg, sched, mx, nd);
+                if (mx > 2e-2f || nd) printf("   !!! %s sched %d: max rel err vs f32 reference %.3e, words differing from sched 1: %u\n", cfg.name, sched, mx, nd);
             }
             for (int round = 0; round < 5; ++round)
                 for (int sched = 1; sched < 3; ++sched) {
                     if (!((smask >> sched) & 1)) { t[sched].push_back(1e9f); continue; }
                     g_gemm8_sched = sched;
                     CK(hipEventRecord(e0, st));
-                    for (int r = 0; r < 4; ++r) gemm8_dispatch(cfg, A, Wt, nullptr, nullptr, C1, M, N, K, lda, K, N, N, 0, cp, st);
+                    for (int r = 0; r < 4; ++r) cfg.run(call(C1));
                     CK(hipEventRecord(e1, st)); CK(hipEventSynchronize(e1));
                     float ms; CK(hipEventElapsedTime(&ms, e0, e1));
                     t[sched].push_back(ms / 4);
@@ -157,26 +159,27 @@ int main(int argc, char** argv) {
                 g_gemm8_sched = sched;
                 unsigned long long* pb; CK(hipMalloc(&pb, 64 * 2 * 5 * 8)); CK(hipMemset(pb, 0, 64 * 2 * 5 * 8));
                 CK(hipMemcpyToSymbol(HIP_SYMBOL(g8_prof_buf), &pb, sizeof(pb)));
-                gemm8_dispatch(cfg, A, Wt, nullptr, nullptr, C1, M, N, K, lda, K, N, N, 0, cp, st); CK(hipStreamSynchronize(st));
+                cfg.run(call(C1)); CK(hipStreamSynchronize(st));
                 std::vector<unsigned long long> hp(640); CK(hipMemcpy(hp.data(), pb, 640 * 8, hipMemcpyDeviceToHost));
                 const int nk = K / 32;
                 for (int g = 0; g < 2; ++g) {
                     double sm[5] = {0, 0, 0, 0, 0};
                     for (int b = 0; b < 64; ++b) for (int i = 0; i < 5; ++i) sm[i] += (double)hp[(b * 2 + g) * 5 + i] / 64 / nk;
-                    printf("      prof cfg %d sched %d group %d: cycles per K step: barrier1 %.0f | L %.0f | barrier2 %.0f | M %.0f | vmcnt wait %.0f | sum %.0f\n", cfg, sched, g, sm[0], sm[1], sm[2], sm[3], sm[4], sm[0] + sm[1] + sm[2] + sm[3] + sm[4]);
+                    printf("      prof %s sched %d group %d: cycles per K step: barrier1 %.0f | L %.0f | barrier2 %.0f | M %.0f | vmcnt wait %.0f | sum %.0f\n", cfg.name, sched, g, sm[0], sm[1], sm[2], sm[3], sm[4], sm[0] + sm[1] + sm[2] + sm[3] + sm[4]);
                 }
                 pb = nullptr; CK(hipMemcpyToSymbol(HIP_SYMBOL(g8_prof_buf), &pb, sizeof(pb)));
             }
 #endif
-            printf("   cfg %d (%s):", cfg, cfg == 1 ? "256x320" : cfg == 2 ? "128x320" : cfg == 3 ? "256x256" : "128x256");
+            printf("   g8 %s:", cfg.name);
             for (int sched = 1; sched < 3; ++sched) if ((smask >> sched) & 1) printf("  s%d %8.1f us %6.0f TF (best %6.0f)", sched, med[sched] * 1e3, flop / med[sched] / 1e9, flop / best[sched] / 1e9);
             printf("\n");
         }
         // round 4: the 8-phase kernels (gemm8q.hip): bit comparison with the last schedule-1 result in C0, sampled f32 reference, same timing protocol
-        for (int qc = 1; qc <= 2; ++qc) {
-            if (cfgs.empty() || !gemm8q_ok(qc, M, N, K, lda ? lda : 8, K, N, N, false, 0, cp)) continue;
+        const struct { int BN; const char* name; int (*run)(const GemmCall&); } qtiles[2] = {{256, "256x256", gemm8q_256x256}, {320, "256x320", gemm8q_256x320}};
+        for (const auto& q : qtiles) {
+            if (cfgs.empty() || !gemm8q_ok(q.BN, call(C1))) continue;
             CK(hipMemsetAsync(C1, 0xff, (size_t)M * N * 2, st));
-            if (gemm8q_dispatch(qc, A, Wt, nullptr, nullptr, C1, M, N, K, lda, K, N, N, 0, cp, st) != TCL_OK) { printf("q launch failed %d\n", qc); exit(1); }
+            if (q.run(call(C1)) != TCL_OK) { printf("q8 launch failed %s\n", q.name); exit(1); }
             CK(hipStreamSynchronize(st));
             hipLaunchKernelGGL(k_ref, dim3(32), dim3(256), 0, st, A, Wt, C1, M, N, K, cp, 8192, derr);
             std::vector<float> herr(8192);
@@ -186,17 +189,17 @@ int main(int argc, char** argv) {
             CK(hipMemsetAsync(dcnt, 0, 4, st));
             hipLaunchKernelGGL(k_diff, dim3(2048), dim3(256), 0, st, (const unsigned*)C0, (const unsigned*)C1, (size_t)M * N / 2, dcnt);
             CK(hipMemcpyAsync(&nd, dcnt, 4, hipMemcpyDeviceToHost, st)); CK(hipStreamSynchronize(st));
-            if (mx > 2e-2f || nd) printf("   !!! q%d: max rel err vs f32 reference %.3e, words differing from k_gemm8s: %u\n", qc, mx, nd);
+            if (mx > 2e-2f || nd) printf("   !!! q8 %s: max rel err vs f32 reference %.3e, words differing from k_gemm8s: %u\n", q.name, mx, nd);
             std::vector<float> tq;
             for (int round = 0; round < 5; ++round) {
                 CK(hipEventRecord(e0, st));
-                for (int r = 0; r < 4; ++r) gemm8q_dispatch(qc, A, Wt, nullptr, nullptr, C1, M, N, K, lda, K, N, N, 0, cp, st);
+                for (int r = 0; r < 4; ++r) q.run(call(C1));
                 CK(hipEventRecord(e1, st)); CK(hipEventSynchronize(e1));
                 float ms; CK(hipEventElapsedTime(&ms, e0, e1));
                 tq.push_back(ms / 4);
             }
             std::sort(tq.begin(), tq.end());
-            printf("   q%d  (%s, 8-phase):  %8.1f us %6.0f TF (best %6.0f)\n", qc, qc == 1 ? "256x256" : "256x320", tq[2] * 1e3, flop / tq[2] / 1e9, flop / tq[0] / 1e9);
+            printf("   q8 %s (8-phase):  %8.1f us %6.0f TF (best %6.0f)\n", q.name, tq[2] * 1e3, flop / tq[2] / 1e9, flop / tq[0] / 1e9);
         }
         CK(hipFree(A)); CK(hipFree(Wt)); CK(hipFree(C0)); CK(hipFree(C1));
     }

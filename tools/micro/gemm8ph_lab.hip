@@ -242,8 +242,8 @@ int main(int argc, char** argv) {
         //           3 = 8-phase st_16x32 without setprio, 4 = 8-phase with the conflict-free swizzle + setprio
         const char* names[7] = {"k_gemm8s 256x256 (two barriers)", "k_gemm8p 256x256 (product)", "8-phase st_16x32 setprio (guide)", "8-phase st_16x32 no setprio", "8-phase full swizzle setprio", "8-phase st_16x32, 4-row bands", "8-phase st_16x32, 8-row bands"};
         auto launch = [&](int v, _Float16* C) {
-            if (v == 0) { g_gemm8_sched = 1; gemm8_dispatch(3, A, W, nullptr, nullptr, C, M, N, K, K, K, N, N, 0, cp, st); }
-            else if (v == 1) { g_gemm8_sched = 2; gemm8_dispatch(3, A, W, nullptr, nullptr, C, M, N, K, K, K, N, N, 0, cp, st); }
+            if (v == 0) { g_gemm8_sched = 1; gemm8_256x256(GemmCall{A, W, nullptr, nullptr, C, M, N, K, K, K, N, N, 0, cp, st}); }
+            else if (v == 1) { g_gemm8_sched = 2; gemm8_256x256(GemmCall{A, W, nullptr, nullptr, C, M, N, K, K, K, N, N, 0, cp, st}); }
             else if (v == 2) run_ph<0, 1>(A, W, C, M, N, K, st);
             else if (v == 3) run_ph<0, 0>(A, W, C, M, N, K, st);
             else if (v == 4) run_ph<1, 1>(A, W, C, M, N, K, st);

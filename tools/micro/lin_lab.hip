@@ -1,7 +1,7 @@
-// Stand-alone lab for the strip-resident K = 320 Linear (csrc/linstrip.hip, cfg 12) against the tiled kernels of csrc/gemm.hip (no torch).
+// Stand-alone lab for the strip-resident K = 320 Linear (csrc/linstrip.hip, tcl_gemm_tune id 12) against the tiled kernels of csrc/gemm.hip (no torch).
 //   python -c "import __graft_entry__ as g; g.build()"       (objects under tc_light_amd/csrc/build/)
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -Wno-comment -c tools/micro/lin_lab.hip -o scratch/lin_lab.o
-//   hipcc --offload-arch=gfx950 scratch/lin_lab.o tc_light_amd/csrc/build/{gemm,gemm8,linstrip}.o -o tools/micro/bin/lin_lab
+//   hipcc --offload-arch=gfx950 scratch/lin_lab.o tc_light_amd/csrc/build/{gemm,gemm8,gemm8q,linstrip,prof}.o -o tools/micro/bin/lin_lab
 // For every shape: cfg 12 is compared bit for bit with cfg 1 (k_gemm_dma 128x128) and timed beside cfgs 1, 3, 11 (median of 5 x 4 launches).
 #include <hip/hip_runtime.h>
 #include <algorithm>
