@@ -166,7 +166,7 @@ int tcl_ln_gemm_f16(const void* x, const void* gamma, const void* beta, float ep
  * AttnProcessor2_0, utils/model_utils.py:66-67): LayerNorm(x) @ W^T -> ws_q's Qp [B, H, ceil256(Tq), 48], pre-scaled by scale * log2 e, exactly as
  * tcl_attention_pack_f16 would have packed the Linear's output (same rounding points), without the [M, H d] round trip.  M = B * Tq rows, d = 40.
  * Rows Tq .. ceil256(Tq) of every (b, h) panel are NOT written: the caller keeps ws_q (tcl_attention_q_bytes) zero-initialised and reuses it.
- * Follow with tcl_attention_f16(..., pack_kv = 4 (pre-packed), ws_q, ws_kv). */
+ * Follow with tcl_attention_f16(..., TCL_ATTN_PREPACKED, ws_q, ws_kv). */
 int tcl_ln_gemm_qpanel_f16(const void* x, const void* gamma, const void* beta, float eps, const void* W, int M, int H, int d, int Tq, int ldx, int ldw,
                            float scale, void* ws_q, hipStream_t st);
 /* attn1's fused QKV projection of a VidToMe-merging block written straight into the attention panels (patch.py:170-176: `attn1(norm_hidden_states)` over the
@@ -175,7 +175,7 @@ int tcl_ln_gemm_qpanel_f16(const void* x, const void* gamma, const void* beta, f
  * merge.py's "replace" mode applied in the operand load instead of by a gather pass)
  * bytes tcl_attention_pack_f16 would have written from the [ne*T, 3 H d] product (d = 40 or 80).  ws_q / ws_kv: tcl_attention_q_bytes / _kv_bytes(ne, H, T, d),
  * ZERO-INITIALISED once per (ne, H, T, d) by the caller and reusable by stream-ordered calls of that shape (padding is never written).  Follow with
- * tcl_attention_f16(..., pack_kv = 4 (pre-packed) [| 2], ws_q, ws_kv). */
+ * tcl_attention_f16(..., TCL_ATTN_PREPACKED [| TCL_ATTN_PAIR], ws_q, ws_kv). */
 int tcl_gemm_qkv_panels_f16(const void* x, long x_bs, const int* row_index, const void* W, int ne, int T, int H, int d, int K, int ldx, int ldw, float scale,
                             void* ws_q, void* ws_kv, hipStream_t st);
 int tcl_layernorm_metric_f16(const void* x, const void* gamma, const void* beta, void* y, void* metric, long rows, int C, float eps, hipStream_t st);
@@ -221,18 +221,24 @@ int tcl_conv1x1_small_f16(const void* x, int ldi, const void* W, const void* b, 
 /* softmax(Q K^T * scale) V per head, flash style (torch SDPA / xformers via AttnProcessor2_0: attn1 on the VidToMe-merged
  * tokens, patch.py:170-176, and attn2 text cross-attention).  q/k/v/o point at head 0 of batch 0 with heads interleaved
  * in channels (head hh = channels [hh*d, (hh+1)*d)); ld* row strides and *bs batch strides in halves; d in {40, 80, 160}.
- * K/V batch = b / kv_div.  pack_kv bit 0: 0 reuses the K/V panels a previous call left in ws_kv (text K/V are constant per run); bit 1: the
- * B samples are one half of an identical pair (the CFG halves before the first text cross-attention): the kernel variant is chosen as for 2 B
- * samples, so the half alone gives the bits the full batch would have given; bit 2: the panels in ws_q / ws_kv were already written by
- * tcl_attention_pack_f16 (same arguments; e.g. on another stream, with the caller's event between the two): only the attention kernels run.
+ * K/V batch = b / kv_div.  pack_kv is a set of TCL_ATTN_* bits.  Without TCL_ATTN_PACK_KV the call reuses the K/V panels a previous call left in ws_kv
+ * (text K/V are constant per run).  TCL_ATTN_PAIR: the B samples are one half of an identical pair (the CFG halves before the first text cross-attention):
+ * the kernel variant is chosen as for 2 B samples, so the half alone gives the bits the full batch would have given.  TCL_ATTN_PREPACKED: the panels in
+ * ws_q / ws_kv were already written by tcl_attention_pack_f16 (same arguments; e.g. on another stream, with the caller's event between the two) or by a
+ * panel-writing GEMM: only the attention kernels run.
  * ws_q (tcl_attention_q_bytes): packed Q panel + one int per 128-query block (head_dim 40, large launches: blocks whose speculative
  * softmax left the f16 range are flagged there and redone by the exact-maximum kernel of the same call); no initialisation needed. */
+enum { TCL_ATTN_PACK_KV = 1, TCL_ATTN_PAIR = 2, TCL_ATTN_PREPACKED = 4 };
 size_t tcl_attention_q_bytes(int B, int H, int Tq, int d);
 size_t tcl_attention_kv_bytes(int Bkv, int H, int Tk, int d);
 int tcl_attention_f16(const void* q, int ldq, long qbs, const void* k, int ldk, long kbs, const void* v, int ldv, long vbs, void* o, int ldo,
                       long obs, int B, int H, int Tq, int Tk, int d, float scale, int kv_div, int pack_kv, void* ws_q, void* ws_kv,
                       hipStream_t st);
-/* The packing half of tcl_attention_f16 alone: Q panel (scaled) into ws_q and, with pack_kv bit 0, the K / V^T panels into ws_kv. */
+/* Which flash kernel tcl_attention_f16 takes for this call (flags: the TCL_ATTN_* bits), asked on the host alone: out4 = (variant id, blocks of its launch,
+ * blocks of the flag-gated exact launch behind the speculative head_dim-40 kernel or 0, dynamic LDS bytes).  Variant ids: 0 d40 two query blocks speculative,
+ * 1 d40 two query blocks exact, 2 d40 one query block, 3 d80, 4 d128, 5 d160.  Refuses what tcl_attention_f16 refuses. */
+int tcl_attention_plan(int B, int H, int Tq, int Tk, int d, int kv_div, int flags, int* out4);
+/* The packing half of tcl_attention_f16 alone: Q panel (scaled) into ws_q and, with TCL_ATTN_PACK_KV, the K / V^T panels into ws_kv. */
 int tcl_attention_pack_f16(const void* q, int ldq, long qbs, const void* k, int ldk, long kbs, const void* v, int ldv, long vbs, int B, int H, int Tq,
                            int Tk, int d, float scale, int kv_div, int pack_kv, void* ws_q, void* ws_kv, hipStream_t st);
 

@@ -12,11 +12,7 @@
 //           of tiles (TPB = 2, 4-slot ring).  S^T = K.Q^T with mfma_f32_32x32x16_f16 (swapped operands: lane l owns query l&31, so the row
 //           max/sum is in-lane + one lane<->lane+32 exchange); P stays in registers as the B operand of O^T = V^T.P^T (the key permutation
 //           of the accumulator layout is matched by the V^T fragment addresses instead of shuffling P).  Block id -> head = id % H so that
-//           each head's K/V panel lives in one XCD's L2.  The forms the dispatch in tcl_attention_f16 picks:
-//             d = 40, large grid : QB = 2, NSTG = 4, TPB = 2, SPEC = 1 (speculative softmax: no row maxima in the loop), followed by the same
-//                                  kernel with SPEC = 0 (exact maxima) gated by the per-block overflow flags of the first
-//             d = 40, small grid : QB = 1, NSTG = 2, four blocks per CU
-//             d = 80 / 128       : QB = 1, NSTG = 2;   d = 160: QB = 1, NSTG = 3
+//           each head's K/V panel lives in one XCD's L2.  The forms choose() picks from: the rows of g_flash.
 //  split-KV: k_flash_lse (the d = 128 body over one chunk of the keys per batch entry, which also hands on log2 of its softmax denominator)
 //           and k_attn_merge (joins the chunks' partial outputs).
 #include "common.h"
@@ -32,12 +28,6 @@ typedef float float16v __attribute__((ext_vector_type(16)));
 typedef float float4v __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-
-#define KV_TILE 64
-#define V_STRIDE 72   // halves: 144 B = 9 x 16 B (odd) -> the 16-lane groups of a ds_read_b128 are conflict-free
-// V^T tile of 64 keys: DPV rows of V_STRIDE halves.  Head_dim 40 stores 64 rows (9 KiB per tile, 16 DMA pieces per 64-key stage with the 7 KiB K
-// image), of which its PV on 16x16x32 MFMAs reads 48 (40 + the ones row + 7 idle).
-__host__ __device__ constexpr int vt_tile_halves(int dpv) { return dpv * V_STRIDE; }
 
 // one_col >= 0: that column (a padding column, >= d) is set to 1 in valid rows (the K panel's ones column for the folded shift)
 __device__ __forceinline__ void pack_rows_blk(int blk, int nblk, const _Float16* __restrict__ src, long bstride, int ld, int T, int H, int d, float scale,
@@ -644,29 +634,94 @@ static void flash_prof_drain(bool all) {
     }
 }
 
-template <int D, int DP, int DPV, int QB, int NSTG, int TPB = 1, int MINB = 0, int SPEC = 0>
-static int launch_flash(const _Float16* Qp, const _Float16* Kp, const _Float16* Vt, _Float16* O, int B, int H, int Tq, int Tk, int Tqp, int Tkp,
-                        int d, int ldo, long obs, int kv_div, hipStream_t st, int* flags = nullptr, bool count = true) {
-    constexpr int SB = KV_TILE * (DP + 8) * 2 + vt_tile_halves(DPV) * 2, NPIECE = (SB + 1023) / 1024;
-    const size_t lds = (size_t)NSTG * NPIECE * 1024 + 1024;
+// ---- host path: every C-ABI entry fills one AttnCall (check), then pack, choose, run
+// One attention call as every host function sees it: the operands (q/k/v/o point at head 0 of batch 0; row strides ld* and batch strides *bs in halves),
+// the problem, the decoded TCL_ATTN_* flags, the panel layout with the panels resolved inside ws_q / ws_kv, and the stream.
+struct AttnCall {
+    const _Float16 *q, *k, *v; int ldq, ldk, ldv; long qbs, kbs, vbs;
+    _Float16* o; int ldo; long obs;
+    int B, H, Tq, Tk, d; float scale; int kv_div;      // K/V batch index = b / kv_div (kv_div = F for the text cross-attention whose context repeats per frame, else 1)
+    bool pack_q, pack_kv, pair;                        // pack_kv = false reuses the K/V panels already in ws_kv (same Bkv, H, Tk, d as the call that packed them)
+    AttnPanels p;
+    _Float16 *Qp, *Kp, *Vt; int* flags;
+    hipStream_t st;
+};
+static bool attn_shape_ok(int B, int H, int Tq, int Tk, int d, int kv_div) {
+    return B > 0 && H > 0 && Tq > 0 && Tk > 0 && kv_div > 0 && B % kv_div == 0 && (d == 40 || d == 80 || d == 128 || d == 160);
+}
+// (shape already checked: kv_div > 0)
+static AttnCall attn_call(const void* q, int ldq, long qbs, const void* k, int ldk, long kbs, const void* v, int ldv, long vbs, void* o, int ldo, long obs,
+                          int B, int H, int Tq, int Tk, int d, float scale, int kv_div, int flags, void* ws_q, void* ws_kv, hipStream_t st) {
+    AttnCall c = {(const _Float16*)q, (const _Float16*)k, (const _Float16*)v, ldq, ldk, ldv, qbs, kbs, vbs, (_Float16*)o, ldo, obs, B, H, Tq, Tk, d, scale, kv_div,
+                  !(flags & TCL_ATTN_PREPACKED), (flags & TCL_ATTN_PACK_KV) != 0, (flags & TCL_ATTN_PAIR) != 0, attn_panels(B, B / kv_div, H, Tq, Tk, d)};
+    c.Qp = (_Float16*)ws_q; c.flags = (int*)((char*)ws_q + c.p.flags_off); c.Kp = (_Float16*)ws_kv; c.Vt = c.Kp + c.p.vt_off; c.st = st;
+    return c;
+}
+constexpr size_t flash_lds(int DP, int DPV, int NSTG) {      // NSTG ring slots of one K + V^T image in whole 1-KiB DMA pieces, + the 1-KiB dump
+    return (size_t)NSTG * ((KV_TILE * (DP + 8) * 2 + vt_tile_halves(DPV) * 2 + 1023) / 1024) * 1024 + 1024;
+}
+
+// One row per flash variant, and what choose() decides for a call: the variant, its launch, and the gated exact pass behind the speculative one
+struct FlashVariant { int id; const char* name; int d, qb; size_t lds; int (*run)(const AttnCall&, int grid, bool gated); };
+struct FlashPlan { const FlashVariant *v, *second; int grid, grid2; };
+
+template <int D, int QB, int NSTG, int TPB = 1, int MINB = 0, int SPEC = 0>
+static int launch_flash(const AttnCall& c, int grid, bool gated) {      // gated: the exact pass behind the speculative launch, over the flagged blocks
+    constexpr int DP = attn_dp(D), DPV = attn_dpv(D);
+    constexpr size_t lds = flash_lds(DP, DPV, NSTG);
     static bool set = false;
     if (!set) { (void)hipFuncSetAttribute((const void*)k_flash<D, DP, DPV, QB, NSTG, TPB, MINB, SPEC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); set = true; }
-    const int nqb = Tqp / (128 * QB);
-    const bool prof = g_prof.on && (g_prof.dfilter == 0 || g_prof.dfilter == d);
+    const int nqb = c.p.Tqp / (128 * QB);
+    const bool prof = g_prof.on && (g_prof.dfilter == 0 || g_prof.dfilter == c.d);
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (prof) {
         if (g_prof.ev.size() > 8192) flash_prof_drain(false);       // a 300-frame pass has ~1e5 launches: keep the live event count bounded
-        (void)hipEventCreate(&e0); (void)hipEventCreate(&e1); (void)hipEventRecord(e0, st);
+        (void)hipEventCreate(&e0); (void)hipEventCreate(&e1); (void)hipEventRecord(e0, c.st);
     }
-    const int nblk = B * H * nqb;
+    hipLaunchKernelGGL((k_flash<D, DP, DPV, QB, NSTG, TPB, MINB, SPEC>), dim3(grid), dim3(256), lds, c.st, c.Qp, c.Kp, c.Vt, c.o, c.H, c.Tq, c.Tk,
+                       c.p.Tqp, c.p.Tkp, c.d, c.ldo, c.obs, c.kv_div, nqb, SPEC || gated ? c.flags : nullptr, c.B * c.H * nqb);
+    // (the statistics count a call once: the gated pass is timed with the speculative launch it follows)
+    if (prof) { (void)hipEventRecord(e1, c.st); g_prof.ev.push_back(e0); g_prof.ev.push_back(e1); if (!gated) { const double fl = 4.0 * c.B * c.H * (double)c.Tq * c.Tk * c.d; g_prof.flops += fl; g_prof.launches++; if (fl > g_prof.bigfl) { g_prof.bigfl = fl; g_prof.big[0] = c.B; g_prof.big[1] = c.H; g_prof.big[2] = c.Tq; g_prof.big[3] = c.Tk; } } }
+    return hipPeekAtLastError() == hipSuccess ? TCL_OK : TCL_ELAUNCH;
+}
+template <int D, int QB, int NSTG, int TPB = 1, int MINB = 0, int SPEC = 0>
+constexpr FlashVariant flash_variant(int id, const char* name) {
+    return {id, name, D, QB, flash_lds(attn_dp(D), attn_dpv(D), NSTG), launch_flash<D, QB, NSTG, TPB, MINB, SPEC>};
+}
+// <head_dim, query blocks per wave, ring slots, tiles per barrier, blocks per CU (0: by shape), speculative>; the index is the id tcl_attention_plan reports
+enum { FV_40_SPEC, FV_40_QB2, FV_40_QB1, FV_80, FV_128, FV_160, FV_COUNT };
+static const FlashVariant g_flash[FV_COUNT] = {
+    // d = 40: two query blocks per wave (shared K/V fragments), 4-slot ring and two tiles per barrier, 2 blocks per CU (750 TFLOP/s at T = 35.6k).
+    // Speculative softmax (no row maxima in the loop), then the exact kernel over the blocks that flagged an f16 overflow of P (normally none)
+    flash_variant<40, 2, 4, 2, 0, 1>(FV_40_SPEC, "d40 qb2 speculative"),
+    flash_variant<40, 2, 4, 2>(FV_40_QB2, "d40 qb2 exact"),
+    // one query block per wave on a 2-slot ring at 4 blocks per CU (107 VGPRs: four waves per SIMD hide each other's softmax; 582 TFLOP/s at T = 8.9k)
+    flash_variant<40, 1, 2, 1, 4>(FV_40_QB1, "d40 qb1"),
+    // d = 80: one block, 2-slot ring (50 KB LDS -> 3 blocks per CU).  The kernel moves 24.5 KiB of K / V^T image per 128 queries and tile through
+    // LDS-DMA -- ~40 B / clk / CU at three blocks per CU, the measured ceiling of that path (profiles/r3_lds_dma_rate.txt)
+    flash_variant<80, 1, 2>(FV_80, "d80"),
+    // d = 128, MemFlowNet memory read: ONE head, ONE entry -- at 1280x720 14 400 queries are 114 blocks of 128 for 256 CUs (507 us per call, 0.17 of peak,
+    // profiles/r6_memflow_kernel_stats_before.txt).  2-wave blocks (twice the blocks) made the frame pair SLOWER, 47.7 against 45.9 ms
+    // (profiles/r6_ab_memflow_graph_nw.txt): the kernel is not simply grid-limited (tcl_attention_splitkv_f16 below cuts the keys instead)
+    flash_variant<128, 1, 2>(FV_128, "d128"),
+    flash_variant<160, 1, 3>(FV_160, "d160"),
+};
+// TCL_FLASH40: 0 = choose() as it stands (default), 1 = always the one-query-block kernel, 5 = no speculative softmax (the exact two-query-block
+// kernel alone: the kill switch; tools/micro/prec_attn.py, bench_attn_long.py).  Any other value behaves as 0.  Read once per process.
+static int flash40_mode() { static const int m = [] { const char* e = getenv("TCL_FLASH40"); const int v = e ? atoi(e) : 0; return v == 1 || v == 5 ? v : 0; }(); return m; }
+// Which variant a call gets, with its grid and LDS bytes.  No HIP call: tcl_attention_plan asks it without a GPU.
+static FlashPlan choose(const AttnCall& c, int flash40) {
+    // d = 40 takes the two-query-block kernels when the grid still fills the chip several times over (pair: counted as for the 2 B samples of the pair)
+    const bool qb2 = (long)c.B * (c.pair ? 2 : 1) * c.H * (c.p.Tqp / 256) >= 1024;
+    const int id = c.d == 40 ? (qb2 && flash40 != 1 ? (flash40 == 0 ? FV_40_SPEC : FV_40_QB2) : FV_40_QB1) : c.d == 80 ? FV_80 : c.d == 128 ? FV_128 : FV_160;
+    const FlashVariant& v = g_flash[id];
+    FlashPlan pl = {&v, nullptr, c.B * c.H * (c.p.Tqp / (128 * v.qb)), 0};
     // gated exact pass: a small grid of blocks walks the flags (normally none is set: what the launch costs is the DISPATCH of its 222-VGPR / 66-KiB blocks --
     // 57 us with one block per flag (round 3), 56 us in the pass with one resident round of 512 (round 4).  Round 5 measured smaller grids
     // (profiles/r5_ab_flash_gate.txt): 64 blocks the same call rate as 512, 16 blocks 1.4 % SLOWER -- the pass is not dispatch-bound)
     constexpr int GATE_BLOCKS = 512;
-    const int grid = (D == 40 && QB == 2 && !SPEC && flags && nblk > GATE_BLOCKS) ? GATE_BLOCKS : nblk;
-    hipLaunchKernelGGL((k_flash<D, DP, DPV, QB, NSTG, TPB, MINB, SPEC>), dim3(grid), dim3(256), lds, st, Qp, Kp, Vt, O, H, Tq, Tk, Tqp, Tkp, d, ldo, obs, kv_div, nqb, flags, nblk);
-    if (prof) { (void)hipEventRecord(e1, st); g_prof.ev.push_back(e0); g_prof.ev.push_back(e1); if (count) { const double fl = 4.0 * B * H * (double)Tq * Tk * d; g_prof.flops += fl; g_prof.launches++; if (fl > g_prof.bigfl) { g_prof.bigfl = fl; g_prof.big[0] = B; g_prof.big[1] = H; g_prof.big[2] = Tq; g_prof.big[3] = Tk; } } }
-    return hipPeekAtLastError() == hipSuccess ? TCL_OK : TCL_ELAUNCH;
+    if (id == FV_40_SPEC) { pl.second = &g_flash[FV_40_QB2]; pl.grid2 = pl.grid > GATE_BLOCKS ? GATE_BLOCKS : pl.grid; }
+    return pl;
 }
 
 // ---- round 6: split-KV for the MemFlowNet memory read (head_dim 128, ONE head, ONE entry: 14 400 queries are 114 blocks for 256 CUs -- 512 us per call,
@@ -701,8 +756,37 @@ __global__ void k_attn_merge(const _Float16* __restrict__ parts, const float* __
         *(half8*)(out + (long)q * ldo + c8) = o;
     }
 }
+// the workspace of a split-KV call: [Q panels | K / V^T panels | parts | lse], each part 1-KiB aligned; the panels are those of nsplit entries of one chunk
+struct SplitKvWs { AttnPanels p; size_t kv_off, parts_off, lse_off, bytes; };
+static SplitKvWs splitkv_ws(int nsplit, int H, int Tq, int Tk, int d) {
+    SplitKvWs w = {attn_panels(nsplit, nsplit, H, Tq, Tk / (nsplit > 0 ? nsplit : 1), d)};
+    w.kv_off = attn_rup(w.p.q_bytes, 1024); w.parts_off = w.kv_off + attn_rup(w.p.kv_bytes, 1024);
+    w.lse_off = w.parts_off + attn_rup((size_t)nsplit * Tq * H * d * 2, 1024); w.bytes = w.lse_off + (size_t)nsplit * H * Tq * 4 + 1024;
+    return w;
+}
 
-static inline int rup(int x, int m) { return (x + m - 1) / m * m; }
+// The Q (scaled), K and V^T panels of a call, as its pack_q / pack_kv ask: one launch when both are packed.
+static int attention_pack(const AttnCall& c) {
+    const AttnPanels& p = c.p;
+    const int Bkv = c.B / c.kv_div, nt = p.Tkp / KV_TILE;
+    const long qc = (long)c.B * c.H * p.Tqp * (p.DP / 8), kc = (long)Bkv * c.H * p.Tkp * (p.KS / 8);
+    const int gq = stream_grid(qc, 256, 2), gk = stream_grid(kc, 256, 2);
+    const size_t vt_lds = (size_t)64 * (p.DPV + 2) * 2;
+    const PackRows pq = {c.q, c.qbs, c.ldq, c.Tq, c.d, AttnPanels::qscale(c.scale), c.Qp, p.Tqp, p.DP, qc, -1};
+    const PackRows pk = {c.k, c.kbs, c.ldk, c.Tk, c.d, 1.f, c.Kp, p.Tkp, p.KS, kc, p.one_col};
+    auto rows = [&](const PackRows& r, int grid) {
+        hipLaunchKernelGGL(k_pack_rows, dim3(grid), dim3(256), 0, c.st, r.src, r.bstride, r.ld, r.T, c.H, r.d, r.scale, r.dst, r.Tp, r.DP, r.total, r.one_col);
+    };
+    if (c.pack_q && c.pack_kv)
+        hipLaunchKernelGGL(k_pack_qkv, dim3(gq + gk + nt * Bkv * c.H), dim3(256), vt_lds, c.st, pq, pk, gq, gk, c.H, c.v, c.vbs, c.ldv, c.Tk, c.d, c.Vt, nt, p.DPV, p.skew);
+    else {
+        if (c.pack_q) rows(pq, gq);
+        if (c.pack_kv) rows(pk, gk);
+        if (c.pack_kv) hipLaunchKernelGGL(k_pack_vt, dim3(nt, Bkv * c.H), dim3(256), vt_lds, c.st, c.v, c.vbs, c.ldv, c.Tk, c.H, c.d, c.Vt, nt, p.DPV, p.skew);
+    }
+    return hipPeekAtLastError() == hipSuccess ? TCL_OK : TCL_ELAUNCH;
+}
+
 extern "C" {
 
 // Timing of the flash kernel launches (all head dims, or only head_dim == dfilter) with HIP events on their stream.
@@ -719,136 +803,75 @@ int tcl_flash_profile_end(double* total_ms, double* total_flops, long* launches)
     return TCL_OK;
 }
 
-// panel sizes: Tqp = ceil256(Tq), Tkp = ceil64(Tk), DP = ceil16(d), DPV = ceil32(d); K rows DP+8 halves, V^T tiles DPV x V_STRIDE
-size_t tcl_attention_q_bytes(int B, int H, int Tq, int d) { return (size_t)B * H * rup(Tq, 256) * rup(d, 16) * 2 + 256 + (size_t)B * H * (rup(Tq, 256) / 128) * 4; }      // Q panel + per-block flags
-size_t tcl_attention_kv_bytes(int Bkv, int H, int Tk, int d) {
-    return ((size_t)Bkv * H * rup(Tk, 64) * (rup(d, 16) + 8) + (size_t)Bkv * H * (rup(Tk, 64) / 64) * rup(d, 32) * V_STRIDE) * 2 + 2048;
-}
+// panel sizes (AttnPanels): the Q panel + per-block flags; the K and V^T panels
+size_t tcl_attention_q_bytes(int B, int H, int Tq, int d) { return attn_panels(B, 0, H, Tq, 0, d).q_bytes; }
+size_t tcl_attention_kv_bytes(int Bkv, int H, int Tk, int d) { return attn_panels(0, Bkv, H, 0, Tk, d).kv_bytes; }
 
-// softmax(Q K^T * scale) V per head.  q/k/v point at head 0 of batch 0; row strides ld* and batch strides *bs in halves.
-// K/V batch index = b / kv_div (kv_div = F for the text cross-attention whose context repeats per frame, else 1).
-// pack_kv = 0 reuses the K/V panels already in ws_kv (same Bkv, H, Tk, d as the call that packed them).
-// The packing half of tcl_attention_f16 on its own (same panels, same workspace layout): Q (scaled) and, with pack_kv, K / V^T.  A caller that
-// runs it on another stream than the attention itself passes pack_kv bit 2 (and bit 0 = 0) to tcl_attention_f16 afterwards.
-static int attention_pack(const void* q, int ldq, long qbs, const void* k, int ldk, long kbs, const void* v, int ldv, long vbs, int B, int H, int Tq,
-                          int Tk, int d, float scale, int kv_div, int pack_q, int pack_kv, void* ws_q, void* ws_kv, hipStream_t st) {
-    const int Tqp = rup(Tq, 256), Tkp = rup(Tk, 64), DP = rup(d, 16), KS = DP + 8, DPV = rup(d, 32), Bkv = B / kv_div;
-    const int skew = d == 40 ? 1 : 0;      // head_dim 40 (64 V^T rows, PV on 16x16x32 MFMAs) reads the skewed panel, see pack_vt_blk
-    _Float16* Qp = (_Float16*)ws_q;
-    _Float16* Kp = (_Float16*)ws_kv;
-    _Float16* Vt = Kp + (((size_t)Bkv * H * Tkp * KS + 511) / 512) * 512;        // 1-KiB aligned
-    long qc = (long)B * H * Tqp * (DP / 8), kc = (long)Bkv * H * Tkp * (KS / 8);
-    if (pack_q && pack_kv) {
-        const int gq = stream_grid(qc, 256, 2), gk = stream_grid(kc, 256, 2), nt = Tkp / 64;
-        PackRows pq = {(const _Float16*)q, qbs, ldq, Tq, d, scale * 1.4426950408889634f, Qp, Tqp, DP, qc, -1};
-        PackRows pk = {(const _Float16*)k, kbs, ldk, Tk, d, 1.f, Kp, Tkp, KS, kc, d == 40 ? d : -1};
-        hipLaunchKernelGGL(k_pack_qkv, dim3(gq + gk + nt * Bkv * H), dim3(256), (size_t)64 * (DPV + 2) * 2, st, pq, pk, gq, gk, H, (const _Float16*)v, vbs, ldv, Tk, d, Vt,
-                           nt, DPV, skew);
-        return hipPeekAtLastError() == hipSuccess ? TCL_OK : TCL_ELAUNCH;
-    }
-    if (pack_q)
-        hipLaunchKernelGGL(k_pack_rows, dim3(stream_grid(qc, 256, 2)), dim3(256), 0, st, (const _Float16*)q, qbs, ldq, Tq, H, d,
-                           scale * 1.4426950408889634f, Qp, Tqp, DP, qc, -1);
-    if (pack_kv) {
-        hipLaunchKernelGGL(k_pack_rows, dim3(stream_grid(kc, 256, 2)), dim3(256), 0, st, (const _Float16*)k, kbs, ldk, Tk, H, d, 1.f, Kp, Tkp, KS, kc,
-                           d == 40 ? d : -1);
-        hipLaunchKernelGGL(k_pack_vt, dim3(Tkp / 64, Bkv * H), dim3(256), (size_t)64 * (DPV + 2) * 2, st, (const _Float16*)v, vbs, ldv, Tk, H, d, Vt, Tkp / 64, DPV, skew);
-    }
-    return hipPeekAtLastError() == hipSuccess ? TCL_OK : TCL_ELAUNCH;
-}
+// The packing half of tcl_attention_f16 on its own (same panels, same workspace layout): Q (scaled) and, with TCL_ATTN_PACK_KV, K / V^T.  A caller that
+// runs it on another stream than the attention itself passes TCL_ATTN_PREPACKED (and no TCL_ATTN_PACK_KV) to tcl_attention_f16 afterwards.
 int tcl_attention_pack_f16(const void* q, int ldq, long qbs, const void* k, int ldk, long kbs, const void* v, int ldv, long vbs, int B, int H, int Tq,
                            int Tk, int d, float scale, int kv_div, int pack_kv, void* ws_q, void* ws_kv, hipStream_t st) {
-    TCL_CHECK_ARG(q && ws_q && ws_kv && B > 0 && H > 0 && Tq > 0 && Tk > 0 && kv_div > 0 && B % kv_div == 0);
-    TCL_CHECK_ARG(d == 40 || d == 80 || d == 128 || d == 160);
-    TCL_CHECK_ARG(!(pack_kv & 1) || (k && v));
-    return attention_pack(q, ldq, qbs, k, ldk, kbs, v, ldv, vbs, B, H, Tq, Tk, d, scale, kv_div, 1, pack_kv & 1, ws_q, ws_kv, st);
+    TCL_CHECK_ARG(q && ws_q && ws_kv && attn_shape_ok(B, H, Tq, Tk, d, kv_div));
+    TCL_CHECK_ARG(!(pack_kv & TCL_ATTN_PACK_KV) || (k && v));
+    return attention_pack(attn_call(q, ldq, qbs, k, ldk, kbs, v, ldv, vbs, nullptr, 0, 0, B, H, Tq, Tk, d, scale, kv_div, pack_kv & TCL_ATTN_PACK_KV, ws_q, ws_kv, st));
 }
-// x: entry b's rows start at x + b * x_bs (elements); row_index (may be NULL): merged token t = row row_index[t] of the entry's block -- the VidToMe merge
-// map applied in the GEMM's operand load (merge.py "replace" mode is a pure gather), so the merged sequence needs no tensor of its own.
 // attn1's QKV projection of ne x T merged tokens (x [ne*T, K] @ W[3 H d, K]^T, no bias: diffusers Attention.to_q / to_k / to_v) written straight into
-// the panels tcl_attention_pack_f16 would have produced from its [ne*T, 3 H d] output -- same bits in every byte the pack writes.  ws_q / ws_kv must have
+// the panels tcl_attention_pack_f16 would have produced from its [ne*T, 3 H d] output -- same bits in every byte the pack writes.
+// x: entry b's rows start at x + b * x_bs (elements); row_index (may be NULL): merged token t = row row_index[t] of the entry's block -- the VidToMe merge
+// map applied in the GEMM's operand load (merge.py "replace" mode is a pure gather), so the merged sequence needs no tensor of its own.  ws_q / ws_kv must have
 // been ZERO-INITIALISED once for this (ne, H, T, d) (sizes: tcl_attention_q_bytes / _kv_bytes) and may be reused by stream-ordered calls of the same shape:
-// padding rows / columns and the V^T rows above the ones row are never written.  Follow with tcl_attention_f16(..., pack_kv = 4 | pair bit, ws_q, ws_kv).
+// padding rows / columns and the V^T rows above the ones row are never written.  Follow with tcl_attention_f16(..., TCL_ATTN_PREPACKED | pair bit, ws_q, ws_kv).
 int tcl_gemm_qkv_panels_f16(const void* x, long x_bs, const int* row_index, const void* W, int ne, int T, int H, int d, int K, int ldx, int ldw, float scale,
                             void* ws_q, void* ws_kv, hipStream_t st) {
     TCL_CHECK_ARG(x && W && ws_q && ws_kv && ne > 0 && T > 0 && H > 0 && (d == 40 || d == 80) && K > 0 && K % 32 == 0 && ldx >= K && ldw >= K);
-    const int Tqp = rup(T, 256), Tkp = rup(T, 64), DP = rup(d, 16), KS = DP + 8, DPV = rup(d, 32);
-    const int skew = d == 40 ? 1 : 0;      // the layout attention_pack writes: head_dim 40 panels are skewed, 64 V^T rows
-    _Float16* Kp = (_Float16*)ws_kv;
-    _Float16* Vt = Kp + (((size_t)ne * H * Tkp * KS + 511) / 512) * 512;
-    const QkvPanel qp = {(_Float16*)ws_q, Kp, Vt, T, Tqp, Tkp, H, d, DP, KS, DPV, vt_tile_halves(DPV), d == 40 ? 40 : -1, skew,
-                         scale * 1.4426950408889634f, row_index, x_bs};
+    const AttnPanels p = attn_panels(ne, ne, H, T, T, d);
+    const QkvPanel qp = {(_Float16*)ws_q, (_Float16*)ws_kv, (_Float16*)ws_kv + p.vt_off, T, p.Tqp, p.Tkp, H, d, p.DP, p.KS, p.DPV, p.vtile, p.one_col, p.skew,
+                         AttnPanels::qscale(scale), row_index, x_bs};
     TclProfScope ps(TCL_PROF_GEMM, st, 2.0 * ne * T * 3.0 * H * d * K);
     return gemm_dma_qkv_panels((const _Float16*)x, (const _Float16*)W, ne, K, ldx, ldw, qp, st);
 }
+// softmax(Q K^T * scale) V per head: check, pack, choose, run.
 int tcl_attention_f16(const void* q, int ldq, long qbs, const void* k, int ldk, long kbs, const void* v, int ldv, long vbs, void* o, int ldo,
                       long obs, int B, int H, int Tq, int Tk, int d, float scale, int kv_div, int pack_kv, void* ws_q, void* ws_kv,
                       hipStream_t st) {
-    TCL_CHECK_ARG(q && o && ws_q && ws_kv && B > 0 && H > 0 && Tq > 0 && Tk > 0 && kv_div > 0 && B % kv_div == 0);
-    TCL_CHECK_ARG(d == 40 || d == 80 || d == 128 || d == 160);
-    const int pair = (pack_kv >> 1) & 1;            // bit 1: these B samples are one half of an identical pair -> pick the kernel variant as for 2 B
-    const int prepacked = (pack_kv >> 2) & 1;       // bit 2: tcl_attention_pack_f16 already filled ws_q (and ws_kv): only the attention kernels run
-    pack_kv &= 1;
-    TCL_CHECK_ARG(!pack_kv || (k && v));
-    TCL_CHECK_ARG(!(prepacked && pack_kv));
-    const int Tqp = rup(Tq, 256), Tkp = rup(Tk, 64), DP = rup(d, 16), KS = DP + 8, Bkv = B / kv_div;
-    _Float16* Qp = (_Float16*)ws_q;
-    _Float16* Kp = (_Float16*)ws_kv;
-    _Float16* Vt = Kp + (((size_t)Bkv * H * Tkp * KS + 511) / 512) * 512;        // 1-KiB aligned
-    if (attention_pack(q, ldq, qbs, k, ldk, kbs, v, ldv, vbs, B, H, Tq, Tk, d, scale, kv_div, !prepacked, pack_kv, ws_q, ws_kv, st) != TCL_OK) return TCL_ELAUNCH;
-    // d = 40: two query blocks per wave (shared K/V fragments), 4-slot ring and two tiles per barrier, 2 blocks per CU, when the grid still
-    // fills the chip several times over (750 TFLOP/s at T = 35.6k); else one query block per wave on a 2-slot ring at 4 blocks per CU (107 VGPRs:
-    // four waves per SIMD hide each other's softmax; 582 TFLOP/s at T = 8.9k).  d = 80: one block, 2-slot ring (50 KB LDS -> 3 blocks per CU)
-    const bool qb2 = (long)B * (pair ? 2 : 1) * H * (Tqp / 256) >= 1024;
-    // TCL_FLASH40: 0 = the dispatch above (default), 1 = always the one-query-block kernel, 5 = no speculative softmax (the exact two-query-block
-    // kernel alone: the kill switch; tools/micro/prec_attn.py, bench_attn_long.py).  Any other value behaves as 0.
-    static const int var40 = [] { const char* e = getenv("TCL_FLASH40"); const int v = e ? atoi(e) : 0; return v == 1 || v == 5 ? v : 0; }();
-    if (d == 40 && qb2 && var40 == 0) {
-        // speculative softmax (no row maxima in the loop), then the exact kernel over the blocks that flagged an f16 overflow of P (normally none:
-        // its blocks read one flag and leave)
-        int* flags = (int*)((char*)ws_q + (((size_t)B * H * Tqp * DP * 2 + 255) / 256) * 256);
-        int rc = launch_flash<40, 48, 64, 2, 4, 2, 0, 1>(Qp, Kp, Vt, (_Float16*)o, B, H, Tq, Tk, Tqp, Tkp, d, ldo, obs, kv_div, st, flags);
-        if (rc == TCL_OK) rc = launch_flash<40, 48, 64, 2, 4, 2>(Qp, Kp, Vt, (_Float16*)o, B, H, Tq, Tk, Tqp, Tkp, d, ldo, obs, kv_div, st, flags, false);
-        return rc;
-    }
-    if (d == 40) return qb2 && var40 != 1 ? launch_flash<40, 48, 64, 2, 4, 2>(Qp, Kp, Vt, (_Float16*)o, B, H, Tq, Tk, Tqp, Tkp, d, ldo, obs, kv_div, st)
-                                          : launch_flash<40, 48, 64, 1, 2, 1, 4>(Qp, Kp, Vt, (_Float16*)o, B, H, Tq, Tk, Tqp, Tkp, d, ldo, obs, kv_div, st);
-    // d = 80: the kernel moves 24.5 KiB of K / V^T image per 128 queries and tile through LDS-DMA -- ~40 B / clk / CU at three blocks per CU, the
-    // measured ceiling of that path (profiles/r3_lds_dma_rate.txt)
-    if (d == 80) return launch_flash<80, 80, 96, 1, 2>(Qp, Kp, Vt, (_Float16*)o, B, H, Tq, Tk, Tqp, Tkp, d, ldo, obs, kv_div, st);
-    // d = 128, MemFlowNet memory read: ONE head, ONE entry -- at 1280x720 14 400 queries are 114 blocks of 128 for 256 CUs (507 us per call, 0.17 of peak,
-    // profiles/r6_memflow_kernel_stats_before.txt).  2-wave blocks (twice the blocks) made the frame pair SLOWER, 47.7 against 45.9 ms
-    // (profiles/r6_ab_memflow_graph_nw.txt): the kernel is not simply grid-limited (tcl_attention_splitkv_f16 below cuts the keys instead)
-    if (d == 128) return launch_flash<128, 128, 128, 1, 2>(Qp, Kp, Vt, (_Float16*)o, B, H, Tq, Tk, Tqp, Tkp, d, ldo, obs, kv_div, st);
-    return launch_flash<160, 160, 160, 1, 3>(Qp, Kp, Vt, (_Float16*)o, B, H, Tq, Tk, Tqp, Tkp, d, ldo, obs, kv_div, st);
+    TCL_CHECK_ARG(q && o && ws_q && ws_kv && attn_shape_ok(B, H, Tq, Tk, d, kv_div));
+    TCL_CHECK_ARG(!(pack_kv & TCL_ATTN_PACK_KV) || ((k && v) && !(pack_kv & TCL_ATTN_PREPACKED)));
+    const AttnCall c = attn_call(q, ldq, qbs, k, ldk, kbs, v, ldv, vbs, o, ldo, obs, B, H, Tq, Tk, d, scale, kv_div, pack_kv, ws_q, ws_kv, st);
+    if (attention_pack(c) != TCL_OK) return TCL_ELAUNCH;
+    const FlashPlan pl = choose(c, flash40_mode());
+    int rc = pl.v->run(c, pl.grid, false);
+    if (rc == TCL_OK && pl.second) rc = pl.second->run(c, pl.grid2, true);
+    return rc;
+}
+// What choose() decides for tcl_attention_f16(..., flags, ...): out4 = (variant id, blocks of its launch, blocks of the gated exact launch behind the
+// speculative kernel or 0, dynamic LDS bytes).  Pure host code.
+int tcl_attention_plan(int B, int H, int Tq, int Tk, int d, int kv_div, int flags, int* out4) {
+    TCL_CHECK_ARG(out4 && attn_shape_ok(B, H, Tq, Tk, d, kv_div) && !((flags & TCL_ATTN_PACK_KV) && (flags & TCL_ATTN_PREPACKED)));
+    const FlashPlan pl = choose(attn_call(nullptr, 0, 0, nullptr, 0, 0, nullptr, 0, 0, nullptr, 0, 0, B, H, Tq, Tk, d, 1.f, kv_div, flags, nullptr, nullptr, nullptr), flash40_mode());
+    out4[0] = pl.v->id; out4[1] = pl.grid; out4[2] = pl.grid2; out4[3] = (int)pl.v->lds;
+    return TCL_OK;
 }
 
 // Split-KV attention for one entry (B = 1): see k_flash_lse.  q [Tq, ldq], k [Tk, ldk], v [Tk, ldv] (head h at column h d), o [Tq, ldo].
 // Tk must be a multiple of 64 nsplit; d = 128.  ws: tcl_attention_splitkv_workspace_bytes(nsplit, H, Tq, Tk, d).
-size_t tcl_attention_splitkv_workspace_bytes(int nsplit, int H, int Tq, int Tk, int d) {
-    const size_t qb = (tcl_attention_q_bytes(nsplit, H, Tq, d) + 1023) / 1024 * 1024, kb = (tcl_attention_kv_bytes(nsplit, H, Tk / (nsplit > 0 ? nsplit : 1), d) + 1023) / 1024 * 1024;
-    return qb + kb + (((size_t)nsplit * Tq * H * d * 2 + 1023) / 1024 * 1024) + (size_t)nsplit * H * Tq * 4 + 1024;
-}
+size_t tcl_attention_splitkv_workspace_bytes(int nsplit, int H, int Tq, int Tk, int d) { return splitkv_ws(nsplit, H, Tq, Tk, d).bytes; }
 int tcl_attention_splitkv_f16(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* o, int ldo, int H, int Tq, int Tk, int d,
                               float scale, int nsplit, void* ws, hipStream_t st) {
     TCL_CHECK_ARG(q && k && v && o && ws && H > 0 && Tq > 0 && Tk > 0 && d == 128 && nsplit >= 2 && nsplit <= 16 && Tk % (64 * nsplit) == 0 && ldo >= H * d);
-    const int chunk = Tk / nsplit, Tqp = rup(Tq, 256), Tkp = chunk, DP = 128, KS = DP + 8;
+    const SplitKvWs w = splitkv_ws(nsplit, H, Tq, Tk, d);
+    const int chunk = Tk / nsplit;
     char* base = (char*)ws;
-    const size_t qb = (tcl_attention_q_bytes(nsplit, H, Tq, d) + 1023) / 1024 * 1024, kb = (tcl_attention_kv_bytes(nsplit, H, chunk, d) + 1023) / 1024 * 1024;
-    void *ws_q = base, *ws_kv = base + qb;
-    _Float16* parts = (_Float16*)(base + qb + kb);
-    float* lse = (float*)(base + qb + kb + (((size_t)nsplit * Tq * H * d * 2 + 1023) / 1024 * 1024));
-    if (attention_pack(q, ldq, 0, k, ldk, (long)chunk * ldk, v, ldv, (long)chunk * ldv, nsplit, H, Tq, chunk, d, scale, 1, 1, 1, ws_q, ws_kv, st) != TCL_OK) return TCL_ELAUNCH;
-    _Float16* Qp = (_Float16*)ws_q;
-    _Float16* Kp = (_Float16*)ws_kv;
-    _Float16* Vt = Kp + (((size_t)nsplit * H * Tkp * KS + 511) / 512) * 512;
-    constexpr int NSTG = 2, SB = KV_TILE * (128 + 8) * 2 + vt_tile_halves(128) * 2, NPIECE = (SB + 1023) / 1024;
-    const size_t lds = (size_t)NSTG * NPIECE * 1024 + 1024;
+    _Float16* parts = (_Float16*)(base + w.parts_off); float* lse = (float*)(base + w.lse_off);
+    // the per-chunk view: nsplit batch entries share the queries (batch stride 0) and own one chunk of the keys each; entry s writes parts[s]
+    const AttnCall c = attn_call(q, ldq, 0, k, ldk, (long)chunk * ldk, v, ldv, (long)chunk * ldv, parts, H * d, (long)Tq * H * d, nsplit, H, Tq, chunk, d, scale, 1,
+                                 TCL_ATTN_PACK_KV, base, base + w.kv_off, st);
+    if (attention_pack(c) != TCL_OK) return TCL_ELAUNCH;
+    constexpr size_t lds = flash_lds(128, 128, 2);
     static bool set = false;
     if (!set) { (void)hipFuncSetAttribute((const void*)k_flash_lse<128, 128, 128, 1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); set = true; }
-    const int nqb = Tqp / 128;
-    hipLaunchKernelGGL((k_flash_lse<128, 128, 128, 1, 2>), dim3(nsplit * H * nqb), dim3(256), lds, st, Qp, Kp, Vt, parts, H, Tq, chunk, Tqp, Tkp, d, H * d,
-                       (long)Tq * H * d, nqb, lse);
+    const int nqb = c.p.Tqp / 128;
+    hipLaunchKernelGGL((k_flash_lse<128, 128, 128, 1, 2>), dim3(nsplit * H * nqb), dim3(256), lds, st, c.Qp, c.Kp, c.Vt, c.o, H, Tq, chunk, c.p.Tqp, c.p.Tkp, d, c.ldo,
+                       c.obs, nqb, lse);
     hipLaunchKernelGGL(k_attn_merge, dim3(stream_grid((long)Tq * (H * d / 8), 256, 2)), dim3(256), 0, st, parts, lse, (_Float16*)o, nsplit, H, Tq, d, ldo);
     TCL_LAUNCH_RET();
 }

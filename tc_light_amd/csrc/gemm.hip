@@ -454,7 +454,7 @@ __global__ __launch_bounds__(256, BM * BN >= 256 * 256 ? 1 : BM * BN > 128 * 128
                         const bool ok = kt * 64 + r < qp.T;
                         o[j] = ok ? (pass ? (_Float16)1.f : src[r * CS]) : (_Float16)0.f;
                     }
-                    *(half8*)(tile + rowi * 72 + 8 * p8) = o;
+                    *(half8*)(tile + rowi * V_STRIDE + 8 * p8) = o;
                 }
             }
         }

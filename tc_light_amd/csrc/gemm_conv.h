@@ -1,6 +1,7 @@
 // Shared between gemm.hip and gemm8.hip: implicit-GEMM 3x3 convolution descriptor and the 8-wave kernel entry.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "attn_panels.h"
 
 struct ConvP {
     int conv;            // 0: dense A[M][lda]; 1: implicit 3x3
@@ -10,8 +11,8 @@ struct ConvP {
     float sy, sx;        // Hin/Hup, Win/Wup (nearest source scale, PyTorch 'nearest' convention)
 };
 
-// QKV projection written straight into the flash kernel's panels (round 5; csrc/attn.hip documents the layouts): Qp [ne, H, Tqp, DP] pre-scaled,
-// Kp [ne, H, Tkp, KS] (+ ones column `one_col` when >= 0), Vt [ne, H, Tkp / 64, vtile halves]: DPV rows of 72 halves per 64-key tile, keys permuted
+// QKV projection written straight into the flash kernel's panels (round 5; csrc/attn.hip documents the layouts, attn_panels.h defines them): Qp [ne, H, Tqp, DP] pre-scaled,
+// Kp [ne, H, Tkp, KS] (+ ones column `one_col` when >= 0), Vt [ne, H, Tkp / 64, vtile halves]: DPV rows of V_STRIDE halves per 64-key tile, keys permuted
 // (bits 2 <-> 3 of the in-tile key index), rows 4..11 (mod 16) skewed by 16 positions when `skew`, row d = ones over the valid keys when DPV > d.
 // Everything the epilogue does not write (padding rows / columns, rows d + 1 .. DPV - 1) is expected to be ZERO already.
 // aidx (may be null): token t of an entry reads row aidx[t] of that entry's source block (the VidToMe merge map: the merged sequence is never gathered into
@@ -37,7 +38,7 @@ __device__ __forceinline__ float gelu_erf(float v) {
     const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, ax, 1.f));
     float p = fmaf(1.061405429f, t, -1.453152027f);
     p = fmaf(p, t, 1.421413741f); p = fmaf(p, t, -0.284496736f); p = fmaf(p, t, 0.254829592f);
-    const float e = __builtin_amdgcn_exp2f(ax * ax * -1.4426950408889634f);
+    const float e = __builtin_amdgcn_exp2f(ax * ax * -TCL_LOG2E);
     const float erfa = fmaf(-(p * t), e, 1.f);                     // erf(|x|)
     return 0.5f * v * (1.f + copysignf(erfa, x));
 }

@@ -35,7 +35,7 @@ __device__ __forceinline__ void ls_exchange(const _Float16 (&o)[16], uint4v& p0,
     p1 = uint4v{s2[0], s3[0], s2[1], s3[1]};
 }
 
-// Q-panel epilogue (round 5): instead of C [M, N] the result goes straight into the flash kernel's query panel Qp [B, H, Tqp, 48] (csrc/attn.hip:
+// Q-panel epilogue (round 5): instead of C [M, N] the result goes straight into the flash kernel's query panel Qp [B, H, Tqp, DP] (csrc/attn_panels.h:
 // head-major rows of DP = 48 halves, pre-scaled by softmax_scale * log2 e, columns 40..47 zero) -- the attn2 to_q projection of the C = 320
 // transformer blocks then needs neither its [M, 320] output nor the pack pass that re-read it (k_pack_rows: 1.07 s per 300-frame pass).  Rows
 // t >= Tq of the panel are never written here: the caller keeps them zero.  Same rounding points as Linear -> pack: f16(acc), then f16(. * scale).
@@ -205,7 +205,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void k_lin_strip(const _F
 #pragma unroll
                         for (int j = 0; j < 8; ++j) v[pc][j] = (_Float16)((float)v[pc][j] * qp.scale);
                         const int c = n0 + a * 32 + 8 * hl + 16 * pc, head = c / 40, dd = c - head * 40;
-                        _Float16* dst = qp.panel + (((long)q_b * q_H + head) * qp.Tqp + q_t) * 48 + dd;
+                        _Float16* dst = qp.panel + (((long)q_b * q_H + head) * qp.Tqp + q_t) * attn_dp(40) + dd;
                         *(half8*)dst = v[pc];
                         if (dd == 32) { half8 z; for (int j = 0; j < 8; ++j) z[j] = (_Float16)0.f; *(half8*)(dst + 8) = z; }      // the panel's padding columns 40..47
                     }
@@ -288,7 +288,7 @@ int tcl_ln_gemm_qpanel_f16(const void* x, const void* gamma, const void* beta, f
     const GemmCall c = {(const _Float16*)x, (const _Float16*)W, nullptr, nullptr, (_Float16*)ws_q, M, N, K, ldx, ldw, N, N, 0, ConvP{}, st};
     TCL_CHECK_ARG(lin_strip_ok(c) && ldx >= K && ldw >= K);
     TclProfScope ps(TCL_PROF_GEMM, st, 2.0 * M * N * K);
-    const QPanel qp = {(_Float16*)ws_q, Tq, (Tq + 255) / 256 * 256, scale * 1.4426950408889634f};
+    const QPanel qp = {(_Float16*)ws_q, Tq, attn_panels(M / Tq, 0, H, Tq, 0, d).Tqp, AttnPanels::qscale(scale)};
     return lin_strip_launch(c, (const _Float16*)gamma, (const _Float16*)beta, eps, qp);
 }
 }

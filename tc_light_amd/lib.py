@@ -15,6 +15,9 @@ ROOT = os.path.dirname(_HERE)
 HEADER = os.path.join(ROOT, "include", "tclight_hip.h")
 LIB_PATH = os.environ.get("TCL_LIB_PATH") or os.path.join(_HERE, "libtclight_hip.so")     # TCL_LIB_PATH: A/B runs of two builds (tools/ab)
 
+# the pack_kv bits of tcl_attention_f16 (the enum of the same names in the header)
+TCL_ATTN_PACK_KV, TCL_ATTN_PAIR, TCL_ATTN_PREPACKED = 1, 2, 4
+
 _ERR = {1: "TCL_EINVAL (bad argument / unsupported shape)", 2: "TCL_ELAUNCH (HIP error)"}
 
 

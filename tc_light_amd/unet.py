@@ -11,7 +11,7 @@ import os
 
 import torch
 
-from .lib import lib, stream
+from .lib import TCL_ATTN_PACK_KV, TCL_ATTN_PAIR, TCL_ATTN_PREPACKED, lib, stream
 from . import sd15
 from .vidtome import VidToMe
 
@@ -126,18 +126,18 @@ class Ops:
         self.L.tcl_ln_gemm_f16(x, gamma, beta, 1e-5, w, bias if bias is not None else 0, 0, c, M, N, K, K, K, c.shape[1], N, act, stream())
         return c
 
-    def attention(self, q, ldq, qbs, k, ldk, kbs, v, ldv, vbs, B, Hh, Tq, Tk, d, kv_div=1, ws_kv=None, pack_kv=1, pair=False, packed=None):
+    def attention(self, q, ldq, qbs, k, ldk, kbs, v, ldv, vbs, B, Hh, Tq, Tk, d, kv_div=1, ws_kv=None, pack_kv=True, pair=False, packed=None):
         """packed: (ws_q, ws_kv) already filled by a panel-writing GEMM (tcl_gemm_qkv_panels_f16 / tcl_ln_gemm_qpanel_f16)."""
         o = self.empty(B * Tq, Hh * d)
         if packed is not None:
-            wq, ws_kv, flags = packed[0], packed[1], 4
+            wq, ws_kv, flags = packed[0], packed[1], TCL_ATTN_PREPACKED
         else:
             wq = torch.empty(self.L.tcl_attention_q_bytes(B, Hh, Tq, d), dtype=torch.uint8, device=self.dev)
             if ws_kv is None:
                 ws_kv = torch.empty(self.L.tcl_attention_kv_bytes(B // kv_div, Hh, Tk, d), dtype=torch.uint8, device=self.dev)
-            flags = pack_kv
+            flags = TCL_ATTN_PACK_KV if pack_kv else 0
         self.L.tcl_attention_f16(q, ldq, qbs, k if k is not None else 0, ldk, kbs, v if v is not None else 0, ldv, vbs, o, Hh * d,
-                                 Tq * Hh * d, B, Hh, Tq, Tk, d, d ** -0.5, kv_div, flags | (2 if pair else 0), wq, ws_kv, stream())
+                                 Tq * Hh * d, B, Hh, Tq, Tk, d, d ** -0.5, kv_div, flags | (TCL_ATTN_PAIR if pair else 0), wq, ws_kv, stream())
         return o
 
 
@@ -405,7 +405,7 @@ class UNetEngine:
         else:
             q = o.ln_gemm(h, *blk["ln"][1], blk["q2"]) if fuse_ln else o.gemm(o.layernorm(h, *blk["ln"][1], M, C), blk["q2"])
             a = o.attention(q, C, N * C, tk["kv"], 2 * C, Lt * 2 * C, tk["kv"][:, C:], 2 * C, Lt * 2 * C, B, Hd, N, Lt, d,
-                            kv_div=F, ws_kv=tk["ws"], pack_kv=0 if tk["packed"] else 1)
+                            kv_div=F, ws_kv=tk["ws"], pack_kv=not tk["packed"])
         tk["packed"] = True
         h = o.gemm(a, blk["o2"][0], blk["o2"][1], resid=h)
         self._fl(2.0 * M * C * C * 2 + 4.0 * M * Lt * C)

@@ -129,7 +129,7 @@ def test_layernorm_geglu_softmax_gemv(L):
 
 
 @pytest.mark.parametrize("d,B,Tq,Tk,kv_div", [(40, 2, 300, 300, 1), (40, 2, 1000, 777, 1), (80, 4, 260, 154, 2), (160, 2, 180, 180, 1),
-                                             (80, 2, 129, 64, 1), (40, 2, 64, 2113, 1)])
+                                             (80, 2, 129, 64, 1), (40, 2, 64, 2113, 1), (40, 16, 1793, 200, 1)])
 def test_attention(L, d, B, Tq, Tk, kv_div):
     Hh = 8
     C = Hh * d
