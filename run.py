@@ -2,7 +2,8 @@
 data.scene_type picks the parser (generate.py:84-95): video (VideoDataParser) or sceneflow (SceneFlowDataParser: ground-truth depth, poses and
 flows -> voxelised Unique Video Tensor ids); carla and interiornet are not built.
 
-load_config -> seed_everything -> init_iclight -> Generator -> output.mp4 (frames / .npy when the image has no encoder), output_gt, loss
+load_config -> seed_everything -> init_iclight (generation.use_lora: the LoRA of generation.lora merged into the UNet and the text encoder) ->
+Generator (start latents from generation.latents_path when an inversion saved them) -> output.mp4 (frames / .npy when the image has no encoder), output_gt, loss
 curves and config.yaml with the reference's metric keys (total_time, sec_per_frame, max_memory_allocated, total_number_of_frames;
 generate.py:607-630).
 Multi-GPU: torchrun --nproc-per-node N run.py ... shards frames over the ranks (tc_light_amd/parallel.py).
@@ -40,6 +41,10 @@ def main(argv=None):
         raise NotImplementedError(f"data.scene_type '{scene_type}': this dataparser is not yet built in tc_light_amd (video and sceneflow are)")
     if scene_type not in ("video", "sceneflow"):
         raise NotImplementedError(f"Scene type '{scene_type}' is not supported.")
+    lora = None
+    if config.generation.get("use_lora"):         # generate_utils.py:95-96; the file is read and its layout checked before any model is loaded
+        from tc_light_amd.lora import from_config
+        lora = from_config(config.generation.get("lora"))
     world, rank, local = (int(os.environ.get(k, d)) for k, d in (("WORLD_SIZE", 1), ("RANK", 0), ("LOCAL_RANK", 0)))
     dev = torch.device("cuda", local)
     torch.cuda.set_device(dev)
@@ -48,7 +53,7 @@ def main(argv=None):
         torch.distributed.init_process_group("nccl", device_id=dev)
     models = config.get("models") or {}
     ok_random = allow_random(models)
-    pipe, scheduler, config.model_key = init_iclight(dev, models, seed=config.seed)
+    pipe, scheduler, config.model_key = init_iclight(dev, models, seed=config.seed, lora=lora)
     config.max_memory_allocated, config.total_time = 0, 0
     if scene_type == "sceneflow":
         from tc_light_amd.sceneflow import SceneFlowDataParser
@@ -89,6 +94,7 @@ def main(argv=None):
         elif err is not None:
             raise err
     cfg = dict(g); cfg.update(config.post_opt); cfg["seed"] = config.seed
+    cfg["frame_ids"], cfg["model_key"] = frame_ids, config.model_key      # generation.latents_path: which saved start latents are this run's
     rmbg = background = None
     if g.get("background_cond"):                               # generate.py:68-69, 147-167
         from tc_light_amd.model_utils import load_rmbg_state
@@ -99,8 +105,8 @@ def main(argv=None):
             background = background[lo:hi]
     gen = Generator(pipe.unet, pipe.vae, cfg, dist=d, scheduler=scheduler, rmbg=rmbg)
     for name, prompt in g.prompt.items():
-        conds = encode_prompt_pair(prompt, g.negative_prompt, dev, models.get("text_encoder"), allow_random=ok_random)
-        conds_t = encode_prompt_pair(g.prompt_t, g.negative_prompt_t, dev, models.get("text_encoder"), allow_random=ok_random)
+        conds = encode_prompt_pair(prompt, g.negative_prompt, dev, models.get("text_encoder"), allow_random=ok_random, lora=lora)
+        conds_t = encode_prompt_pair(g.prompt_t, g.negative_prompt_t, dev, models.get("text_encoder"), allow_random=ok_random, lora=lora)
         masks = inv = k = past = None
         if scene is not None:
             masks, inv, k, past = scene["masks"], scene["inv"], scene["k"], scene["past_flows"]

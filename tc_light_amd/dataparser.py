@@ -11,6 +11,8 @@ Flow: the reference's on-disk cache format `<video>_{past,future}_flow_memflow/%
 file count matches, :112-132).  `estimate_and_cache_flow` runs the MemFlowNet engine (tc_light_amd/memflow.py) when no cache exists.
 Output: `save_video` / `save_frames` (utils.py:147-187): `output{post_fix}.mp4` through torchvision/cv2 when an encoder exists, else the
 frames as PNGs under `frames{post_fix}/` plus `output{post_fix}.npy` (uint8 [N,H,W,3]) so `evaluate.py`-style consumers still find data.
+Start latents: `get_latents_dir`, `check_latent_exists`, `load_latent` (utils.py:200-213, 304-309; generate_utils.py:323-334) find and read the
+`noisy_latents_<t>.pt` an inversion saved under `generation.latents_path`.
 """
 import os
 from glob import glob
@@ -347,6 +349,32 @@ class VideoDataParser:
                     torch.save(fl[i:i + 1].cpu(), dst + ".tmp")
                     os.replace(dst + ".tmp", dst)
         return fut, past
+
+
+def get_latents_dir(latents_path, model_key):
+    """utils/VidToMe/utils.py:304-309: the latents of one model live under `<latents_path>/<last component of model_key>` ("default" without one)."""
+    return os.path.join(latents_path, "default" if model_key is None else model_key.split("/")[-1])
+
+
+def latent_file(latent_path, t):
+    """`noisy_latents_<t>.pt` (utils.py:201-203); t is the scheduler's timestep, an int or a 0-dim integer tensor."""
+    return os.path.join(latent_path, f"noisy_latents_{int(t)}.pt")
+
+
+def check_latent_exists(latent_path, timesteps):
+    """generate_utils.py:323-334 without PnP: `timesteps` is [scheduler.timesteps[0]]; every one of them needs its file."""
+    return all(os.path.exists(latent_file(latent_path, t)) for t in timesteps)
+
+
+def load_latent(latent_path, t, frame_ids=None):
+    """utils.py:200-213: the saved tensor over the video's frames, `frame_ids` selected along dim 0 (on the CPU; the caller casts and moves it)."""
+    lp = latent_file(latent_path, t)
+    if not os.path.exists(lp):
+        raise FileNotFoundError(f"Latent at timestep {int(t)} not found in {latent_path}.")
+    latents = _torch_load(lp)
+    if frame_ids is not None:
+        latents = latents[list(frame_ids)]
+    return latents
 
 
 def get_frame_ids(frame_range, n_frames, frame_ids=None):

@@ -17,6 +17,7 @@ import torch
 from .lib import lib, stream
 from . import hostlogic as HL
 from . import post_opt
+from .dataparser import check_latent_exists, get_latents_dir, load_latent
 from .parallel import Dist, sharded_temporal_pass
 from .scheduler import DPMSolverSDEScheduler
 
@@ -38,6 +39,9 @@ DEFAULTS = dict(  # configs/tclight_default.yaml (generation / post_opt sections
                                      #   from K ~ 1e7 up; kept for memory-bound cases).  "shard": the round-1 approximation, each rank's frame
                                      #   block as a video of its own (tracks cut at the block seams) -- NOT the reference's result.
     shard_post_opt=False,            # legacy spelling of post_opt_mode="shard"
+    latents_path=None, model_key="iclight", frame_ids=None,
+    # ^ generation.latents_path (generate.py:563-566): saved start latents `<latents_path>/<model_key>/noisy_latents_<first timestep>.pt`, a tensor
+    #   over the video's frames of which `frame_ids` (None: all) are this run's; when the file exists it replaces the random start noise.
     max_tokens_per_pass=None)
     # ^ None: TCL_MAX_TOKENS_PER_PASS (read when the Generator is built), else min(16 M, 80 % of the device's free memory / 10.5 KB) -- a block-major pass
     #   peaks at ~10.4 KB of activations per level-0 token (90 GB for the 8.64 M tokens of 300 frames at 1280x720): a 288 GB MI355X gets the 16 M
@@ -94,6 +98,8 @@ class Generator:
         self.h, self.w = H // 8, W // 8
         self.n_total = getattr(self, "n_total", None) or n * self.dist.world
         self.rng_dev = torch.Generator(device=self.dev).manual_seed(int(c.seed))
+        if c.latents_path is not None and self._load_start_latents(n):
+            return
         if c.noise_mode.lower() == "same":        # prepare_latents(1, 4, H, W) repeated (generate.py:183-188)
             z = torch.randn(1, 4, self.h, self.w, generator=self.rng_dev, device=self.dev, dtype=torch.float32)
             self.init_noise = (z * self.scheduler.init_noise_sigma).to(H16).repeat(n, 1, 1, 1).contiguous()
@@ -103,6 +109,31 @@ class Generator:
             self.init_noise = (z[lo:hi] * self.scheduler.init_noise_sigma).to(H16).contiguous()
         else:
             raise NotImplementedError(f"Noise mode '{c.noise_mode}' is not supported.")
+
+    def _load_start_latents(self, n):
+        """generate.py:563-566, 191-194: start from the saved latents of the scheduler's first timestep when they exist (-> True); nothing is
+        drawn from the RNG then, as in the reference.  The file covers the video, `frame_ids` picks this run's frames, the rank takes its block."""
+        c = self.cfg
+        # the file is named after the first timestep, so prepare_data sets the scheduler's timesteps here (generate.py:561 does it before prepare_data
+        # too); ddim_sample sets them again, and set_timesteps depends on nothing but n_timesteps
+        self.scheduler.set_timesteps(c.n_timesteps)
+        t0 = self.scheduler.timesteps[0]
+        path = get_latents_dir(c.latents_path, c.model_key)
+        found = check_latent_exists(path, [t0])
+        print(f"[INFO] latent path {f'found at {path}' if found else 'not found, generating new latents.'}")
+        if not found:
+            return False
+        try:
+            z = load_latent(path, t0, c.frame_ids)
+        except IndexError as e:
+            raise ValueError(f"start latents under {path} do not cover frame_ids: {e}") from e
+        lo, hi = self.dist.range(self.n_total)
+        if not torch.is_tensor(z) or tuple(z.shape) != (self.n_total, 4, self.h, self.w):
+            raise ValueError(f"start latents under {path}: {tuple(z.shape) if torch.is_tensor(z) else type(z).__name__} after the frame selection, "
+                             f"expected {(self.n_total, 4, self.h, self.w)} = [frames, 4, H/8, W/8]")
+        self.init_noise = z[lo:hi].to(self.dev).to(H16).contiguous()
+        assert self.init_noise.shape[0] == n
+        return True
 
     # ------------------------------------------------------------------ one UNet evaluation with CFG
     def _groups(self, chunks, tokens_per_frame):

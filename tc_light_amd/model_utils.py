@@ -1,8 +1,8 @@
 """init_iclight (reference: utils/model_utils.py:12-94) for the MI355X engine.
 
 Loads the SD-1.5 UNet (HF safetensors keys), widens conv_in to 8 input channels with zero-initialised extra weights
-(:21-26), ADDS the IC-Light offset file to every tensor (:47-54, strict key match), loads the VAE, and builds the
-SDE-DPM-Solver++ scheduler (:71-78).
+(:21-26), ADDS the IC-Light offset file to every tensor (:47-54, strict key match), merges the LoRA of `generation.lora` on top when one is
+given (generate_utils.py:95-96; tc_light_amd/lora.py), loads the VAE, and builds the SDE-DPM-Solver++ scheduler (:71-78).
 
 A missing or mistyped weight path raises FileNotFoundError: the engine never silently relights with noise weights.  Seeded random
 tensors of the same architecture (bench / tests: no network, no checkpoints in the images) must be asked for explicitly with
@@ -38,12 +38,22 @@ def _load_safetensors(path):
     return load_file(path)
 
 
-def load_unet_state(unet_path=None, offset_path=None, seed=1, allow=False):
-    """utils/model_utils.py:14-54: SD-1.5 UNet state dict with the 8-channel conv_in and the IC-Light offsets added to EVERY key."""
+def _with_lora(sd, lora):
+    """generation.lora (generate_utils.py:95-96), merged last: the reference loads it into the pipe that already carries the offsets."""
+    if lora is None:
+        return sd
+    from . import lora as L
+    entries, weight = L.from_config(lora)
+    return L.merge_into(sd, entries, weight, part="unet")
+
+
+def load_unet_state(unet_path=None, offset_path=None, seed=1, allow=False, lora=None):
+    """utils/model_utils.py:14-54: SD-1.5 UNet state dict with the 8-channel conv_in and the IC-Light offsets added to EVERY key; then
+    `lora` (the generation.lora block or lora.LoRASet; None: nothing) merged in f32: base -> conv_in widening -> offsets -> LoRA."""
     shapes = sd15.unet_param_shapes()
     if not (unet_path and os.path.exists(unet_path)):
         _missing("SD-1.5 UNet", unet_path, allow)
-        return sd15.random_state_dict(shapes, seed)
+        return _with_lora(sd15.random_state_dict(shapes, seed), lora)
     sd = {k: v.float() for k, v in _load_safetensors(unet_path).items()}
     w = sd["conv_in.weight"]
     if w.shape[1] == 4:                                    # new_conv_in: zero weights for the 4 concat channels (:21-26)
@@ -64,7 +74,7 @@ def load_unet_state(unet_path=None, offset_path=None, seed=1, allow=False):
     bad = [k for k, s in shapes.items() if k not in sd or tuple(sd[k].shape) != tuple(s)]
     if bad:
         raise KeyError(f"UNet checkpoint mismatch on {bad[:3]}")
-    return sd
+    return _with_lora(sd, lora)
 
 
 def load_vae_state(path=None, seed=2, allow=False):
@@ -167,12 +177,12 @@ def load_rmbg_state(path=None, seed=3, allow=False):
     return {k: v for k, v in raw.items()}
 
 
-def init_iclight(device="cuda", models=None, seed=12345):
-    """-> (pipe-like namespace with .unet/.vae/.scheduler, scheduler, 'iclight')."""
+def init_iclight(device="cuda", models=None, seed=12345, lora=None):
+    """-> (pipe-like namespace with .unet/.vae/.scheduler, scheduler, 'iclight').  `lora`: see load_unet_state."""
     from types import SimpleNamespace
     m = models or {}
     ok = allow_random(m)
-    unet = UNetEngine(load_unet_state(m.get("unet"), m.get("iclight_offset"), allow=ok), device, VidToMe(device, seed=seed))
+    unet = UNetEngine(load_unet_state(m.get("unet"), m.get("iclight_offset"), allow=ok, lora=lora), device, VidToMe(device, seed=seed))
     vae = VAEEngine(load_vae_state(m.get("vae"), allow=ok), device)
     scheduler = DPMSolverSDEScheduler(num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012)
     return SimpleNamespace(unet=unet, vae=vae, scheduler=scheduler), scheduler, "iclight"

@@ -7,6 +7,8 @@ model_max_length-2 wrapped in BOS/EOS, padded with EOS to model_max_length -> la
 shorter side, concatenates the chunks along the sequence and returns cat([uncond, cond]) (generate.py:553-555).
 `load_text_encoder(dir)` loads CLIP ViT-L/14 with `transformers` from a local directory; a missing directory raises unless random
 stand-ins were explicitly allowed (model_utils.allow_random), in which case deterministic text-seeded embeddings of the right shape are used.
+A LoRA's text-encoder entries (`lora_te_...` / `text_encoder....`, tc_light_amd/lora.py) are merged into the local checkpoint's state dict in
+f32 before it is cast to f16; the stand-in embeddings have no weights to merge into, which is said once in a warning.
 """
 import hashlib
 import math
@@ -17,6 +19,7 @@ import numpy as np
 import torch
 
 _ENC = {}
+_WARNED_TE_LORA = False
 
 
 def encode_prompt_inner(txt, tokenizer, text_encoder, device):
@@ -50,11 +53,26 @@ def tile_and_concat(c, uc):
     return as_sequence(c), as_sequence(uc)
 
 
-def load_text_encoder(enc_dir, dev):
-    if enc_dir not in _ENC:
+def merge_text_lora(text_encoder, lora):
+    """The lora_te_ entries of `lora` (lora.LoRASet) merged into an HF-CLIP-shaped module's weights, f32 on the host."""
+    from . import lora as L
+    sd = {k: (v.detach().float().cpu() if v.is_floating_point() else v) for k, v in text_encoder.state_dict().items()}
+    text_encoder.load_state_dict(L.merge_into(sd, lora.entries, lora.weight, part="te"))
+    return text_encoder
+
+
+def load_text_encoder(enc_dir, dev, lora=None):
+    from . import lora as L
+    te_lora = lora if lora is not None and L.has_part(lora.entries, "te") else None
+    key = (enc_dir, te_lora is not None)
+    # the cache entry holds the LoRASet it was merged with (so the object stays alive and `is` cannot meet a recycled id); another set reloads
+    if key not in _ENC or _ENC[key][2] is not te_lora:
         from transformers import CLIPTextModel, CLIPTokenizer
-        _ENC[enc_dir] = (CLIPTokenizer.from_pretrained(enc_dir), CLIPTextModel.from_pretrained(enc_dir).to(dev).half().eval())
-    return _ENC[enc_dir]
+        enc = CLIPTextModel.from_pretrained(enc_dir)
+        if te_lora is not None:
+            enc = merge_text_lora(enc.float(), te_lora)
+        _ENC[key] = (CLIPTokenizer.from_pretrained(enc_dir), enc.to(dev).half().eval(), te_lora)
+    return _ENC[key][:2]
 
 
 def _n_chunks_proxy(txt):
@@ -67,10 +85,12 @@ def _stand_in(txt, dev):
     return torch.from_numpy(np.random.default_rng(seed).standard_normal((n, 77, 768)).astype(np.float32)).to(dev).half()
 
 
-def encode_prompt_pair(positive, negative, dev, enc_dir=None, allow_random=False, tokenizer=None, text_encoder=None):
-    """-> [2, L*k, 768] f16 = cat([uncond, cond]) (generate.py:553-555)."""
+def encode_prompt_pair(positive, negative, dev, enc_dir=None, allow_random=False, tokenizer=None, text_encoder=None, lora=None):
+    """-> [2, L*k, 768] f16 = cat([uncond, cond]) (generate.py:553-555).  `lora` (lora.LoRASet): its text-encoder entries are merged into
+    the checkpoint under `enc_dir`; a tokenizer / text_encoder handed in is used as it is."""
+    global _WARNED_TE_LORA
     if tokenizer is None and enc_dir and os.path.isdir(enc_dir):
-        tokenizer, text_encoder = load_text_encoder(enc_dir, dev)
+        tokenizer, text_encoder = load_text_encoder(enc_dir, dev, lora)
     if tokenizer is not None:
         c = encode_prompt_inner(positive, tokenizer, text_encoder, dev)
         uc = encode_prompt_inner(negative, tokenizer, text_encoder, dev)
@@ -79,6 +99,12 @@ def encode_prompt_pair(positive, negative, dev, enc_dir=None, allow_random=False
             raise FileNotFoundError(f"CLIP text encoder directory {enc_dir!r} not found (models.text_encoder); set models.allow_random / "
                                     "TCL_ALLOW_RANDOM_WEIGHTS=1 for deterministic stand-in embeddings")
         warnings.warn("CLIP text encoder not found -> deterministic text-seeded stand-in embeddings (allow_random)")
+        if lora is not None and not _WARNED_TE_LORA:
+            from . import lora as L
+            if L.has_part(lora.entries, "te"):
+                _WARNED_TE_LORA = True
+                warnings.warn("the LoRA carries text-encoder entries (lora_te_ / text_encoder.), but the stand-in embeddings have no text "
+                              "encoder to merge them into: they are not applied")
         c, uc = _stand_in(positive, dev), _stand_in(negative, dev)
     c, uc = tile_and_concat(c, uc)
     return torch.cat([uc, c]).to(torch.float16).contiguous()
