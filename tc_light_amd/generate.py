@@ -78,9 +78,8 @@ class Generator:
                 free = 288 << 30
                 if torch.cuda.is_available() and self.dev.type == "cuda":      # the driver's free bytes + what this process's caching allocator holds unused
                     free = torch.cuda.mem_get_info(self.dev)[0] + torch.cuda.memory_reserved(self.dev) - torch.cuda.memory_allocated(self.dev)
-                cap = self.unet.panel_cache_cap() if hasattr(self.unet, "panel_cache_cap") else 0     # persistent attention panels live beside the pass
-                cached = sum(a.numel() + b.numel() for a, b in getattr(self.unet, "_panel_cache", {}).values())
-                free -= max(0, cap - cached)
+                if hasattr(self.unet, "panel_cache_cap"):      # persistent attention panels live beside the pass (a stand-in engine keeps none)
+                    free -= max(0, self.unet.panel_cache_cap() - self.unet.panel_cache_bytes())
                 c.max_tokens_per_pass = int(min(16_000_000, max(1_000_000, 0.8 * free / 10_500)))
 
     # ------------------------------------------------------------------ data

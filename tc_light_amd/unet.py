@@ -6,8 +6,8 @@ Host-side mirror of what the reference assembles from diffusers + monkey-patchin
 Activations are NHWC f16 [B, H*W, C]; every op below is one C-ABI call (tc_light_amd/csrc/*.hip).  Python only
 sequences launches and owns buffers; there is no torch arithmetic on the data path.
 """
-import math
 import os
+from typing import NamedTuple
 
 import torch
 
@@ -31,6 +31,25 @@ def _geglu_rows(w):
 
 def _conv_w(w, dev):          # [Cout,Cin,3,3] -> [Cout, 9*Cin] tap-major
     return _dev(w.permute(0, 2, 3, 1).reshape(w.shape[0], -1), dev)
+
+
+class Switches(NamedTuple):
+    """The A/B switches of the UNet pass: every fused route below can be turned off to fall back to the general one it replaced (which the shapes
+    the fused kernels do not cover take anyway).  `forward_many` reads them once per pass and hands the record down."""
+    gn_concat: bool       # a ResNet block's norm1 also writes the raw [x | skip] concat its 1x1 shortcut reads (else: a concat pass)
+    ln_metric: bool       # norm1 of a merging block also writes VidToMe's matching metric y / |y| (else: the merge normalises the rows itself)
+    qkv_panel: bool       # attn1's QKV GEMM writes the attention panels itself, d = 40 / 80 (else: a [rows, 3C] tensor and a pack launch)
+    merge_lazy: bool      # ... and gathers the merged sequence in its operand load (else: the merge materialises it)
+    ln_gemm: bool         # C = 320: norm2 / norm3 ride in the operand load of to_q / the GEGLU Linear (else: a LayerNorm pass each)
+    qpanel: bool          # ... and norm2 -> to_q writes attn2's query panel directly, once the text K/V are packed (else: an [M, C] q and a pack pass)
+    tome_stream: bool     # the matching chain of the merging blocks runs on a side stream, ahead of the attention (else: in line on the main stream)
+    cfg_dedup: bool       # forward_many(cfg_pair=True) computes the text-free prefix of the two guidance halves once (else: both halves)
+
+    @classmethod
+    def from_env(cls):
+        """TCL_GN_CONCAT, TCL_LN_METRIC, TCL_QKV_PANEL, TCL_MERGE_LAZY, TCL_LN_GEMM, TCL_QPANEL, TCL_TOME_STREAM, TCL_CFG_DEDUP (TCL_ + the field's
+        name): on unless the variable is "0"."""
+        return cls(*(os.environ.get("TCL_" + f.upper(), "1") != "0" for f in cls._fields))
 
 
 GEMM_TABLE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "gemm_tune_gfx950.txt")
@@ -126,18 +145,21 @@ class Ops:
         self.L.tcl_ln_gemm_f16(x, gamma, beta, 1e-5, w, bias if bias is not None else 0, 0, c, M, N, K, K, K, c.shape[1], N, act, stream())
         return c
 
-    def attention(self, q, ldq, qbs, k, ldk, kbs, v, ldv, vbs, B, Hh, Tq, Tk, d, kv_div=1, ws_kv=None, pack_kv=True, pair=False, packed=None):
-        """packed: (ws_q, ws_kv) already filled by a panel-writing GEMM (tcl_gemm_qkv_panels_f16 / tcl_ln_gemm_qpanel_f16)."""
+    def attention(self, q, ldq, qbs, k, ldk, kbs, v, ldv, vbs, B, Hh, Tq, Tk, d, kv_div=1, ws_kv=None, pack_kv=True, pair=False):
+        """Strided operands: Q is packed into a fresh panel workspace, K / V into ws_kv (pack_kv=False: ws_kv already holds them packed)."""
         o = self.empty(B * Tq, Hh * d)
-        if packed is not None:
-            wq, ws_kv, flags = packed[0], packed[1], TCL_ATTN_PREPACKED
-        else:
-            wq = torch.empty(self.L.tcl_attention_q_bytes(B, Hh, Tq, d), dtype=torch.uint8, device=self.dev)
-            if ws_kv is None:
-                ws_kv = torch.empty(self.L.tcl_attention_kv_bytes(B // kv_div, Hh, Tk, d), dtype=torch.uint8, device=self.dev)
-            flags = TCL_ATTN_PACK_KV if pack_kv else 0
-        self.L.tcl_attention_f16(q, ldq, qbs, k if k is not None else 0, ldk, kbs, v if v is not None else 0, ldv, vbs, o, Hh * d,
-                                 Tq * Hh * d, B, Hh, Tq, Tk, d, d ** -0.5, kv_div, flags | (TCL_ATTN_PAIR if pair else 0), wq, ws_kv, stream())
+        wq = torch.empty(self.L.tcl_attention_q_bytes(B, Hh, Tq, d), dtype=torch.uint8, device=self.dev)
+        if ws_kv is None:
+            ws_kv = torch.empty(self.L.tcl_attention_kv_bytes(B // kv_div, Hh, Tk, d), dtype=torch.uint8, device=self.dev)
+        self.L.tcl_attention_f16(q, ldq, qbs, k, ldk, kbs, v, ldv, vbs, o, Hh * d, Tq * Hh * d, B, Hh, Tq, Tk, d, d ** -0.5, kv_div,
+                                 (TCL_ATTN_PACK_KV if pack_kv else 0) | (TCL_ATTN_PAIR if pair else 0), wq, ws_kv, stream())
+        return o
+
+    def attention_prepacked(self, wq, wkv, B, Hh, Tq, Tk, d, kv_div=1, pair=False, ldq=0, qbs=0):
+        """Panels already filled by tcl_gemm_qkv_panels_f16 / tcl_ln_gemm_qpanel_f16; ldq / qbs: strides of the Q tensor never written (the ABI takes them)."""
+        o = self.empty(B * Tq, Hh * d)
+        self.L.tcl_attention_f16(wq, ldq, qbs, 0, 0, 0, 0, 0, 0, o, Hh * d, Tq * Hh * d, B, Hh, Tq, Tk, d, d ** -0.5, kv_div,
+                                 TCL_ATTN_PREPACKED | (TCL_ATTN_PAIR if pair else 0), wq, wkv, stream())
         return o
 
 
@@ -204,6 +226,8 @@ class UNetEngine:
         w["conv_out"] = (_conv_w(sd["conv_out.weight"], d), _dev(sd["conv_out.bias"], d))
         self.w = w
         self._temb_cache = (None, None)
+        self._panel_cache, self._qpanels = {}, {}    # attn1's (Q, K / V^T) panels (`_attn_panels`, at most _panel_cap bytes), attn2's Q panels (`_q_panel`)
+        self._panel_cap = self._side = None          # set on first use: `panel_cache_cap`; the matching chain's stream (`_attn1_merged`)
         self.flops = 0.0          # algorithmic FLOPs (2*MACs) of the reference's computation, accumulated per forward for the roofline figure
         self.flops_executed = 0.0  # FLOPs that actually ran (== flops without the CFG-pair de-duplication)
         self.count_flops = False
@@ -226,38 +250,36 @@ class UNetEngine:
         return proj
 
     # ------------------------------------------------------------------ blocks
-    def _resblock(self, p, x, B, Hh, Ww, tproj, skip=None, cskip=0, rep=1):
+    def _resblock(self, p, x, B, Hh, Ww, tproj, sw, skip=None, cskip=0, rep=1):
         """rep: how many identical copies of these B samples the reference computes (FLOP accounting only)."""
         o, r = self.ops, self.res[p]
         HW = Hh * Ww
         cx = r["cin"] - cskip
-        fuse_cat = skip is not None and "sc" in r and os.environ.get("TCL_GN_CONCAT", "1") != "0"
+        fuse_cat = skip is not None and "sc" in r and sw.gn_concat
         hn = o.groupnorm(x, cx, *r["n1"], B, HW, 1e-5, True, x2=skip, c2=cskip, raw=fuse_cat)
         if fuse_cat:            # norm1's apply pass reads x and skip anyway: it writes the raw concat for the 1x1 shortcut as well (same bits as a concat pass)
             hn, xc = hn
         h1, _, _ = o.conv3x3(hn, B, Hh, Ww, r["cin"], r["c1"], tproj[p])
         hn2 = o.groupnorm(h1, r["cout"], *r["n2"], B, HW, 1e-5, True)
         if "sc" in r:
-            if fuse_cat:
-                pass
-            elif skip is not None:
+            if skip is None:
+                xc = x
+            elif not fuse_cat:
                 xc = o.empty(B * HW, r["cin"])
                 self.L.tcl_concat_channels_f16(x, cx, skip, cskip, xc, B * HW, stream())
-            else:
-                xc = x
             xs = o.gemm(xc, r["sc"][0], r["sc"][1])
-            self._fl(rep * 2.0 * B * HW * r["cin"] * r["cout"], 2.0 * B * HW * r["cin"] * r["cout"])
+            self._fl(2.0 * HW * r["cin"] * r["cout"], rep * B, B)
         else:
             xs = x
         out, _, _ = o.conv3x3(hn2, B, Hh, Ww, r["cout"], r["c2"], r["b2"], resid=xs)
-        self._fl(rep * 2.0 * B * HW * 9 * (r["cin"] + r["cout"]) * r["cout"], 2.0 * B * HW * 9 * (r["cin"] + r["cout"]) * r["cout"])
+        self._fl(2.0 * HW * 9 * (r["cin"] + r["cout"]) * r["cout"], rep * B, B)
         return out
 
-    def _fl(self, f, executed=None):
-        """f: algorithmic FLOPs of the reference's computation; executed: what ran here (less where the identical CFG halves are computed once)."""
+    def _fl(self, f, n=1, n_executed=None):
+        """f FLOPs per sample / row: n of them in the reference's computation, n_executed run here (fewer where the CFG halves run once); exact integers."""
         if self.count_flops:
-            self.flops += f
-            self.flops_executed += f if executed is None else executed
+            self.flops += f * n
+            self.flops_executed += f * (n if n_executed is None else n_executed)
 
     def _text_kv(self, blk, text):
         key = id(text)
@@ -275,7 +297,7 @@ class UNetEngine:
         """A zero-initialised query-panel workspace per shape, reused by every block (stream order serialises them): tcl_ln_gemm_qpanel_f16 writes the
         rows t < Tq of every (sample, head) panel and never touches the padding rows, which therefore stay zero."""
         key = (B, Hh, Tq, d)
-        cache = self.__dict__.setdefault("_qpanels", {})
+        cache = self._qpanels
         if key not in cache:
             if len(cache) > 4:
                 cache.clear()
@@ -283,24 +305,29 @@ class UNetEngine:
         return cache[key]
 
     def panel_cache_cap(self):
-        """Byte bound of the persistent attention-panel cache: 8 % of the device's memory, at most 24 GiB (the 288 GB part: 23 GiB; ADVICE r5: the cap
-        was a constant the token budget of Generator.__init__ did not know about -- that budget now subtracts this figure from `free`)."""
-        cap = getattr(self, "_panel_cap", None)
-        if cap is None:
+        """Byte bound of the persistent attention-panel cache: 8 % of the device's memory, at most 24 GiB; Generator.__init__'s token budget subtracts it."""
+        if self._panel_cap is None:
             total = torch.cuda.get_device_properties(self.dev).total_memory if self.dev.type == "cuda" and torch.cuda.is_available() else (288 << 30)
-            cap = self._panel_cap = int(min(24 << 30, 0.08 * total))
-        return cap
+            self._panel_cap = int(min(24 << 30, 0.08 * total))
+        return self._panel_cap
+
+    def panel_cache_bytes(self):
+        return sum(a.numel() + b.numel() for a, b in self._panel_cache.values())
+
+    def drop_panels(self):
+        self._panel_cache.clear()
+        self._qpanels.clear()
 
     def _attn_panels(self, ne, Hh, T, d):
         """Zero-initialised Q and K / V^T panel workspaces per (entries, heads, merged length, head_dim), reused by every chunk and block that meets the shape
         again (all on the main stream: stream order serialises writer and readers).  tcl_gemm_qkv_panels_f16 never writes the panels' padding, which therefore
         stays zero.  The merged lengths of a clip are a handful of values (chunk lengths 1..4 x which side of the global merge is src); the cache is bounded."""
         key = (ne, Hh, T, d)
-        cache = self.__dict__.setdefault("_panel_cache", {})
+        cache = self._panel_cache
         hit = cache.pop(key, None)
         if hit is None:
             nq, nkv = self.L.tcl_attention_q_bytes(ne, Hh, T, d), self.L.tcl_attention_kv_bytes(ne, Hh, T, d)
-            while cache and sum(a.numel() + b.numel() for a, b in cache.values()) + nq + nkv > self.panel_cache_cap():
+            while cache and self.panel_cache_bytes() + nq + nkv > self.panel_cache_cap():
                 cache.pop(next(iter(cache)))                      # oldest first (dict order = insertion / last use)
             try:
                 hit = (torch.zeros(nq, dtype=torch.uint8, device=self.dev), torch.zeros(nkv, dtype=torch.uint8, device=self.dev))
@@ -311,111 +338,96 @@ class UNetEngine:
         cache[key] = hit
         return hit
 
-    def _side_stream(self):
-        if getattr(self, "_side", None) is None:
-            self._side = torch.cuda.Stream(device=self.dev)
-        return self._side
+    def _attn1_plain(self, blk, h, n1, B, N, ne):
+        """attn1 of a level that does not merge (downsample > max_downsample): per-frame attention over all the samples present, in one launch."""
+        o, C, Hd, Bx = self.ops, blk["c"], sd15.HEADS, B // 2 * ne
+        qkv = o.gemm(n1, blk["qkv"])
+        a = o.attention(qkv, 3 * C, N * 3 * C, qkv[:, C:], 3 * C, N * 3 * C, qkv[:, 2 * C:], 3 * C, N * 3 * C, Bx, Hd, N, N, C // Hd, pair=ne == 1)
+        self._fl(2.0 * N * C * C * 4 + 4.0 * N * N * C, B, Bx)
+        return o.gemm(a, blk["o1"][0], blk["o1"][1], resid=h)
 
-    def _transformer(self, p, x, B, Fs, Hh, Ww, text, pair_half=False):
-        """x [B*N, C] with B = 2*sum(Fs) samples: the unconditional samples of all chunks (chunk order), then the conditional ones.
-        Everything is batched over the chunks except attn1 of the merging levels, which runs chunk by chunk in the reference order
-        because each chunk's merge uses -- and updates -- this block's global-token bank (patch.py:59-82).
-        pair_half: x holds only the FIRST half of the B samples (see forward_many: the two classifier-free-guidance halves are identical up to
-        the first text cross-attention); proj_in, norm1, the VidToMe merge and attn1 run on that half, the result is duplicated before attn2."""
-        o, L, blk = self.ops, self.L, self.tfm[p]
-        C, N, Hd = blk["c"], Hh * Ww, sd15.HEADS
-        d = C // Hd
-        ne = 1 if pair_half else 2                               # batch entries physically present through attn1
-        Bx = B // 2 * ne
-        M = Bx * N
-        Ftot = B // 2
-        hn = o.groupnorm(x, C, *blk["gn"], Bx, N, 1e-6, False)
-        h = o.gemm(hn, blk["pin"][0], blk["pin"][1])
-        self._fl(2.0 * B * N * C * C * 2, 2.0 * M * C * C * 2)
-        # ---- attn1 over VidToMe-merged tokens (patch.py:161-179)
-        merging = self.tome.merges(N) and os.environ.get("TCL_LN_METRIC", "1") != "0"
-        n1, m1 = o.layernorm(h, *blk["ln"][0], M, C, metric=True) if merging else (o.layernorm(h, *blk["ln"][0], M, C), None)
-        if not self.tome.merges(N):                             # downsample > max_downsample: per-frame attention
-            qkv = o.gemm(n1, blk["qkv"])
-            a = o.attention(qkv, 3 * C, N * 3 * C, qkv[:, C:], 3 * C, N * 3 * C, qkv[:, 2 * C:], 3 * C, N * 3 * C, Bx, Hd, N, N, d, pair=pair_half)
-            h = o.gemm(a, blk["o1"][0], blk["o1"][1], resid=h)
-            self._fl(2.0 * B * N * C * C * 4 + 4.0 * B * N * N * C, 2.0 * M * C * C * 4 + 4.0 * Bx * N * N * C)
+    def _attn1_merged(self, p, blk, h, n1, m1, Fs, N, ne, sw):
+        """attn1 over VidToMe-merged tokens, added into h chunk by chunk: each chunk's merge uses and updates this block's bank (patch.py:59-82, 161-179).
+        The matching chain runs on a side stream, ahead of the attention of the chunks already matched (single-chunk passes too: the banks stay in its pool)."""
+        C = blk["c"]
+        xbs = sum(Fs) * N * C                                   # a chunk's conditional rows sit xbs elements after its unconditional ones
+        qkv_panel = C // sd15.HEADS in (40, 80) and sw.qkv_panel
+        main = side = torch.cuda.current_stream()
+        if sw.tome_stream:
+            side = self._side = self._side or torch.cuda.Stream(device=self.dev)
+            side.wait_stream(main)                              # n1 is ready
+        off = 0
+        for ci, F in enumerate(Fs):
+            self.tome.select_chunk(ci)
+            with torch.cuda.stream(side):
+                merged, unm, T = self.tome.compute_merge(p, n1[off * N:], F, N, C, xbs=xbs, metric=m1[off * N:] if m1 is not None else None, ne=ne,
+                                                         lazy_merged=qkv_panel and sw.merge_lazy)
+            if sw.tome_stream:
+                main.wait_event(side.record_event())
+                for tns in (merged.block, merged.index, unm):
+                    if tns is not None:                         # allocated on the side stream's pool, read on the main stream
+                        tns.record_stream(main)
+            self._attend_chunk(blk, h[off * N:], xbs, merged, unm, T, F * N, ne, qkv_panel)
+            off += F
+        return h
+
+    def _attend_chunk(self, blk, h, xbs, merged, unm, T, FN, ne, qkv_panel):
+        o, C, Hd, d = self.ops, blk["c"], sd15.HEADS, blk["c"] // sd15.HEADS
+        if qkv_panel:
+            # the QKV GEMM writes the attention panels itself (gemm.hip QP epilogue) and gathers a lazily merged sequence in its operand load
+            wq, wkv = self._attn_panels(ne, Hd, T, d)
+            self.L.tcl_gemm_qkv_panels_f16(merged.block, merged.entry_stride, merged.index, blk["qkv"], ne, T, Hd, d, C, C, C, d ** -0.5, wq, wkv, stream())
+            a = o.attention_prepacked(wq, wkv, ne, Hd, T, T, d, pair=ne == 1, ldq=3 * C, qbs=T * 3 * C)
         else:
-            off, xbs = 0, Ftot * N * C                          # a chunk's conditional rows sit xbs elements after its unconditional ones
-            # The matching chain (bank order, dozens of small launches per chunk) runs on a side stream, ahead of the attention of the
-            # chunks already matched: only merge(c) -> merge(c+1) and merge(c) -> attention(c) are real dependencies, so the small
-            # kernels of chunk c+1 fill the tails of chunk c's QKV GEMM / flash launches instead of serialising with them.
-            qkv_panel = d in (40, 80) and os.environ.get("TCL_QKV_PANEL", "1") != "0"
+            qkv = o.gemm(merged.block, blk["qkv"], M=ne * T)
+            a = o.attention(qkv, 3 * C, T * 3 * C, qkv[:, C:], 3 * C, T * 3 * C, qkv[:, 2 * C:], 3 * C, T * 3 * C, ne, Hd, T, T, d, pair=ne == 1)
+        y = o.gemm(a, blk["o1"][0], blk["o1"][1], M=ne * T)
+        self.tome.unmerge_add(h, xbs, y, T, unm, FN, C, ne)
+        self._fl(2.0 * T * C * C * 4 + 4.0 * T * T * C, 2, ne)
 
-            def attend(F, off, merged, unm, T):
-                if qkv_panel:
-                    # the QKV projection writes the attention panels itself (gemm.hip QP epilogue): no [ne*T, 3C] tensor, no pack launch; a lazily merged
-                    # sequence (block, entry stride, merge map) is gathered by the GEMM's operand load
-                    wq, wkv = self._attn_panels(ne, Hd, T, d)
-                    src, sbs, idx = merged if isinstance(merged, tuple) else (merged, T * C, 0)
-                    L.tcl_gemm_qkv_panels_f16(src, sbs, idx, blk["qkv"], ne, T, Hd, d, C, C, C, d ** -0.5, wq, wkv, stream())
-                    a = o.attention(wq, 3 * C, T * 3 * C, None, 0, 0, None, 0, 0, ne, Hd, T, T, d, pair=pair_half, packed=(wq, wkv))
-                else:
-                    qkv = o.gemm(merged, blk["qkv"], M=ne * T)
-                    a = o.attention(qkv, 3 * C, T * 3 * C, qkv[:, C:], 3 * C, T * 3 * C, qkv[:, 2 * C:], 3 * C, T * 3 * C, ne, Hd, T, T, d, pair=pair_half)
-                y = o.gemm(a, blk["o1"][0], blk["o1"][1], M=ne * T)
-                self.tome.unmerge_add(h[off * N:], xbs, y, T, unm, F * N, C, ne)  # u_a(...) + x (patch.py:178-179)
-                self._fl(2.0 * 2 * T * C * C * 4 + 4.0 * 2 * T * T * C, 2.0 * ne * T * C * C * 4 + 4.0 * ne * T * T * C)
-
-            main = torch.cuda.current_stream()
-            # (Always on the side stream, single-chunk passes included: the banks then live in that stream's allocator pool for good.)
-            two = os.environ.get("TCL_TOME_STREAM", "1") != "0"
-            side = self._side_stream() if two else main
-            if two:
-                side.wait_stream(main)                          # n1 is ready
-
-            def hand_over(merged, unm, ev):
-                if two:
-                    main.wait_event(ev)
-                    for tns in ((merged[0], merged[2]) if isinstance(merged, tuple) else (merged,)) + (unm,):
-                        if tns is not None:                     # allocated on the side stream's pool, read on the main stream
-                            tns.record_stream(main)
-
-            for ci, F in enumerate(Fs):
-                self.tome.select_chunk(ci)
-                with torch.cuda.stream(side):
-                    merged, unm, T = self.tome.compute_merge(p, n1[off * N:], F, N, C, xbs=xbs, metric=m1[off * N:] if m1 is not None else None, ne=ne,
-                                                             lazy_merged=qkv_panel and os.environ.get("TCL_MERGE_LAZY", "1") != "0")     # merged [ne, T, C]
-                ev = None
-                if two:
-                    ev = torch.cuda.Event()
-                    ev.record(side)
-                hand_over(merged, unm, ev)
-                attend(F, off, merged, unm, T)
-                off += F
-            # (running the attention of alternate chunks on a second stream as well was measured: no further gain)
-        if pair_half:                                           # from here on the halves differ (text): both exist
-            h, x = torch.cat([h, h]), torch.cat([x, x])
-            M = B * N
-        F = Ftot
-        # ---- attn2: text cross-attention on the full tokens
-        fuse_ln = C == 320 and os.environ.get("TCL_LN_GEMM", "1") != "0"      # norm2 / norm3 ride in the consumer's operand load (strip-resident Linear)
+    def _attn2(self, blk, h, B, N, text, fuse_ln, qpanel):
+        """Text cross-attention on the full tokens; every sample of a guidance half shares that half's text K / V (kv_div)."""
+        o, C, Hd, d, M = self.ops, blk["c"], sd15.HEADS, blk["c"] // sd15.HEADS, B * N
         tk = self._text_kv(blk, text)
         Lt = tk["L"]
-        if fuse_ln and tk["packed"] and os.environ.get("TCL_QPANEL", "1") != "0":
+        if fuse_ln and qpanel and tk["packed"]:
             # norm2 -> to_q straight into the attention kernel's query panel (linstrip.hip Q-panel epilogue): no [M, C] output, no pack pass
             wq = self._q_panel(B, Hd, N, d)
-            L.tcl_ln_gemm_qpanel_f16(h, *blk["ln"][1], 1e-5, blk["q2"], M, Hd, d, N, C, C, d ** -0.5, wq, stream())
-            a = o.attention(wq, C, N * C, None, 0, 0, None, 0, 0, B, Hd, N, Lt, d, kv_div=F, packed=(wq, tk["ws"]))
+            self.L.tcl_ln_gemm_qpanel_f16(h, *blk["ln"][1], 1e-5, blk["q2"], M, Hd, d, N, C, C, d ** -0.5, wq, stream())
+            a = o.attention_prepacked(wq, tk["ws"], B, Hd, N, Lt, d, kv_div=B // 2, ldq=C, qbs=N * C)
         else:
             q = o.ln_gemm(h, *blk["ln"][1], blk["q2"]) if fuse_ln else o.gemm(o.layernorm(h, *blk["ln"][1], M, C), blk["q2"])
             a = o.attention(q, C, N * C, tk["kv"], 2 * C, Lt * 2 * C, tk["kv"][:, C:], 2 * C, Lt * 2 * C, B, Hd, N, Lt, d,
-                            kv_div=F, ws_kv=tk["ws"], pack_kv=not tk["packed"])
+                            kv_div=B // 2, ws_kv=tk["ws"], pack_kv=not tk["packed"])
         tk["packed"] = True
-        h = o.gemm(a, blk["o2"][0], blk["o2"][1], resid=h)
-        self._fl(2.0 * M * C * C * 2 + 4.0 * M * Lt * C)
-        # ---- GEGLU feed-forward
-        if fuse_ln:
-            f2 = o.ln_gemm(h, *blk["ln"][2], blk["ff1"][0], blk["ff1"][1], act=2)
-        else:
-            f2 = o.gemm(o.layernorm(h, *blk["ln"][2], M, C), blk["ff1"][0], blk["ff1"][1], act=2)   # Linear(C -> 8C) + GEGLU fused in the GEMM epilogue -> [M, 4C]
-        h = o.gemm(f2, blk["ff2"][0], blk["ff2"][1], resid=h)
-        self._fl(2.0 * M * C * C * 12)
+        self._fl(2.0 * C * C * 2 + 4.0 * Lt * C, M)
+        return o.gemm(a, blk["o2"][0], blk["o2"][1], resid=h)
+
+    def _feed_forward(self, blk, h, M, fuse_ln):
+        o, C = self.ops, blk["c"]                               # Linear(C -> 8C) + GEGLU fused in the GEMM epilogue -> [M, 4C], then Linear(4C -> C)
+        f2 = o.ln_gemm(h, *blk["ln"][2], *blk["ff1"], act=2) if fuse_ln else o.gemm(o.layernorm(h, *blk["ln"][2], M, C), *blk["ff1"], act=2)
+        self._fl(2.0 * C * C * 12, M)
+        return o.gemm(f2, blk["ff2"][0], blk["ff2"][1], resid=h)
+
+    def _transformer(self, p, x, B, Fs, Hh, Ww, text, sw, pair_half=False):
+        """x [B*N, C], B = 2*sum(Fs) samples: the unconditional ones of all chunks, then the conditional ones; only `_attn1_merged` goes chunk by chunk.
+        pair_half: x holds only the FIRST half of the B samples (see forward_many: the two classifier-free-guidance halves are identical up to
+        the first text cross-attention); proj_in, norm1, the VidToMe merge and attn1 run on that half, the result is duplicated before attn2."""
+        o, blk = self.ops, self.tfm[p]
+        C, N = blk["c"], Hh * Ww
+        ne = 1 if pair_half else 2                              # batch entries physically present through attn1
+        Bx = B // 2 * ne
+        hn = o.groupnorm(x, C, *blk["gn"], Bx, N, 1e-6, False)
+        h = o.gemm(hn, blk["pin"][0], blk["pin"][1])
+        self._fl(2.0 * N * C * C * 2, B, Bx)                    # proj_in and proj_out
+        merging = self.tome.merges(N)
+        n1, m1 = o.layernorm(h, *blk["ln"][0], Bx * N, C, metric=True) if merging and sw.ln_metric else (o.layernorm(h, *blk["ln"][0], Bx * N, C), None)
+        h = self._attn1_merged(p, blk, h, n1, m1, Fs, N, ne, sw) if merging else self._attn1_plain(blk, h, n1, B, N, ne)
+        if pair_half:                                           # from here on the halves differ (text): both exist
+            h, x = torch.cat([h, h]), torch.cat([x, x])
+        fuse_ln = C == 320 and sw.ln_gemm                       # norm2 / norm3 ride in the consumer's operand load (strip-resident Linear)
+        h = self._attn2(blk, h, B, N, text, fuse_ln, sw.qpanel)
+        h = self._feed_forward(blk, h, B * N, fuse_ln)
         return o.gemm(h, blk["pout"][0], blk["pout"][1], resid=x)
 
     # ------------------------------------------------------------------ forward
@@ -437,7 +449,8 @@ class UNetEngine:
         o, L, w = self.ops, self.L, self.w
         Ftot = sum(Fs)
         B = 2 * Ftot
-        half = bool(cfg_pair) and os.environ.get("TCL_CFG_DEDUP", "1") != "0"
+        sw = Switches.from_env()                                # per pass: callers flip switches between two passes of one engine
+        half = bool(cfg_pair) and sw.cfg_dedup
         Bh = Ftot if half else B                                # samples through the text-free prefix
         tproj = self._temb(t)
         self.tome.begin_step(Fs, (Hh, Ww))                      # every chunk's lock-step draws, in chunk order (patch.py:206-231)
@@ -445,17 +458,17 @@ class UNetEngine:
         L.tcl_im2col3x3_small_f16(x_in, col, Bh, Hh, Ww, w["conv_in"][2], 128, stream())
         h = o.gemm(col, w["conv_in"][0], w["conv_in"][1])
         del col
-        self._fl(2.0 * B * Hh * Ww * 72 * 320, 2.0 * Bh * Hh * Ww * 72 * 320)
+        self._fl(2.0 * Hh * Ww * 72 * 320, B, Bh)
         sizes = [(Hh, Ww)]
         skips = [(torch.cat([h, h]) if half else h, 320)]
         hh, ww, c = Hh, Ww, 320
         for i, co in enumerate(sd15.BLOCK_OUT):
             for j in range(2):
                 first = half and i == 0 and j == 0
-                h = self._resblock(f"down_blocks.{i}.resnets.{j}.", h, Bh if first else B, hh, ww, tproj, rep=2 if first else 1)
+                h = self._resblock(f"down_blocks.{i}.resnets.{j}.", h, Bh if first else B, hh, ww, tproj, sw, rep=2 if first else 1)
                 c = co
                 if i < 3:
-                    h = self._transformer(f"down_blocks.{i}.attentions.{j}.", h, B, Fs, hh, ww, text, pair_half=first)
+                    h = self._transformer(f"down_blocks.{i}.attentions.{j}.", h, B, Fs, hh, ww, text, sw, pair_half=first)
                 skips.append((h, c))
             if i < 3:
                 h, hh2, ww2 = o.conv3x3(h, B, hh, ww, c, *w[f"down{i}"], stride=2, pad=1)
@@ -463,17 +476,17 @@ class UNetEngine:
                 hh, ww = hh2, ww2
                 sizes.append((hh, ww))
                 skips.append((h, c))
-        h = self._resblock("mid_block.resnets.0.", h, B, hh, ww, tproj)
-        h = self._transformer("mid_block.attentions.0.", h, B, Fs, hh, ww, text)
-        h = self._resblock("mid_block.resnets.1.", h, B, hh, ww, tproj)
+        h = self._resblock("mid_block.resnets.0.", h, B, hh, ww, tproj, sw)
+        h = self._transformer("mid_block.attentions.0.", h, B, Fs, hh, ww, text, sw)
+        h = self._resblock("mid_block.resnets.1.", h, B, hh, ww, tproj, sw)
         level = 3
         for i, co in enumerate(sd15.BLOCK_OUT[::-1]):
             for j in range(3):
                 sk, cs = skips.pop()
-                h = self._resblock(f"up_blocks.{i}.resnets.{j}.", h, B, hh, ww, tproj, skip=sk, cskip=cs)
+                h = self._resblock(f"up_blocks.{i}.resnets.{j}.", h, B, hh, ww, tproj, sw, skip=sk, cskip=cs)
                 del sk
                 if i > 0:
-                    h = self._transformer(f"up_blocks.{i}.attentions.{j}.", h, B, Fs, hh, ww, text)
+                    h = self._transformer(f"up_blocks.{i}.attentions.{j}.", h, B, Fs, hh, ww, text, sw)
             if i < 3:
                 level -= 1
                 h, hh2, ww2 = o.conv3x3(h, B, hh, ww, co, *w[f"up{i}"], up=sizes[level])   # nearest upsample fused in the gather
@@ -482,7 +495,6 @@ class UNetEngine:
         hn = o.groupnorm(h, 320, *w["norm_out"], B, hh * ww, 1e-5, True)
         eps, _, _ = o.conv3x3(hn, B, hh, ww, 320, *w["conv_out"])
         self._fl(2.0 * B * hh * ww * 9 * 320 * 4)
-        self.tome.end_forward()
         return eps
 
     def forward_nhwc(self, x_in, F, Hh, Ww, t, text):

@@ -11,6 +11,7 @@ transformer block.  Differences, all deliberate and documented in DESIGN.md:
 """
 import math
 import os
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -19,6 +20,15 @@ from .lib import lib, stream
 
 H16 = torch.float16
 I32 = torch.int32
+
+
+class Merged(NamedTuple):
+    """The merged token sequence of one chunk, as compute_merge hands it to attn1: entry b's row t is row `index[t]` (row t when index is None) of
+    `block[b]`.  Materialised sequences are Merged(contiguous [ne, T, C], T*C, None); a lazily merged one leaves the gather by `index` to the
+    consumer's operand load (tcl_gemm_qkv_panels_f16)."""
+    block: torch.Tensor                 # [ne, Tcat, C] f16, possibly a strided view (a bank in its slot of the next chunk's [src | dst] block)
+    entry_stride: int                   # elements between batch entries
+    index: Optional[torch.Tensor]       # int32 [T] shared by the entries, or None: the rows are already in place
 
 
 class VidToMe:
@@ -69,6 +79,7 @@ class VidToMe:
     def begin_step(self, Fs, size):
         """One UNet pass over the chunks Fs (reference chunk order): draw each chunk's (randf per round, coin) in that order."""
         self.size = size
+        self._legacy_chain = os.environ.get("TCL_TOME_CAT", "0") != "0"       # gather -> cat -> normalise -> match instead of the carried-metric chain
         self._chunks = []
         for F in Fs:
             if self.draws is not None:
@@ -84,9 +95,6 @@ class VidToMe:
         self._cur = (self._chunks, i)
         self.F, self.randfs, self.coin = self._chunks[i]
         self.randf = self.randfs[0] if self.randfs else -1
-
-    def end_forward(self):
-        pass
 
     # ---- helpers
     def _positions(self, F, N, randf, unm_pre=0):
@@ -134,6 +142,13 @@ class VidToMe:
                                 off, n, out[b], stream())
         return out
 
+    def _merged(self, cat, T, mrg, Tm, C, ne, lazy):
+        if lazy:
+            return Merged(cat, T * C, mrg)
+        out = torch.empty(ne, Tm, C, dtype=H16, device=self.dev)
+        self._gather(cat, T * C, mrg, out, Tm * C, Tm, C, ne)
+        return Merged(out, Tm * C, None)
+
     def unmerge_add(self, h, bsh, y, T, unm, n, C, nb=2):
         """h[b][i] += y[b][unm[i]]: unmerge of attn1's output + residual (patch.py:178-179); unm None = identity."""
         L = self.L
@@ -179,8 +194,6 @@ class VidToMe:
                 L.tcl_tome_match_f16(mt, mbs, Bt, C, a_pos, na, b_pos, nb, r, mo, uo, self._ws, stream())
         return mrg, unm, na - r + nb
 
-
-    # ---- round 6: the chain without `cat` and without a second normalisation
     def _local_len(self, F, N):
         """Tokens a single-round chunk of F frames keeps after the local merge (merge.py:90: r = min(na, int(na * ratio)))."""
         if F <= 1:
@@ -189,7 +202,7 @@ class VidToMe:
         return na - min(na, int(na * self.args["local_merge_ratio"])) + N
 
     def _slots(self, coin, TL, Tb):
-        """(src_len, loff, boff) of the global match's [src | dst] block (patch.py:61-70)."""
+        """(src_len, loff, boff) of the global match's [src | dst] block: local tokens are src on a coin above global_rand, else the bank's (patch.py:61-70)."""
         return (TL, 0, TL) if coin > self.args["global_rand"] else (Tb, Tb, 0)
 
     def _next_block(self, ne, TL_bank, N, C):
@@ -205,6 +218,14 @@ class VidToMe:
         _, loff, boff = self._slots(coin_n, TLn, TL_bank)
         T = TLn + TL_bank
         return (torch.empty(ne, T, C, dtype=H16, device=self.dev), torch.empty(ne, T, C, dtype=H16, device=self.dev), TLn, loff, boff)
+
+    def _bank_slot(self, name, ne, TL, N, C):
+        """Where the bank this chunk leaves goes -> (tok, met) [ne, TL, C]: its slot of the next chunk's blocks (`_next_block`, kept in _home) or new buffers."""
+        nxt = self._next_block(ne, TL, N, C)
+        if nxt is None:
+            return torch.empty(ne, TL, C, dtype=H16, device=self.dev), torch.empty(ne, TL, C, dtype=H16, device=self.dev)
+        cat_n, catm_n, _, _, boff_n = self._home[name] = nxt
+        return cat_n[:, boff_n:boff_n + TL], catm_n[:, boff_n:boff_n + TL]
 
     def _compute_merge_carried(self, name, x, F, N, C, xbs, metric, ne, lazy_merged):
         """compute_merge for the shape every TC-Light configuration has (one local round, maps shared by the batch entries, global merge on), with the
@@ -231,19 +252,12 @@ class VidToMe:
             assert Tn == TL
         bank, bmet, home = self.banks.get(name), self._bank_met.get(name), self._home.pop(name, None)
         if bank is None:                                                        # patch.py:81-82: the first chunk seeds the bank with its local tokens
-            nxt = self._next_block(ne, TL, N, C)
-            if nxt is not None:
-                cat_n, catm_n, TLn, loff_n, boff_n = nxt
-                tok, met = cat_n[:, boff_n:boff_n + TL], catm_n[:, boff_n:boff_n + TL]
-                self._home[name] = (cat_n, catm_n, TLn, loff_n, boff_n)
-            else:
-                tok, met = torch.empty(ne, TL, C, dtype=H16, device=self.dev), torch.empty(ne, TL, C, dtype=H16, device=self.dev)
+            tok, met = self._bank_slot(name, ne, TL, N, C)
             L.tcl_gather_rows_pair_f16(x, xbs, mx, mbs, mrg1 if mrg1 is not None else 0, tok, tok.stride(0), met, met.stride(0), ne, TL, C, stream())
             self.banks[name], self._bank_met[name] = tok, met
             if self.trace is not None:
                 self.trace.append(dict(name=name, F=F, unm=unm1, gather=mrg1, mrg1=mrg1, T=TL))
-            merged = (tok, tok.stride(0), None) if lazy_merged else tok.contiguous()
-            return merged, unm1, TL
+            return (Merged(tok, tok.stride(0), None) if lazy_merged else Merged(tok.contiguous(), TL * C, None)), unm1, TL
         if bank.shape[0] != ne:
             raise RuntimeError(f"VidToMe bank of block {name!r} was seeded with {bank.shape[0]} batch entr{'y' if bank.shape[0] == 1 else 'ies'}, this call "
                                f"carries {ne}: call reset_global_tokens() when switching between forward_many(cfg_pair=True) and the two-entry paths")
@@ -263,20 +277,10 @@ class VidToMe:
         L.tcl_gather_rows_pair_f16(x, xbs, mx, mbs, mrg1 if mrg1 is not None else 0, cat[:, loff:], T * C, catm[:, loff:], T * C, ne, TL, C, stream())
         mrg2, unm2, Tm = self._match(None, T, C, self._range(0, src_len), src_len, self._range(src_len, T), T - src_len, a["global_merge_ratio"],
                                      tbs=T * C, affine=(src_len, 0, src_len), metric=catm, ne=ne)
-        if lazy_merged:
-            merged = (cat, T * C, mrg2)
-        else:
-            merged = torch.empty(ne, Tm, C, dtype=H16, device=self.dev)
-            self._gather(cat, T * C, mrg2, merged, Tm * C, Tm, C, ne)
+        merged = self._merged(cat, T, mrg2, Tm, C, ne, lazy_merged)
         unm = self._compose(unm2, unm1, loff, FN)                               # 2s-unmerge then the randframe unmerge (func_warper(u_ls[::-1]))
         bmap = self._compose(mrg2, unm2[loff:], 0, TL)                          # bank <- u(merged_tokens), local part (patch.py:80)
-        nxt = self._next_block(ne, TL, N, C)
-        if nxt is not None:
-            cat_n, catm_n, TLn, loff_n, boff_n = nxt
-            tok, met = cat_n[:, boff_n:boff_n + TL], catm_n[:, boff_n:boff_n + TL]
-            self._home[name] = (cat_n, catm_n, TLn, loff_n, boff_n)
-        else:
-            tok, met = torch.empty(ne, TL, C, dtype=H16, device=self.dev), torch.empty(ne, TL, C, dtype=H16, device=self.dev)
+        tok, met = self._bank_slot(name, ne, TL, N, C)
         L.tcl_gather_rows_pair_f16(cat, T * C, catm, T * C, bmap, tok, tok.stride(0), met, met.stride(0), ne, TL, C, stream())
         self.banks[name], self._bank_met[name] = tok, met
         if self.trace is not None:
@@ -290,24 +294,22 @@ class VidToMe:
             return False
         return int(math.ceil(math.sqrt((self.size[0] * self.size[1]) // N))) <= self.args["max_downsample"]
 
-    def compute_merge(self, name, x, F, N, C, _unused=None, xbs=None, metric=None, ne=2, lazy_merged=False):
+    def compute_merge(self, name, x, F, N, C, xbs=None, metric=None, ne=2, lazy_merged=False):
         """x: norm1 output of one chunk: the unconditional [F*N, C] rows at x, the conditional ones xbs elements further (default
         F*N*C: a contiguous [2F, N, C] == joined [2, F*N, C]); metric: x's cosine-normalised rows in the same layout if norm1 wrote them
         (unet.py: tcl_layernorm_metric_f16), else None.  ne = 1: x holds ONE entry because the caller knows the pair to be identical (the
         classifier-free-guidance pair before the first text cross-attention, unet.py): with equal scores in both entries the matching picks
         the first one (lowest concatenated dst index), i.e. exactly the single-entry matching -- same maps, merged tokens and bank [1, T, C].
         Returns None when this block is not merged, else
-        (merged [2,T,C], unm int32 [F*N] ([2, F*N] without align_batch) or None for identity, T).
-        lazy_merged=True (unet.py, round 5): where the merged sequence is a gather of the [local | bank] block by a map shared by the entries, it is NOT
-        materialised -- `merged` is then the tuple (block [ne, Tcat, C], Tcat*C, map int32 [T]) for a consumer that applies the map in its operand load
-        (tcl_gemm_qkv_panels_f16)."""
+        (Merged, unm int32 [F*N] ([2, F*N] without align_batch) or None for identity, T).
+        lazy_merged=True: a merged sequence that is a gather of the [local | bank] block by a map shared by the entries is NOT materialised (see Merged)."""
         a = self.args
         if not self.merges(N):
             return None
         L = self.L
         if xbs is None:
             xbs = F * N * C
-        if a["align_batch"] and a["merge_global"] and F <= a["target_stride"] and os.environ.get("TCL_TOME_CAT", "0") == "0":
+        if a["align_batch"] and a["merge_global"] and F <= a["target_stride"] and not self._legacy_chain:
             return self._compute_merge_carried(name, x, F, N, C, xbs, metric, ne, lazy_merged)
         self._home.pop(name, None)
         self._bank_met.pop(name, None)
@@ -339,32 +341,25 @@ class VidToMe:
                 local = torch.empty(2, N, C, dtype=H16, device=self.dev)
                 L.tcl_gather_rows_f16(x, xbs, 0, 0, 0, local, N * C, 2, N, C, stream())
         if not a["merge_global"]:
-            return local, unm1, TL
+            return Merged(local, TL * C, None), unm1, TL
         bank = self.banks.get(name)
         if bank is None:                                                        # patch.py:81-82: the first chunk seeds the bank
             self.banks[name] = local if F > 1 else local.clone()
             if self.trace is not None:
                 self.trace.append(dict(name=name, F=F, unm=unm1, gather=mrg1, mrg1=mrg1, T=TL))
-            return local, unm1, TL
+            return Merged(local, TL * C, None), unm1, TL
         if bank.shape[0] != ne:       # (a real exception: `python -O` strips asserts and a 2-entry gather would then read past a 1-entry bank)
             raise RuntimeError(f"VidToMe bank of block {name!r} was seeded with {bank.shape[0]} batch entr{'y' if bank.shape[0] == 1 else 'ies'}, this call "
                                f"carries {ne}: call reset_global_tokens() when switching between forward_many(cfg_pair=True) and the two-entry paths")
         Tb = bank.shape[1]
-        if self.coin > a["global_rand"]:                                        # patch.py:61-65: local tokens are src
-            src_len, loff, boff = TL, 0, TL
-        else:                                                                   # patch.py:66-70: bank tokens are src
-            src_len, loff, boff = Tb, Tb, 0
+        src_len, loff, boff = self._slots(self.coin, TL, Tb)
         T = TL + Tb
         cat = torch.empty(ne, T, C, dtype=H16, device=self.dev)
         L.tcl_gather_rows_f16(local, TL * C, 0, 0, 0, cat[:, loff:], T * C, ne, TL, C, stream())
         L.tcl_gather_rows_f16(bank, bank.stride(0), 0, 0, 0, cat[:, boff:], T * C, ne, Tb, C, stream())
         mrg2, unm2, Tm = self._match(cat, T, C, self._range(0, src_len), src_len, self._range(src_len, T), T - src_len,
                                      a["global_merge_ratio"], affine=(src_len, 0, src_len), ne=ne)
-        if lazy_merged and mrg2.dim() == 1:
-            merged = (cat, T * C, mrg2)
-        else:
-            merged = torch.empty(ne, Tm, C, dtype=H16, device=self.dev)
-            self._gather(cat, T * C, mrg2, merged, Tm * C, Tm, C, ne)
+        merged = self._merged(cat, T, mrg2, Tm, C, ne, lazy_merged and mrg2.dim() == 1)
         unm = self._compose(unm2, unm1, loff, F * N)                            # 2s-unmerge then the randframe unmerges (func_warper(u_ls[::-1]))
         bmap = self._compose(mrg2, unm2[..., loff:].contiguous() if unm2.dim() == 2 else unm2[loff:], 0, TL)     # bank <- u(merged_tokens) (patch.py:80)
         nb_ = torch.empty(ne, TL, C, dtype=H16, device=self.dev)

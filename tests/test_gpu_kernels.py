@@ -232,6 +232,8 @@ def test_vidtome_maps_vs_oracle(L):
         tome.begin_forward(F, (15, 23))
         tome.trace = []
         merged, unm, T = tome.compute_merge("blk", x.cuda(), F, N, C)
+        assert merged.index is None and merged.entry_stride == T * C and merged.block.is_contiguous()
+        merged = merged.block
         r = OV.compute_merge(x.float(), F, bank, randf, coin, emulate_f16=True)
         assert T == r["merged"].shape[1]
         um = unm.cpu().long() if unm is not None else torch.arange(F * N)
@@ -294,10 +296,10 @@ def test_vidtome_carried_metric_chain_equals_legacy_chain(L):
                         met = torch.empty_like(xin)
                         L.tcl_tome_normalize_f16(xin, met, xin.shape[0] * N, C, st())
                     merged, unm, T = tome.compute_merge("blk", xin, F, N, C, metric=met, ne=ne, lazy_merged=lazy)
-                    if isinstance(merged, tuple):
-                        src, sbs, idx = merged
-                        rows = torch.stack([torch.as_strided(src, (T if idx is None else src.shape[1], C), (C, 1), src.storage_offset() + b * sbs) for b in range(ne)])
-                        merged = rows if idx is None else rows[:, idx.long()]
+                    src, sbs, idx = merged
+                    assert lazy or (idx is None and src.is_contiguous() and src.shape == (ne, T, C) and sbs == T * C)
+                    rows = torch.stack([torch.as_strided(src, (T if idx is None else src.shape[1], C), (C, 1), src.storage_offset() + b * sbs) for b in range(ne)])
+                    merged = rows if idx is None else rows[:, idx.long()]
                     outs.append((merged.clone(), None if unm is None else unm.clone(), T, tome.banks["blk"].clone()))
             torch.cuda.synchronize()
             return outs, tome.trace
@@ -344,6 +346,8 @@ def test_vidtome_multi_round_and_per_sample_vs_oracle(L):
             tome.draws = [(randfs, coin)]
             tome.begin_forward(F, (10, 15))
             merged, unm, T = tome.compute_merge("blk", x.cuda(), F, N, C)
+            assert merged.index is None and merged.entry_stride == T * C and merged.block.is_contiguous()
+            merged = merged.block
             r = OV.compute_merge(x.float(), F, bank, randfs, coin, emulate_f16=True, align_batch=aligned)
             assert T == r["merged"].shape[1], (F, T, r["merged"].shape)
             assert r["rounds"] == len(randfs)

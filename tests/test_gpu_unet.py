@@ -268,10 +268,10 @@ def test_persistent_attention_panels_stay_clean(setup):
     tome = VidToMe("cuda", seed=5)
     eng = UNetEngine(sd, "cuda", tome)
     run(eng, tome, *A, xa)                                 # fills the panel caches with A's (larger-valued, differently sized) sequences
-    n_cached = len(eng.__dict__.get("_panel_cache", {})) + len(eng.__dict__.get("_qpanels", {}))
+    n_cached = len(eng._panel_cache) + len(eng._qpanels)
     assert n_cached > 0
     used = run(eng, tome, *B, xb)                          # ... B on the used panels
-    eng.__dict__.pop("_panel_cache", None); eng.__dict__.pop("_qpanels", None)
+    eng.drop_panels()
     fresh = run(eng, tome, *B, xb)                         # ... and on freshly zeroed ones
     torch.cuda.synchronize()
     assert torch.isfinite(fresh.float()).all() and torch.equal(used, fresh)

@@ -84,3 +84,33 @@ def test_run_groups_one_pass_per_group():
     pack = lambda grp: (None, None, sum(len(c) for c in grp))
     Generator._run_groups(gen, [chunks], 8, 8, 1.0, None, pack, lambda *a: None)
     assert calls == [("one", [3, 16, 16, 5])]
+
+
+UNET_SWITCHES = dict(gn_concat="TCL_GN_CONCAT", ln_metric="TCL_LN_METRIC", qkv_panel="TCL_QKV_PANEL", merge_lazy="TCL_MERGE_LAZY", ln_gemm="TCL_LN_GEMM",
+                     qpanel="TCL_QPANEL", tome_stream="TCL_TOME_STREAM", cfg_dedup="TCL_CFG_DEDUP")
+
+
+def test_unet_switches_from_env(monkeypatch):
+    """Names, defaults and the `!= "0"` rule of the eight UNet switches: on by default, "0" turns exactly its own field off, "1" is the same as unset."""
+    from tc_light_amd.unet import Switches
+    assert Switches._fields == tuple(UNET_SWITCHES)
+    for var in UNET_SWITCHES.values():
+        monkeypatch.delenv(var, raising=False)
+    default = Switches.from_env()
+    assert default == Switches(*[True] * 8)
+    for field, var in UNET_SWITCHES.items():
+        monkeypatch.setenv(var, "0")
+        assert Switches.from_env() == default._replace(**{field: False}), var
+        monkeypatch.setenv(var, "1")
+        assert Switches.from_env() == default, var
+        monkeypatch.delenv(var)
+
+
+def test_environment_is_read_in_the_stated_places_only():
+    """The UNet pass reads its switches once, at its top: `os.environ` appears in unet.py only in Switches.from_env and load_gemm_table, in vidtome.py
+    only in VidToMe.begin_step -- never in the code that runs per block or per chunk."""
+    import inspect
+    from tc_light_amd import unet, vidtome
+    for mod, fns in ((unet, (unet.Switches.from_env.__func__, unet.load_gemm_table)), (vidtome, (vidtome.VidToMe.begin_step,))):
+        inside = [inspect.getsource(f).count("os.environ") for f in fns]
+        assert all(n > 0 for n in inside) and inspect.getsource(mod).count("os.environ") == sum(inside), (mod.__name__, inside)
