@@ -206,6 +206,19 @@ int tcl_adain_fuse_f16(void* noises_t, void* noises, int planes, int hw, float a
  * x <- ca*x + cb0*m0 + cb1*m1 + cc*z (coefficients from tc_light_amd/scheduler.py; f32 math; m1/z may be NULL). */
 int tcl_dpm_sde_step_f16(void* x, const void* eps, float* m0, const float* m1, const void* z, long n, float sigma_t, float alpha_t, float ca,
                          float cb0, float cb1, float cc, hipStream_t st);
+/* DDIM inversion of the IC-Light UNet (invert.py:151-244; tc_light_amd/invert.py).  The master latents x [N,4,h,w] stay f32 on the device; slot j of a
+ * group serves frame idx[j] (F physical slots: both halves of the pair batch, an odd group's duplicate included).  A slot whose idx is outside [0, N) is
+ * skipped.  h, w <= 0, F <= 0, N <= 0 and null pointers return TCL_EINVAL.
+ * tcl_invert_pack_f16 (replaces `torch.cat([x, concat_conds], dim=1)` of model_utils.py:35-40 and the NCHW -> NHWC cast): out [F,h,w,8] f16 NHWC,
+ * channels 0-3 = f16(x[idx[j]]), channels 4-7 = cond[idx[j]] (cond [N,4,h,w] f16). */
+int tcl_invert_pack_f16(const float* x, const void* cond, const int* idx, int N, int F, int h, int w, void* out, hipStream_t st);
+/* tcl_ddim_step_f32 (replaces pred_next_x, invert.py:215-244): eps [F,h,w,4] f16 NHWC as the UNet returns it; the first F_valid slots are applied
+ * (0 < F_valid <= F; their idx entries are distinct).  mu = sqrt(alpha_t), sigma = sqrt(1 - alpha_t), *_prev the same of alpha_t_prev (host, f64 -> f32;
+ * mu, mu_prev > 0).  In f32, no fma contraction, IEEE division:  x0 = (x - s_a*eps) / m_a;  x = m_b*x0 + s_b*eps  with (a, b) = (prev, t) when
+ * `inversion` and (t, prev) otherwise (invert.py:237-242).  x is updated in place and f16(x) goes into channels 0-3 of record j of xin [F,h,w,8] f16
+ * (the UNet input tcl_invert_pack_f16 wrote; channels 4-7 are left alone), so the next step needs no repack. */
+int tcl_ddim_step_f32(float* x, const void* eps, const int* idx, int N, int F, int F_valid, int h, int w, float mu, float sigma, float mu_prev,
+                      float sigma_prev, int inversion, void* xin, hipStream_t st);
 /* layout conversions around the VAE (generate_utils.py:140-172): 2*img-1 -> NHWC8 f16; clamp(y/2+0.5) -> [B,3,H,W] f32.
  * ldc = row stride in halves, >= the channels read or written (tcl_nchw_to_nhwc_f16 zeroes columns C..ldc-1); empty batches and narrower strides
  * return TCL_EINVAL.  tcl_transpose_f16: in [batch,R,ldi] -> out [batch,Cc,ldo], ldi >= Cc, ldo >= R, padding columns of out are left untouched. */

@@ -1,9 +1,10 @@
 // HBM-bound f16 kernels of path 1 (gfx950): GroupNorm(+SiLU), LayerNorm, GEGLU, row softmax, channel concat,
 // small-Cin im2col, GEMV (time embedding), latent pack/unpack with classifier-free guidance, AdaIN + noise fusion,
-// SDE-DPM-Solver++ update, image<->latent layout conversion.  All loads/stores are 16 B per lane (8 halves).
+// SDE-DPM-Solver++ update, DDIM inversion pack / step (f32 master latents), image<->latent layout conversion.  All loads/stores are 16 B per lane (8 halves)
+// unless a kernel says otherwise.
 // Reference call sites: UNet/VAE norms via diffusers (generate.py:342-347); pred_noise generate.py:288-352;
 // temporal_denoise :241-284; adaptive_instance_normalization utils/general_utils.py:137-156;
-// scheduler.step generate.py:235; encode/decode_latents utils/VidToMe/generate_utils.py:140-172.
+// scheduler.step generate.py:235; encode/decode_latents utils/VidToMe/generate_utils.py:140-172; Inverter.pred_next_x invert.py:215-244.
 #include "common.h"
 #include "../../include/tclight_hip.h"
 #include <unordered_map>
@@ -435,6 +436,56 @@ __global__ void k_dpm_step(_Float16* __restrict__ x, const _Float16* __restrict_
     }
 }
 
+// ------------------------------------------------------------------------------------------ DDIM inversion (invert.py:151-244)
+// One lane per pixel of one slot: slot j serves frame idx[j]; a slot whose frame id is outside [0, N) is skipped (nothing read or written).
+typedef _Float16 h4 __attribute__((ext_vector_type(4)));
+
+// master x [N,4,hw] f32, cond [N,4,hw] f16 -> out [F,hw,8] f16: channels 0-3 = f16(x), 4-7 = cond
+__global__ void k_invert_pack(const float* __restrict__ x, const _Float16* __restrict__ cond, const int* __restrict__ idx, int N, int F, long hw,
+                              _Float16* __restrict__ out) {
+    const long total = (long)F * hw;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const long j = i / hw, p = i - j * hw;
+        const int n = idx[j];
+        if (n < 0 || n >= N) continue;
+        h8 v;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const long src = ((long)n * 4 + c) * hw + p;
+            v[c] = (_Float16)x[src]; v[4 + c] = cond[src];
+        }
+        *(h8*)(out + i * 8) = v;
+    }
+}
+
+// pred_next_x (invert.py:237-242) on the f32 master planes of the first F_valid slots, in place:
+//   x0 = (x - s_a*eps) / m_a ; x = m_b*x0 + s_b*eps        every product, difference, quotient and sum rounded to f32 on its own
+// and f16(x) into channels 0-3 of the slot's UNet input record (channels 4-7 stay as k_invert_pack wrote them).
+__global__ void k_ddim_step(float* __restrict__ x, const _Float16* __restrict__ eps, const int* __restrict__ idx, int N, int F_valid, long hw,
+                            float s_a, float m_a, float m_b, float s_b, _Float16* __restrict__ xin) {
+#pragma clang fp contract(off)
+    const long total = (long)F_valid * hw;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const long j = i / hw, p = i - j * hw;
+        const int n = idx[j];
+        if (n < 0 || n >= N) continue;
+        const h4 e = *(const h4*)(eps + i * 4);
+        h4 o;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            float* px = x + ((long)n * 4 + c) * hw + p;
+            const float ev = (float)e[c];
+            const float se = s_a * ev;
+            const float x0 = (*px - se) / m_a;
+            const float a = m_b * x0, b = s_b * ev;
+            const float xn = a + b;
+            *px = xn;
+            o[c] = (_Float16)xn;
+        }
+        *(h4*)(xin + i * 8) = o;
+    }
+}
+
 // ------------------------------------------------------------------------------------------ image <-> NHWC f16
 // img [B,3,H,W] f32 in [0,1] -> out [B,H,W,8] f16 = 2*img-1 (channels 3..7 zero: K padding for the im2col conv)
 __global__ void k_img_to_nhwc(const float* __restrict__ img, _Float16* __restrict__ out, int B, int HW) {
@@ -606,6 +657,22 @@ int tcl_dpm_sde_step_f16(void* x, const void* eps, float* m0, const float* m1, c
                          float cb0, float cb1, float cc, hipStream_t st) {
     TCL_CHECK_ARG(x && eps && m0 && n > 0);
     hipLaunchKernelGGL(k_dpm_step, dim3(stream_grid(n, 256, 2)), dim3(256), 0, st, (_Float16*)x, (const _Float16*)eps, m0, m1, (const _Float16*)z, n, sigma_t, alpha_t, ca, cb0, cb1, cc);
+    TCL_LAUNCH_RET();
+}
+int tcl_invert_pack_f16(const float* x, const void* cond, const int* idx, int N, int F, int h, int w, void* out, hipStream_t st) {
+    TCL_CHECK_ARG(x && cond && idx && out && N > 0 && F > 0 && h > 0 && w > 0);
+    const long hw = (long)h * w;
+    hipLaunchKernelGGL(k_invert_pack, dim3(stream_grid((long)F * hw, 256, 1)), dim3(256), 0, st, x, (const _Float16*)cond, idx, N, F, hw, (_Float16*)out);
+    TCL_LAUNCH_RET();
+}
+int tcl_ddim_step_f32(float* x, const void* eps, const int* idx, int N, int F, int F_valid, int h, int w, float mu, float sigma, float mu_prev,
+                      float sigma_prev, int inversion, void* xin, hipStream_t st) {
+    TCL_CHECK_ARG(x && eps && idx && xin && N > 0 && F > 0 && F_valid > 0 && F_valid <= F && h > 0 && w > 0 && mu > 0.f && mu_prev > 0.f);
+    const long hw = (long)h * w;
+    // (a, b) = (prev, t) stepping up the noise levels, (t, prev) stepping down
+    const float s_a = inversion ? sigma_prev : sigma, m_a = inversion ? mu_prev : mu, m_b = inversion ? mu : mu_prev, s_b = inversion ? sigma : sigma_prev;
+    hipLaunchKernelGGL(k_ddim_step, dim3(stream_grid((long)F_valid * hw, 256, 1)), dim3(256), 0, st, x, (const _Float16*)eps, idx, N, F_valid, hw,
+                       s_a, m_a, m_b, s_b, (_Float16*)xin);
     TCL_LAUNCH_RET();
 }
 int tcl_img_to_nhwc8_f16(const float* img, void* out, int B, int HW, hipStream_t st) {

@@ -53,6 +53,19 @@ DEFAULTS = dict(  # configs/tclight_default.yaml (generation / post_opt sections
     #   the in-call tuner -- the 4.5 M line of that file).  tests/test_gpu_fullsize.py pins pass-size invariance (same bits) beyond 2^31 elements.
 
 
+def default_max_tokens_per_pass(unet, dev):
+    """max_tokens_per_pass when the configuration leaves it open (see DEFAULTS): TCL_MAX_TOKENS_PER_PASS, else what the device's free memory carries."""
+    env = os.environ.get("TCL_MAX_TOKENS_PER_PASS")
+    if env:
+        return int(env)
+    free = 288 << 30
+    if torch.cuda.is_available() and dev.type == "cuda":      # the driver's free bytes + what this process's caching allocator holds unused
+        free = torch.cuda.mem_get_info(dev)[0] + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
+    if hasattr(unet, "panel_cache_cap"):      # persistent attention panels live beside the pass (a stand-in engine keeps none)
+        free -= max(0, unet.panel_cache_cap() - unet.panel_cache_bytes())
+    return int(min(16_000_000, max(1_000_000, 0.8 * free / 10_500)))
+
+
 class Generator:
     def __init__(self, unet, vae, config=None, dist=None, scheduler=None, rmbg=None):
         cfg = dict(DEFAULTS)
@@ -71,16 +84,7 @@ class Generator:
         self.batch_size = 2
         self.timing = {}
         if c.max_tokens_per_pass is None:
-            env = os.environ.get("TCL_MAX_TOKENS_PER_PASS")
-            if env:
-                c.max_tokens_per_pass = int(env)
-            else:
-                free = 288 << 30
-                if torch.cuda.is_available() and self.dev.type == "cuda":      # the driver's free bytes + what this process's caching allocator holds unused
-                    free = torch.cuda.mem_get_info(self.dev)[0] + torch.cuda.memory_reserved(self.dev) - torch.cuda.memory_allocated(self.dev)
-                if hasattr(self.unet, "panel_cache_cap"):      # persistent attention panels live beside the pass (a stand-in engine keeps none)
-                    free -= max(0, self.unet.panel_cache_cap() - self.unet.panel_cache_bytes())
-                c.max_tokens_per_pass = int(min(16_000_000, max(1_000_000, 0.8 * free / 10_500)))
+            c.max_tokens_per_pass = default_max_tokens_per_pass(self.unet, self.dev)
 
     # ------------------------------------------------------------------ data
     def prepare_data(self, frames, background=None):
