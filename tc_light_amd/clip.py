@@ -17,6 +17,11 @@ preprocessing of transformers' image processor, whose centre crop is floored whe
 
 State dicts use OpenAI's key names.  `from_hf_state` / `to_hf_state` map to and from `transformers.CLIPModel`'s names (q / k / v concatenated into
 in_proj, the projections transposed).  Pinned against `transformers.CLIPModel` in f32 by tests/golden/clip.npz (tests/test_gpu_clip.py).
+
+`CLIPTextEngine` is the text tower alone, read at every position (ln_final on all rows, no projection): `transformers.CLIPTextModel`'s
+last_hidden_state, the prompt embeddings of SD-1.5 (`SD15_TEXT`, the text tower of CLIP ViT-L/14; tc_light_amd/text.py).  It shares the block sequence
+with CLIPEngine (`_Blocks`); `from_hf_text_state` / `to_hf_text_state` map a text_encoder checkpoint, `text_options` reads its config.json.  Pinned by
+tests/golden/text.npz (tests/test_gpu_text.py).
 """
 import hashlib
 import math
@@ -36,7 +41,9 @@ SOT, EOT = 49406, 49407                                                  # <|sta
 # nine entries are clip_param_shapes' arguments (arch_shapes); the rest is what a transformers checkpoint keeps in config.json, not in its tensors.
 PICKSCORE_V1 = dict(embed_dim=1024, image_resolution=224, vision_layers=32, vision_width=1280, vision_patch_size=14, context_length=77,
                     vocab_size=49408, transformer_width=1024, transformer_layers=24, vision_heads=16, text_heads=16, act="gelu", eps=1e-5)
-ACTS = {"quick_gelu": 0, "gelu": 4}                                      # -> tcl_gemm_f16's act of c_fc (QuickGELU is a pass of its own)
+# SD-1.5's text_encoder: the text tower of CLIP ViT-L/14, read at last_hidden_state (CLIPTextEngine; text_param_shapes takes the first four entries)
+SD15_TEXT = dict(width=768, layers=12, context_length=77, vocab_size=49408, heads=12, act="quick_gelu", eps=1e-5)
+ACTS = {"quick_gelu": 0, "gelu": 4}                                     # -> tcl_gemm_f16's act of c_fc (QuickGELU is a pass of its own)
 CROPS = {"round": 0, "floor": 1}                                         # -> the crop rule of tcl_clip_preprocess_ld_u8
 
 
@@ -79,13 +86,7 @@ def arch_shapes(arch):
     return {k: arch[k] for k in VIT_B32 if k in arch}
 
 
-def seeded_state_dict(seed=6, **arch):
-    """Seeded stand-in weights of the architecture (default ViT-B/32), scaled so that the features depend on the input -- with the usual small
-    initialisation the class token barely hears the patches and every image gets almost the same feature.  Linears are N(0, g^2 / fan_in) with
-    g = 1 for in_proj (attention logits of about one unit: the softmax selects) and the MLP's c_fc, and 0.7 for the two output projections of a
-    block; LayerNorm weights 1 +- 0.1, biases +- 0.1; embeddings N(0, 1) (class / positional at 0.3); the columns of the two final projections
-    decay as 0.75^j, so a feature lives mostly in a few directions and cosines between features of unrelated inputs spread over [-1, 1]."""
-    shapes = clip_param_shapes(**arch)
+def _seeded(shapes, seed):
     g = torch.Generator().manual_seed(seed)
     sd = {}
     for k, s in shapes.items():
@@ -113,6 +114,30 @@ def seeded_state_dict(seed=6, **arch):
             v = r
         sd[k] = v.contiguous()
     return sd
+
+
+def seeded_state_dict(seed=6, **arch):
+    """Seeded stand-in weights of the architecture (default ViT-B/32), scaled so that the features depend on the input -- with the usual small
+    initialisation the class token barely hears the patches and every image gets almost the same feature.  Linears are N(0, g^2 / fan_in) with
+    g = 1 for in_proj (attention logits of about one unit: the softmax selects) and the MLP's c_fc, and 0.7 for the two output projections of a
+    block; LayerNorm weights 1 +- 0.1, biases +- 0.1; embeddings N(0, 1) (class / positional at 0.3); the columns of the two final projections
+    decay as 0.75^j, so a feature lives mostly in a few directions and cosines between features of unrelated inputs spread over [-1, 1]."""
+    return _seeded(clip_param_shapes(**arch), seed)
+
+
+def text_param_shapes(width=768, layers=12, context_length=77, vocab_size=49408):
+    """State-dict keys and shapes of a text tower alone, as CLIPTextEngine takes it (the defaults are SD15_TEXT): no text_projection, no visual.*."""
+    sh = {"token_embedding.weight": (vocab_size, width), "positional_embedding": (context_length, width)}
+    for i in range(layers):
+        _block_shapes(sh, f"transformer.resblocks.{i}.", width)
+    sh["ln_final.weight"] = (width,); sh["ln_final.bias"] = (width,)
+    return sh
+
+
+def seeded_text_state_dict(seed=8, **arch):
+    """seeded_state_dict's recipe on the keys of text_param_shapes.  `arch` is an architecture dictionary such as SD15_TEXT; the entries that are not
+    shapes (heads, act, eps) are CLIPTextEngine's business and are ignored here."""
+    return _seeded(text_param_shapes(**{k: v for k, v in arch.items() if k in ("width", "layers", "context_length", "vocab_size")}), seed)
 
 
 _HF_BLOCK = (("ln_1.", "layer_norm1."), ("ln_2.", "layer_norm2."), ("attn.out_proj.", "self_attn.out_proj."), ("mlp.c_fc.", "mlp.fc1."),
@@ -164,6 +189,50 @@ def from_hf_state(sd, consume=False):
                 out[a + "attn.in_proj_" + kind] = torch.cat([take(h + f"self_attn.{n}_proj." + kind) for n in "qkv"]).contiguous()
                 for x, y in _HF_BLOCK:
                     out[a + x + kind] = take(h + y + kind)
+    return out
+
+
+_HF_TEXT_TOP = tuple((oa, hf) for oa, hf in _HF_TOP if hf.startswith("text_model."))
+_HF_TEXT = "text_model."
+
+
+def with_text_prefix(sd):
+    """A `transformers.CLIPTextModel` state dict in the `text_model.`-prefixed spelling: checkpoints on disk carry the prefix, the state dict of a
+    recent transformers' CLIPTextModel does not.  The LoRA names of the text encoder (lora_te_text_model_...) are derived from the prefixed form."""
+    return {(k if k.startswith(_HF_TEXT) else _HF_TEXT + k): v for k, v in sd.items()}
+
+
+def to_hf_text_state(sd, prefix=_HF_TEXT):
+    """OpenAI names of a text tower -> `transformers.CLIPTextModel` names (in_proj split into q / k / v), under `prefix` ("text_model." as in the
+    checkpoints, or "" for a transformers whose CLIPTextModel has no such level)."""
+    out = {prefix + hf[len(_HF_TEXT):]: sd[oa] for oa, hf in _HF_TEXT_TOP}
+    oa, hf = _HF_TOWERS[1]
+    for i in range(_layers(sd, oa)):
+        a, h = f"{oa}{i}.", f"{prefix}{hf[len(_HF_TEXT):]}{i}."
+        for kind in ("weight", "bias"):
+            q, k, v = sd[a + "attn.in_proj_" + kind].chunk(3, 0)
+            out[h + "self_attn.q_proj." + kind], out[h + "self_attn.k_proj." + kind], out[h + "self_attn.v_proj." + kind] = \
+                q.contiguous(), k.contiguous(), v.contiguous()
+            for x, y in _HF_BLOCK:
+                out[h + y + kind] = sd[a + x + kind]
+    return out
+
+
+def from_hf_text_state(sd):
+    """`transformers.CLIPTextModel` names, with or without the leading `text_model.` -> OpenAI names (the inverse of to_hf_text_state).  The
+    `embeddings.position_ids` buffer of older checkpoints is ignored, as is any other key the tower does not have."""
+    sd = with_text_prefix(sd)
+    missing = [hf for _, hf in _HF_TEXT_TOP if hf not in sd]
+    if missing:
+        raise KeyError(f"text encoder state dict lacks {missing[:3]} (transformers.CLIPTextModel's key names)")
+    out = {oa: sd[hf] for oa, hf in _HF_TEXT_TOP}
+    oa, hf = _HF_TOWERS[1]
+    for i in range(_layers(sd, hf)):
+        a, h = f"{oa}{i}.", f"{hf}{i}."
+        for kind in ("weight", "bias"):
+            out[a + "attn.in_proj_" + kind] = torch.cat([sd[h + f"self_attn.{n}_proj." + kind] for n in "qkv"]).contiguous()
+            for x, y in _HF_BLOCK:
+                out[a + x + kind] = sd[h + y + kind]
     return out
 
 
@@ -232,13 +301,10 @@ def tokenize_truncated(prompt, tokenizer, context=77, allow_random=False):
 
 
 def load_tokenizer(tok_dir):
-    """A CLIPTokenizer from a local directory (the directory itself or its `tokenizer` sub-directory), or None when there is none."""
-    import os
-    for d in (tok_dir, os.path.join(tok_dir, "tokenizer") if tok_dir else None):
-        if d and os.path.isfile(os.path.join(d, "vocab.json")):
-            from transformers import CLIPTokenizer
-            return CLIPTokenizer.from_pretrained(d)
-    return None
+    """CLIP's tokenizer (bpe.CLIPBPE) from a local directory (the directory itself or its `tokenizer` sub-directory: vocab.json + merges.txt), or None
+    when there is none."""
+    from .bpe import CLIPBPE
+    return CLIPBPE.from_dir(tok_dir) if tok_dir else None
 
 
 # ---- the engine
@@ -256,7 +322,53 @@ class _Tower:
             raise ValueError(f"{prefix}: {heads} heads on width {self.width} (tcl_clip_attention_f16 takes a head_dim that is a multiple of 16 up to 128)")
 
 
-class CLIPEngine:
+class _Blocks:
+    """The launches both engines are made of.  Expects self.dev, self.L, self.act and self.eps (the LayerNorms')."""
+
+    def _gemm(self, x, w, bias, resid, M, act=0):
+        N, K = w.shape
+        y = torch.empty(M, N, dtype=H16, device=self.dev)
+        self.L.tcl_gemm_f16(x, w, bias if bias is not None else 0, resid if resid is not None else 0, y, M, N, K, K, K, N, N, act, stream())
+        return y
+
+    def _ln(self, x, wb, M, C):
+        y = torch.empty(M, C, dtype=H16, device=self.dev)
+        self.L.tcl_layernorm_f16(x, wb[0], wb[1], y, M, C, self.eps, stream())
+        return y
+
+    def attention(self, qkv, B, T, heads, causal):
+        """qkv [B*T, 3*heads*d] f16 -> [B*T, heads*d] f16 (tcl_clip_attention_f16)."""
+        W = qkv.shape[1] // 3
+        d = W // heads
+        out = torch.empty(B * T, W, dtype=H16, device=self.dev)
+        self.L.tcl_clip_attention_f16(qkv, out, B, T, heads, d, 1.0 / math.sqrt(d), int(causal), stream())
+        return out
+
+    def _blocks(self, x, tower, B, T, causal):
+        M, W = B * T, tower.width
+        for p in tower.layers:
+            qkv = self._gemm(self._ln(x, (p["ln_1.weight"], p["ln_1.bias"]), M, W), p["attn.in_proj_weight"], p["attn.in_proj_bias"], None, M)
+            x = self._gemm(self.attention(qkv, B, T, tower.heads, causal), p["attn.out_proj.weight"], p["attn.out_proj.bias"], x, M)
+            u = self._gemm(self._ln(x, (p["ln_2.weight"], p["ln_2.bias"]), M, W), p["mlp.c_fc.weight"], p["mlp.c_fc.bias"], None, M, ACTS[self.act])
+            if self.act == "quick_gelu":
+                self.L.tcl_clip_quick_gelu_f16(u, u, u.numel(), stream())
+            x = self._gemm(u, p["mlp.c_proj.weight"], p["mlp.c_proj.bias"], x, M)
+        return x
+
+    def _token_rows(self, ids):
+        """ids int [B, T], checked -> (token + positional embedding rows [B*T, W] f16, B, T).  Expects self.table, self.tpos, self.vocab, self.context."""
+        if ids.dim() != 2 or not 1 <= ids.shape[1] <= self.context:
+            raise ValueError(f"token ids must be [B, T] with 1 <= T <= {self.context}, got {tuple(ids.shape)}")
+        if int(ids.min()) < 0 or int(ids.max()) >= self.vocab:
+            raise ValueError(f"token ids outside the vocabulary [0, {self.vocab})")
+        B, T, W = ids.shape[0], ids.shape[1], self.table.shape[1]
+        i32 = ids.to(self.dev).to(torch.int32).contiguous()
+        x = torch.empty(B * T, W, dtype=H16, device=self.dev)
+        self.L.tcl_clip_embed_f16(0, 0, i32, self.table, self.tpos, 0, 0, x, B, T, W, self.vocab, self.eps, stream())
+        return x, B, T
+
+
+class CLIPEngine(_Blocks):
     """clip/model.py's CLIP (VisionTransformer image tower) in inference on the device.  The keyword arguments are what the tensors of a
     transformers.CLIPModel checkpoint do not say (its config.json does): the head counts (None: width // 64, OpenAI's rule), the MLP's activation
     ("quick_gelu", or "gelu" = erf, in c_fc's GEMM epilogue) and the centre-crop rule of the preprocessing ("round": clip's _transform, "floor":
@@ -267,8 +379,8 @@ class CLIPEngine:
             raise ValueError(f"act must be one of {sorted(ACTS)}, got {act!r}")
         if crop not in CROPS:
             raise ValueError(f"crop must be one of {sorted(CROPS)}, got {crop!r}")
-        self.act, self.crop = act, crop
-        missing = [k for k in ("visual.conv1.weight", "visual.proj", "token_embedding.weight", "text_projection", "ln_final.weight") if k not in state_dict]
+        self.act, self.crop, self.eps = act, crop, 1e-5
+        missing =[k for k in ("visual.conv1.weight", "visual.proj", "token_embedding.weight", "text_projection", "ln_final.weight") if k not in state_dict]
         if missing:
             raise KeyError(f"CLIP state dict lacks {missing} (OpenAI key names; a transformers checkpoint goes through from_hf_state)")
         self.dev, self.L = torch.device(device), lib()
@@ -302,37 +414,6 @@ class CLIPEngine:
         self.logit_scale = float(sd["logit_scale"]) if "logit_scale" in sd else None               # the log, as stored (CLIP.logit_scale)
         if self.vwidth % 64 or self.twidth % 64:
             raise ValueError(f"widths {self.vwidth} / {self.twidth} must be multiples of 64 (tcl_gemm_f16's K)")
-
-    # ---- building blocks
-    def _gemm(self, x, w, bias, resid, M, act=0):
-        N, K = w.shape
-        y = torch.empty(M, N, dtype=H16, device=self.dev)
-        self.L.tcl_gemm_f16(x, w, bias if bias is not None else 0, resid if resid is not None else 0, y, M, N, K, K, K, N, N, act, stream())
-        return y
-
-    def _ln(self, x, wb, M, C):
-        y = torch.empty(M, C, dtype=H16, device=self.dev)
-        self.L.tcl_layernorm_f16(x, wb[0], wb[1], y, M, C, 1e-5, stream())
-        return y
-
-    def attention(self, qkv, B, T, heads, causal):
-        """qkv [B*T, 3*heads*d] f16 -> [B*T, heads*d] f16 (tcl_clip_attention_f16)."""
-        W = qkv.shape[1] // 3
-        d = W // heads
-        out = torch.empty(B * T, W, dtype=H16, device=self.dev)
-        self.L.tcl_clip_attention_f16(qkv, out, B, T, heads, d, 1.0 / math.sqrt(d), int(causal), stream())
-        return out
-
-    def _blocks(self, x, tower, B, T, causal):
-        M, W = B * T, tower.width
-        for p in tower.layers:
-            qkv = self._gemm(self._ln(x, (p["ln_1.weight"], p["ln_1.bias"]), M, W), p["attn.in_proj_weight"], p["attn.in_proj_bias"], None, M)
-            x = self._gemm(self.attention(qkv, B, T, tower.heads, causal), p["attn.out_proj.weight"], p["attn.out_proj.bias"], x, M)
-            u = self._gemm(self._ln(x, (p["ln_2.weight"], p["ln_2.bias"]), M, W), p["mlp.c_fc.weight"], p["mlp.c_fc.bias"], None, M, ACTS[self.act])
-            if self.act == "quick_gelu":
-                self.L.tcl_clip_quick_gelu_f16(u, u, u.numel(), stream())
-            x = self._gemm(u, p["mlp.c_proj.weight"], p["mlp.c_proj.bias"], x, M)
-        return x
 
     # ---- the two encoders
     def preprocess(self, frames_u8, want_crop=False):
@@ -377,18 +458,48 @@ class CLIPEngine:
         """CLIP.encode_text: ids int [B, T], 1 <= T <= context (clip.tokenize's padded layout, or tokenize_truncated's unpadded row, which uses the
         first T positional rows) -> [B, embed_dim] f32 on the device: the row of the end-of-text token, the largest id of its row."""
         ids = torch.as_tensor(ids)
-        if ids.dim() != 2 or not 1 <= ids.shape[1] <= self.context:
-            raise ValueError(f"token ids must be [B, T] with 1 <= T <= {self.context}, got {tuple(ids.shape)}")
-        if int(ids.min()) < 0 or int(ids.max()) >= self.vocab:
-            raise ValueError(f"token ids outside the vocabulary [0, {self.vocab})")
-        B, T, W = ids.shape[0], ids.shape[1], self.twidth
-        i32 = ids.to(self.dev).to(torch.int32).contiguous()
-        x = torch.empty(B * T, W, dtype=H16, device=self.dev)
-        self.L.tcl_clip_embed_f16(0, 0, i32, self.table, self.tpos, 0, 0, x, B, T, W, self.vocab, 1e-5, stream())
+        x, B, T = self._token_rows(ids)
+        W = self.twidth
         x = self._blocks(x, self.text, B, T, True)
         eot = ids.to(self.dev).argmax(-1)
         c = self._ln(x.view(B, T, W)[torch.arange(B, device=self.dev), eot].contiguous(), self.ln_final, B, W)
         return self._gemm(c, self.tproj, None, None, B).float()
+
+
+class CLIPTextEngine(_Blocks):
+    """A CLIP text tower alone, read at every position: `transformers.CLIPTextModel(...).last_hidden_state`, what SD-1.5 conditions its UNet on
+    (SD15_TEXT: the text tower of CLIP ViT-L/14).  The state dict holds token_embedding.weight, positional_embedding, transformer.resblocks.* and
+    ln_final.* in OpenAI's names (a transformers checkpoint goes through from_hf_text_state); a text_projection or an image tower is not needed and
+    not read.  heads None: width // 64; act: "quick_gelu" or "gelu"; eps: the LayerNorms'."""
+
+    def __init__(self, state_dict, device, heads=None, act="quick_gelu", eps=1e-5):
+        if act not in ACTS:
+            raise ValueError(f"act must be one of {sorted(ACTS)}, got {act!r}")
+        self.act, self.eps = act, float(eps)
+        missing = [k for k in ("token_embedding.weight", "positional_embedding", "ln_final.weight", "ln_final.bias") if k not in state_dict]
+        if missing:
+            raise KeyError(f"CLIP text state dict lacks {missing} (OpenAI key names; a transformers checkpoint goes through from_hf_text_state)")
+        self.dev, self.L = torch.device(device), lib()
+        sd = {k: v.float() for k, v in state_dict.items() if torch.is_tensor(v)}
+
+        def h(k):
+            return sd[k].to(H16).contiguous().to(self.dev)
+
+        self.table, self.tpos = h("token_embedding.weight"), h("positional_embedding")
+        self.vocab, self.width = self.table.shape
+        self.context = self.tpos.shape[0]
+        self.ln_final = (h("ln_final.weight"), h("ln_final.bias"))
+        self.text = _Tower(sd, "transformer.resblocks.", self.dev, heads)
+        if self.width % 64:
+            raise ValueError(f"width {self.width} must be a multiple of 64 (tcl_gemm_f16's K)")
+
+    @torch.no_grad()
+    def hidden_states(self, ids):
+        """ids int [B, T], 1 <= T <= context -> [B, T, width] f16 on the device: token + positional embedding, the causal blocks, ln_final on every
+        row; no projection and no pooling.  Row t depends on ids[:, :t + 1] only."""
+        x, B, T = self._token_rows(torch.as_tensor(ids))
+        x = self._blocks(x, self.text, B, T, True)
+        return self._ln(x, self.ln_final, B * T, self.width).view(B, T, self.width)
 
 
 def scores(feats, text=None):
@@ -464,6 +575,41 @@ def to_hf_config(arch, vision_layers=None, text_layers=None):
                 projection_dim=arch["embed_dim"], num_attention_heads=arch.get("text_heads", arch["transformer_width"] // HEAD_DIM), hidden_act=act,
                 layer_norm_eps=eps, bos_token_id=SOT, eos_token_id=EOT)
     return dict(vision_config=vision, text_config=text, projection_dim=arch["embed_dim"], logit_scale_init_value=math.log(1 / 0.07))
+
+
+_HF_TEXT_DEFAULTS = dict(hidden_size=512, intermediate_size=2048, num_hidden_layers=12, num_attention_heads=8, max_position_embeddings=77,
+                         hidden_act="quick_gelu", layer_norm_eps=1e-5)                                    # transformers' CLIPTextConfig
+
+
+def text_options(config=None):
+    """CLIPTextEngine's keyword arguments from the dictionary of a text_encoder's config.json (num_attention_heads, hidden_act, layer_norm_eps,
+    hidden_size, intermediate_size; a field that is absent has transformers' default) -> (dict(heads, act, eps), the shape the config promises:
+    dict(width, layers, context_length)).  ValueError, naming the field, for what the kernels do not cover: a head_dim that is not a multiple of 16
+    or is above 128, an activation other than quick_gelu / gelu, a LayerNorm eps other than 1e-5, an intermediate_size other than 4 x hidden_size.
+    Host-side: no device is touched."""
+    c = dict(_HF_TEXT_DEFAULTS, **{k: v for k, v in (config or {}).items() if k in _HF_TEXT_DEFAULTS})
+    w, h = c["hidden_size"], c["num_attention_heads"]
+    if not isinstance(w, int) or w <= 0 or w % 64:
+        raise ValueError(f"hidden_size {w!r}: the width must be a positive multiple of 64 (tcl_gemm_f16's K)")
+    if not isinstance(h, int) or h <= 0 or w % h or (w // h) % 16 or w // h > 128:
+        raise ValueError(f"num_attention_heads {h!r} on hidden_size {w}: head_dim must be a multiple of 16 up to 128 (tcl_clip_attention_f16)")
+    if c["hidden_act"] not in ACTS:
+        raise ValueError(f"hidden_act {c['hidden_act']!r}: the engine runs one of {sorted(ACTS)}")
+    if abs(float(c["layer_norm_eps"]) - 1e-5) > 1e-12:
+        raise ValueError(f"layer_norm_eps {c['layer_norm_eps']!r}: the engine's LayerNorms are tested at 1e-5")
+    if c["intermediate_size"] != 4 * w:
+        raise ValueError(f"intermediate_size {c['intermediate_size']!r}: the MLP must be 4 x hidden_size = {4 * w} wide")
+    return (dict(heads=h, act=c["hidden_act"], eps=1e-5),
+            dict(width=w, layers=c["num_hidden_layers"], context_length=c["max_position_embeddings"]))
+
+
+def to_hf_text_config(arch):
+    """A text architecture dictionary (SD15_TEXT) as the dictionary of a transformers config.json (`CLIPTextConfig(**to_hf_text_config(arch))`): the
+    inverse of text_options' reading, used by the golden and the tests."""
+    w = arch["width"]
+    return dict(hidden_size=w, intermediate_size=4 * w, num_hidden_layers=arch["layers"], num_attention_heads=arch.get("heads") or w // HEAD_DIM,
+                max_position_embeddings=arch["context_length"], vocab_size=arch["vocab_size"], hidden_act=arch.get("act", "quick_gelu"),
+                layer_norm_eps=arch.get("eps", 1e-5), projection_dim=w, bos_token_id=arch["vocab_size"] - 2, eos_token_id=arch["vocab_size"] - 1)
 
 
 def pick_engine(state, device, config=None):

@@ -167,6 +167,39 @@ def load_pick_state(path=None, seed=7, allow=False):
     return clip.from_hf_state(raw, consume=True), config
 
 
+def load_text_state(enc_dir):
+    """The `text_encoder/` directory of an SD-1.5 snapshot (a transformers.CLIPTextModel: config.json + model.safetensors, model.fp16.safetensors or
+    pytorch_model.bin, the first that exists) -> (state dict in transformers' key names with the leading `text_model.`, f32;  CLIPTextEngine's
+    keyword arguments).  Read without transformers.  config.json is checked first and on the host (clip.text_options: ValueError naming the field
+    for what the kernels do not cover), then against the tensors' shapes; a directory without weights is a FileNotFoundError naming it."""
+    import json
+    from . import clip
+    config = None
+    cfg = os.path.join(enc_dir, "config.json")
+    if os.path.isfile(cfg):
+        with open(cfg) as f:
+            config = json.load(f)
+    options, promised = clip.text_options(config)
+    names = ("model.safetensors", "model.fp16.safetensors", "pytorch_model.bin")
+    path = next((p for p in (os.path.join(enc_dir, n) for n in names) if os.path.isfile(p)), None)
+    if path is None:
+        raise FileNotFoundError(f"CLIP text encoder directory {enc_dir!r} holds none of {', '.join(names)} (models.text_encoder)")
+    raw = _load_safetensors(path) if path.endswith(".safetensors") else torch.load(path, map_location="cpu", weights_only=True)
+    sd = {k: (v.float() if v.is_floating_point() else v) for k, v in clip.with_text_prefix(raw).items() if not k.endswith("embeddings.position_ids")}
+    pos = sd.get("text_model.embeddings.position_embedding.weight")
+    if pos is None:
+        raise KeyError(f"{path!r} does not hold a transformers.CLIPTextModel (no embeddings.position_embedding.weight)")
+    if config is not None:
+        found = dict(width=pos.shape[1], layers=clip._layers(sd, "text_model.encoder.layers."), context_length=pos.shape[0])
+        fields = dict(width="hidden_size", layers="num_hidden_layers", context_length="max_position_embeddings")
+        for k, name in fields.items():
+            if found[k] != promised[k]:
+                raise ValueError(f"{name} {promised[k]!r} of {cfg!r}, but the tensors of {path!r} say {found[k]}")
+    else:                                                                  # no config.json: the head count comes from the width, OpenAI's rule
+        options["heads"] = None
+    return sd, options
+
+
 def load_rmbg_state(path=None, seed=3, allow=False):
     """briaai/RMBG-1.4 weights (`model.safetensors` / `model.pth` with the reference module's keys, generate.py:149)."""
     from . import rmbg

@@ -5,7 +5,8 @@ scheme on any tokenizer / encoder with the HF CLIP interface (`tokenizer(txt, tr
 `.model_max_length`, `.bos_token_id`, `.eos_token_id`; `text_encoder(ids).last_hidden_state`): untruncated tokens -> chunks of
 model_max_length-2 wrapped in BOS/EOS, padded with EOS to model_max_length -> last_hidden_state per chunk.  `encode_prompt_pair` tiles the
 shorter side, concatenates the chunks along the sequence and returns cat([uncond, cond]) (generate.py:553-555).
-`load_text_encoder(dir)` loads CLIP ViT-L/14 with `transformers` from a local directory; a missing directory raises unless random
+`load_text_encoder(dir)` loads SD-1.5's text encoder (the text tower of CLIP ViT-L/14) from a local directory into clip.CLIPTextEngine, the
+HIP engine of the CLIP figures read at last_hidden_state, and its tokenizer into bpe.CLIPBPE; a missing directory raises unless random
 stand-ins were explicitly allowed (model_utils.allow_random), in which case deterministic text-seeded embeddings of the right shape are used.
 A LoRA's text-encoder entries (`lora_te_...` / `text_encoder....`, tc_light_amd/lora.py) are merged into the local checkpoint's state dict in
 f32 before it is cast to f16; the stand-in embeddings have no weights to merge into, which is said once in a warning.
@@ -14,6 +15,7 @@ import hashlib
 import math
 import os
 import warnings
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -61,17 +63,41 @@ def merge_text_lora(text_encoder, lora):
     return text_encoder
 
 
+class TextEncoder:
+    """clip.CLIPTextEngine behind the call encode_prompt_inner makes: `encoder(ids).last_hidden_state` [B, T, width] f16 on the device."""
+
+    def __init__(self, engine):
+        self.engine = engine
+
+    def __call__(self, ids):
+        return SimpleNamespace(last_hidden_state=self.engine.hidden_states(ids))
+
+
+def load_tokenizer(enc_dir):
+    """bpe.CLIPBPE from `enc_dir`, its `tokenizer` sub-directory or, in the layout of an SD snapshot, the sibling `../tokenizer`."""
+    from .bpe import CLIPBPE
+    tried = (enc_dir, os.path.join(os.path.dirname(os.path.abspath(enc_dir)), "tokenizer"))
+    for d in tried:
+        tok = CLIPBPE.from_dir(d)
+        if tok is not None:
+            return tok
+    raise FileNotFoundError(f"no CLIP tokenizer (vocab.json + merges.txt) in {tried[0]!r}, its `tokenizer` sub-directory or {tried[1]!r}")
+
+
 def load_text_encoder(enc_dir, dev, lora=None):
-    from . import lora as L
+    """-> (bpe.CLIPBPE, TextEncoder) for the `text_encoder/` directory of an SD-1.5 snapshot.  The LoRA's text-encoder entries are merged into the
+    f32 state dict in transformers' key names (the names LoRA files spell) before it is renamed and packed: one f16 rounding, like the UNet's."""
+    from . import clip, lora as L
+    from .model_utils import load_text_state
     te_lora = lora if lora is not None and L.has_part(lora.entries, "te") else None
     key = (enc_dir, te_lora is not None)
     # the cache entry holds the LoRASet it was merged with (so the object stays alive and `is` cannot meet a recycled id); another set reloads
     if key not in _ENC or _ENC[key][2] is not te_lora:
-        from transformers import CLIPTextModel, CLIPTokenizer
-        enc = CLIPTextModel.from_pretrained(enc_dir)
+        tok = load_tokenizer(enc_dir)
+        sd, options = load_text_state(enc_dir)
         if te_lora is not None:
-            enc = merge_text_lora(enc.float(), te_lora)
-        _ENC[key] = (CLIPTokenizer.from_pretrained(enc_dir), enc.to(dev).half().eval(), te_lora)
+            sd = L.merge_into(sd, te_lora.entries, te_lora.weight, part="te")
+        _ENC[key] = (tok, TextEncoder(clip.CLIPTextEngine(clip.from_hf_text_state(sd), dev, **options)), te_lora)
     return _ENC[key][:2]
 
 
