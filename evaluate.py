@@ -1,4 +1,4 @@
-"""Evaluate a relit video: `python evaluate.py --output_dir <run output directory> [--eval_cost] [--raft PATH] [--clip PATH] [--pick PATH]` (the reference's evaluate.py).
+"""Evaluate a relit video: `python evaluate.py --output_dir <run output directory> [--eval_cost] [--raft PATH] [--clip PATH] [--pick PATH] [--lpips PATH --lpips_lin PATH]` (the reference's evaluate.py).
 
 Reads `<output_dir>/config.yaml`, the relit video (output_opt / output, .mp4 or .avi, else output.npy) and the source video (output_gt), computes
 warp-error-ssim on the device (tc_light_amd/evaluate.py: RAFT flows of the source frames, cubic warp, forward-backward mask, SSIM) and writes
@@ -9,7 +9,10 @@ named (`models.clip` or --clip, OpenAI's ViT-B-32.pt or a transformers .safetens
 `models.clip_tokenizer`, else `models.text_encoder`); clip-text differs per prompt.  pick-score is computed when a PickScore_v1 checkpoint is named
 (`models.pick` or --pick: a transformers snapshot directory or a .safetensors / .bin file; tokenizer directory: --pick_tokenizer, else
 `models.pick_tokenizer`, else the snapshot itself, else the CLIP one); it differs per prompt too.  Figures whose checkpoint is not named are listed as
-not computed; with both named result.txt holds the reference's four figures.
+not computed; with both named result.txt holds the reference's four figures.  frame-lpips, the LPIPS-VGG distance of every relit frame but the last to
+its source frame (the reference's FrameLPIPS, which its evaluate.py ships but never calls), is added when a torchvision VGG-16 state dict is named
+(`models.lpips_vgg` or --lpips) together with LPIPS's linear layers (`models.lpips_lin` or --lpips_lin: the lpips package's weights/v0.1/vgg.pth);
+without them nothing of it is loaded and the output is unchanged.
 """
 import argparse
 import os
@@ -31,14 +34,16 @@ def main(argv=None):
     ap.add_argument("--clip_tokenizer", type=str, default=None, help="CLIP tokenizer directory; default: models.clip_tokenizer, else models.text_encoder")
     ap.add_argument("--pick", type=str, default=None, help="PickScore_v1 checkpoint (snapshot directory or .safetensors); default: models.pick; none: no pick-score")
     ap.add_argument("--pick_tokenizer", type=str, default=None, help="tokenizer directory for pick-score; default: models.pick_tokenizer, else the snapshot, else the CLIP one")
+    ap.add_argument("--lpips", type=str, default=None, help="torchvision VGG-16 state dict (.pth / .safetensors) for frame-lpips; default: models.lpips_vgg; none: no frame-lpips")
+    ap.add_argument("--lpips_lin", type=str, default=None, help="LPIPS linear layers (the lpips package's weights/v0.1/vgg.pth); default: models.lpips_lin")
     ap.add_argument("--batch", type=int, default=4, help="frame pairs per RAFT / metric batch")
     a = ap.parse_args(argv)
 
     import torch
     from tc_light_amd.config_utils import _wrap
-    from tc_light_amd.evaluate import (clip_frame, clip_settings, clip_text, cost_scores, find_videos, format_results, not_computed, pick_score,
-                                       pick_settings, read_video_u8, video_name, warp_ssim)
-    from tc_light_amd.model_utils import allow_random, load_clip_state, load_pick_state, load_raft_state
+    from tc_light_amd.evaluate import (clip_frame, clip_settings, clip_text, cost_scores, find_videos, format_results, frame_lpips, lpips_settings,
+                                       not_computed, pick_score, pick_settings, read_video_u8, video_name, warp_ssim)
+    from tc_light_amd.model_utils import allow_random, load_clip_state, load_lpips_state, load_pick_state, load_raft_state
     from tc_light_amd.raft import RAFTEngine
 
     with open(os.path.join(a.output_dir, "config.yaml")) as f:
@@ -51,6 +56,7 @@ def main(argv=None):
     print(f"[INFO] edit {edit_path} ({tuple(edit.shape)}), source {source_path} ({tuple(source.shape)})")
     clip_path, tok_dir = clip_settings(models, a.clip, a.clip_tokenizer)
     pick_path, pick_tok_dir = pick_settings(models, a.pick, a.pick_tokenizer)
+    lpips_path, lpips_lin = lpips_settings(models, a.lpips, a.lpips_lin)
     left_out = not_computed(bool(clip_path), bool(pick_path))
     if left_out and pick_path:
         print(f"[INFO] not computed here: {', '.join(left_out)} (no CLIP checkpoint is configured: models.clip / --clip)")
@@ -85,6 +91,12 @@ def main(argv=None):
         for extra, prompt in zip(per_prompt, prompts):
             extra["pick-score"] = pick_score(edit, prompt, pick_eng, tokenizer, allow_random=allow_random(models), features=feats)
         del pick_eng, feats
+    if lpips_path:
+        from tc_light_amd.lpips import LPIPSEngine
+        torch.cuda.empty_cache()
+        lpips_eng = LPIPSEngine(load_lpips_state(lpips_path, lpips_lin, allow=allow_random(models)), "cuda")
+        scores["frame-lpips"], _ = frame_lpips(edit, source, lpips_eng, batch=a.batch)
+        del lpips_eng
     if a.eval_cost:
         scores.update(cost_scores(config, edit.shape[2], edit.shape[1]))
     name = video_name(config)

@@ -461,6 +461,31 @@ int tcl_clip_scores(const float* feats, const float* text, int N, int D, double*
  *   input gives the same bits. */
 int tcl_pick_scores(const float* feats, const float* text, int N, int D, float logit_scale, double* out, hipStream_t st);
 
+/* ---- frame-lpips (utils/evaluation/eval_utils.py:368-386 FrameLPIPS: lpips.LPIPS(net='vgg') between each relit frame and its source frame, both in
+ *   0..255); csrc/lpips.hip.  The model is LPIPS v0.1 (lpips/lpips.py LPIPS.forward, ScalingLayer, NetLinLayer, normalize_tensor, spatial_average;
+ *   lpips/pretrained_networks.py vgg16 = torchvision VGG-16 `features` tapped at relu1_2 .. relu5_3).  features.2 .. features.28 run on
+ *   tcl_conv3x3_f16 (act 3); the entry points below are the rest.  Everything here returns TCL_EINVAL, and launches nothing, for a shape it cannot serve.
+ * tcl_lpips_stem_f16: ScalingLayer (lpips.py:148-156) + features.0 + ReLU.  img [B,H,W,3] u8 -> y [B,H,W,64] f16 NHWC,
+ *   y = relu(bias[o] + sum over the 3x3 taps and 3 channels of w[o][(ky*3+kx)*3 + c] * v), v = img - shift_c inside the frame and 0 outside: the zero
+ *   padding is Conv2d's, of the SCALED image.  w [64,27] f32 is the conv weight times (input scale / scale_c), bias [64] f32; f32 sums, one rounding.
+ * tcl_maxpool2_f16: MaxPool2d(kernel_size=2, stride=2) of VGG-16 (floor mode: an odd last row / column is dropped).  x [B,H,W,C] -> y [B,H/2,W/2,C]
+ *   f16 NHWC, C % 64 == 0, H, W >= 2.  Of equal values the first in window order wins, NaN wins over all: bit-equal to torch's max_pool2d.
+ * tcl_lpips_head: one tap of lpips.py:112-123.  f [2B,P,C] f16 (image 0 of pair b at row b, image 1 at row B + b), w [C] f32 (lin{k}.model.1.weight):
+ *   per pixel sum_c w_c (f0_c / (|f0| + eps) - f1_c / (|f1| + eps))^2 in f32, summed over blocks of 64 pixels into the workspace, with each block's
+ *   count of non-finite features.  h_P (HOST, ntaps ints, ntaps <= 8): the pixel counts of all the taps of this evaluation, tap: which of them f is;
+ *   C % 64 == 0.  ws: tap k's section follows those of the taps before it and is B * ceil(h_P[k] / 64) * 8 bytes.
+ * tcl_lpips_finish: spatial_average and the sum over the taps (lpips.py:119-128): out [B] f32 = sum_k (partials of tap k, added in index order in
+ *   f64) / h_P[k], the taps in order; nonfinite [ntaps] int32 (device) = the non-finite features seen per tap.  No atomics anywhere: the same
+ *   input gives the same bits.
+ * tcl_lpips_workspace_bytes: the workspace of the five VGG taps of an H x W frame (H x W, then halved with floor four times) for B pairs; 0 when a
+ *   pooled size would be 0 (H or W < 16) or B is outside 1..65535. */
+int tcl_lpips_stem_f16(const void* img, const float* w, const float* bias, float shift_r, float shift_g, float shift_b, void* y, int B, int H, int W,
+                       hipStream_t st);
+int tcl_maxpool2_f16(const void* x, void* y, int B, int H, int W, int C, hipStream_t st);
+size_t tcl_lpips_workspace_bytes(int B, int H, int W);
+int tcl_lpips_head(const void* f, const float* w, int B, const int* h_P, int ntaps, int tap, int C, float eps, void* ws, hipStream_t st);
+int tcl_lpips_finish(const void* ws, int B, const int* h_P, int ntaps, float* out, int* nonfinite, hipStream_t st);
+
 /* ===================================================================== spatio-temporal Unique Video Tensor (sceneflow scenes); csrc/voxel.hip */
 /* SceneFlowDataParser.rgbd2pcd  utils/dataparsers/sceneflow_dataparsers.py:257-274.  depth [N,H,W], c2w [N,4,4] row-major -> p_world [N,3,H,W]
  *   (planar, so process_frames applies directly).  Per pixel, without fma contraction: x = (px - cx) * d / fx (product, then quotient), y likewise,

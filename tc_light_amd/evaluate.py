@@ -14,7 +14,12 @@ computed, as before.
 pick-score (evaluate.py:52-56, eval_utils.py:163-176) is computed when a PickScore_v1 checkpoint is configured (`models.pick` / --pick): the same
 engine at CLIP ViT-H/14 (`clip.pick_engine`: 16 heads per tower, erf GELU, patch rows padded from 588 to 640 columns, the transformers processor's
 floored centre crop), the prompt tokenised as the processor does (truncated to 77, unpadded), and exp(logit_scale) cos(text, frame) averaged over the
-frames (tcl_pick_scores).  FrameLPIPS is not computed: the reference's evaluate.py never calls it.
+frames (tcl_pick_scores).
+
+frame-lpips (eval_utils.py:368-386 FrameLPIPS, which the reference ships but its evaluate.py never calls) is computed when a VGG-16 state dict is
+configured (`models.lpips_vgg` / --lpips, with `models.lpips_lin` / --lpips_lin for LPIPS's linear layers): the LPIPS-VGG distance (`lpips.LPIPSEngine`)
+between every relit frame but the last and its source frame, both in 0..255 and replicate-padded to multiples of 8, averaged over the frames.  It asks
+whether the relit video is still the same video, which none of the other figures does.  With no path it is not loaded and result.txt is what it was.
 """
 import math
 import os
@@ -56,6 +61,16 @@ def pick_settings(models, pick_arg=None, tokenizer_arg=None):
     own = path if path and os.path.isfile(os.path.join(path, "vocab.json")) else None
     tok = tokenizer_arg or models.get("pick_tokenizer") or own or models.get("clip_tokenizer") or models.get("text_encoder") or None
     return path, (tok if path else None)
+
+
+def lpips_settings(models, lpips_arg=None, lin_arg=None):
+    """-> (VGG-16 state dict path or None, LPIPS linear-layer path or None).  The first is --lpips, else `models.lpips_vgg`; None switches
+    frame-lpips off (allow_random alone never switches it on).  The second is --lpips_lin, else `models.lpips_lin`, and counts only when the
+    figure is on."""
+    models = models or {}
+    path = lpips_arg or models.get("lpips_vgg") or None
+    lin = lin_arg or models.get("lpips_lin") or None
+    return path, (lin if path else None)
 
 
 # ---- the kernels
@@ -198,6 +213,32 @@ def pick_score(edit_u8, prompt, engine, tokenizer, allow_random=False, batch=64,
     feats = engine.encode_image(_nhwc_u8(edit_u8), batch=batch) if features is None else features
     ids = clip.tokenize_truncated(prompt, tokenizer, engine.context, allow_random)
     return clip.pick_scores(feats, engine.encode_text(ids)[0], engine.logit_scale)[0]
+
+
+# ---- frame-lpips
+@torch.no_grad()
+def frame_lpips(edit_u8, source_u8, engine, batch=4):
+    """eu.FrameLPIPS (eval_utils.py:368-386): edit_u8 / source_u8 uint8 [N,H,W,3] (numpy or tensors) -> (the mean LPIPS-VGG distance between relit
+    frame i and source frame i over i = 0 .. N-2, the per-frame float64 array).  The reference's own behaviour is kept: the last frame is left out
+    (`edit_pil_list[:-1]`), the frames stay in 0..255 (load_image; LPIPS's normalize=False) and both are replicate-padded to multiples of 8
+    (InputPadder) before the distance.  Source frames of another size are resized to the edit size first, as for the other figures.  `engine` is a
+    lpips.LPIPSEngine; `batch` pairs run at a time."""
+    from .lpips import pad8_u8
+    edit, src = _nhwc_u8(edit_u8), _nhwc_u8(source_u8)
+    N, H, W = edit.shape[:3]
+    if N < 2 or len(src) < N - 1:
+        raise ValueError(f"frame-lpips leaves the last frame out: it needs at least 2 edit frames and one source frame fewer, got {N} / {len(src)}")
+    src = src[:N - 1]
+    if tuple(src.shape[1:3]) != (H, W):
+        src = resize_like(src, H, W)
+    batch = max(1, min(batch, N - 1))
+    per = []
+    for s in range(0, N - 1, batch):
+        e = pad8_u8(edit[s:min(s + batch, N - 1)].to(engine.dev))
+        g = pad8_u8(src[s:s + batch].to(engine.dev))
+        per.append(engine.distance(g, e))                                   # loss_fn_vgg(gt, pil_img)
+    per = torch.cat(per).cpu().numpy().astype(np.float64)
+    return float(np.mean(per)), per
 
 
 # ---- files

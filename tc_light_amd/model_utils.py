@@ -167,6 +167,32 @@ def load_pick_state(path=None, seed=7, allow=False):
     return clip.from_hf_state(raw, consume=True), config
 
 
+def load_lpips_state(vgg_path=None, lin_path=None, allow=False, seed=8):
+    """The two files lpips.LPIPS(net='vgg') reads (eval_utils.py:371): `vgg_path`, a torchvision vgg16 state dict (`features.N.weight / .bias`; its
+    classifier is ignored), and `lin_path`, the lpips package's weights/v0.1/vgg.pth (`lin{k}.model.1.weight`); each a .pth or a .safetensors.  ->
+    one dict with both key sets, every key and shape checked (KeyError naming it) before anything is handed on.  A missing file is an error
+    unless `allow`, which stands seeded tensors in for that file."""
+    from . import lpips
+    sd = {}
+    for what, path, shapes in (("LPIPS VGG-16", vgg_path, lpips.vgg_param_shapes()), ("LPIPS linear-layer (vgg.pth)", lin_path, lpips.lin_param_shapes())):
+        if not (path and os.path.exists(path)):
+            _missing(what, path, allow)
+            stand_in = lpips.seeded_state(seed)
+            sd.update({k: stand_in[k] for k in shapes})
+            continue
+        raw = _load_safetensors(path) if path.endswith(".safetensors") else torch.load(path, map_location="cpu", weights_only=True)
+        raw = raw.get("state_dict", raw) if isinstance(raw, dict) else raw
+        raw = {(k[7:] if k.startswith("module.") else k): v for k, v in raw.items()}
+        for k, s in shapes.items():
+            if k not in raw:
+                raise KeyError(f"{what} file {path!r} lacks {k}")
+            if tuple(raw[k].shape) != tuple(s):
+                raise KeyError(f"{what} file {path!r}: {k} has shape {tuple(raw[k].shape)}, expected {tuple(s)}")
+            sd[k] = raw[k].float()
+    lpips.check_state(sd)
+    return sd
+
+
 def load_text_state(enc_dir):
     """The `text_encoder/` directory of an SD-1.5 snapshot (a transformers.CLIPTextModel: config.json + model.safetensors, model.fp16.safetensors or
     pytorch_model.bin, the first that exists) -> (state dict in transformers' key names with the leading `text_model.`, f32;  CLIPTextEngine's
