@@ -219,6 +219,19 @@ int tcl_invert_pack_f16(const float* x, const void* cond, const int* idx, int N,
  * (the UNet input tcl_invert_pack_f16 wrote; channels 4-7 are left alone), so the next step needs no repack. */
 int tcl_ddim_step_f32(float* x, const void* eps, const int* idx, int N, int F, int F_valid, int h, int w, float mu, float sigma, float mu_prev,
                       float sigma_prev, int inversion, void* xin, hipStream_t st);
+/* IC-Light's "Lighting Preference" start (gradio_demo_iclight.py:235-299: bg_source, lowres_denoise, the img2img call; csrc/light.hip).
+ * tcl_light_gradient_f32: out [3,H,W] f32 (16 B aligned) = u/254, the same plane three times, u = uint8(np.linspace(255, 0, W)) along x for
+ * TCL_LIGHT_LEFT, (0, 255, W) for RIGHT, the same over H along y for TOP / BOTTOM -- linspace in f64 as start + i*step with
+ * step = (stop - start)/(n - 1), no fma contraction, the last sample = stop, n == 1 -> start; truncated to uint8.  u/254 is the [0,1]-convention
+ * image whose 2x - 1 (VAEEngine.encode) is the demo's u/127 - 1 (numpy2pytorch).  H, W <= 0, 3*H*W >= 2^31 - 3 or another side return TCL_EINVAL. */
+enum { TCL_LIGHT_LEFT = 0, TCL_LIGHT_RIGHT = 1, TCL_LIGHT_TOP = 2, TCL_LIGHT_BOTTOM = 3 };
+int tcl_light_gradient_f32(float* out, int H, int W, int side, hipStream_t st);
+/* tcl_light_start_f16 (the img2img pipeline's scheduler.add_noise at the first executed sigma): out [N,chw] f16, x0 f16, z f32;
+ * out[n][i] = f16(fl32(fl32(alpha*x0[n*x0_stride + i]) + fl32(sigma_t*z[n*z_stride + i]))) -- no contraction, one rounding to f16.  Strides are in
+ * elements per frame, 0 broadcasts one frame to all N (x0: the gradient's latent; z: noise_mode "same"), otherwise >= chw.  Any chw > 0; 16 B
+ * accesses when chw and the strides are multiples of 8 and the pointers 16 B aligned.  alpha = 1/sqrt(sigma^2 + 1), sigma_t = sigma*alpha (host f64 -> f32). */
+int tcl_light_start_f16(void* out, const void* x0, long x0_stride, const float* z, long z_stride, int N, long chw, float alpha, float sigma_t,
+                        hipStream_t st);
 /* layout conversions around the VAE (generate_utils.py:140-172): 2*img-1 -> NHWC8 f16; clamp(y/2+0.5) -> [B,3,H,W] f32.
  * ldc = row stride in halves, >= the channels read or written (tcl_nchw_to_nhwc_f16 zeroes columns C..ldc-1); empty batches and narrower strides
  * return TCL_EINVAL.  tcl_transpose_f16: in [batch,R,ldi] -> out [batch,Cc,ldo], ldi >= Cc, ldo >= R, padding columns of out are left untouched. */

@@ -1,4 +1,5 @@
-"""Entry point with the reference's surface (run.py:8-32): python run.py --config Y | -i video -p prompt [-n neg] [--multi_axis].
+"""Entry point with the reference's surface (run.py:8-32): python run.py --config Y | -i video -p prompt [-n neg] [--multi_axis],
+plus [--light left|right|top|bottom|source] [--strength F]: IC-Light's "Lighting Preference" start (generation.init_latent / init_strength).
 data.scene_type picks the parser (generate.py:84-95): video (VideoDataParser) or sceneflow (SceneFlowDataParser: ground-truth depth, poses and
 flows -> voxelised Unique Video Tensor ids); carla and interiornet are not built.
 
@@ -18,7 +19,8 @@ import torch
 
 from tc_light_amd.config_utils import load_config, save_config
 from tc_light_amd.dataparser import VideoDataParser, get_frame_ids, save_loss_curve, save_video
-from tc_light_amd.generate import Generator
+from tc_light_amd.generate import DEFAULTS, Generator
+from tc_light_amd.hostlogic import check_init
 from tc_light_amd.model_utils import allow_random, init_iclight
 from tc_light_amd.parallel import Dist
 from tc_light_amd.text import encode_prompt_pair
@@ -41,6 +43,10 @@ def main(argv=None):
         raise NotImplementedError(f"data.scene_type '{scene_type}': this dataparser is not yet built in tc_light_amd (video and sceneflow are)")
     if scene_type not in ("video", "sceneflow"):
         raise NotImplementedError(f"Scene type '{scene_type}' is not supported.")
+    # IC-Light's "Lighting Preference" start (generation.init_latent / init_strength; --light / --strength): refused here when malformed
+    config.generation.init_latent, config.generation.init_strength = check_init(
+        config.generation.get("init_latent", DEFAULTS["init_latent"]), config.generation.get("init_strength", DEFAULTS["init_strength"]),
+        config.generation.get("n_timesteps", DEFAULTS["n_timesteps"]))
     lora = None
     if config.generation.get("use_lora"):         # generate_utils.py:95-96; the file is read and its layout checked before any model is loaded
         from tc_light_amd.lora import from_config
@@ -119,6 +125,7 @@ def main(argv=None):
             config.total_time += info["total_time"]
             config.sec_per_frame = config.total_time / len(frame_ids)
             config.max_memory_allocated = max(config.max_memory_allocated, info["max_memory_allocated"])
+            g.scheduler_steps, g.steps_executed = info["scheduler_steps"], info["steps_executed"]      # init_latent / init_strength are in g already
             # generate.py:613-630: save_name, config.yaml, output.mp4 (+ frames), output_gt.mp4, loss curves
             path = os.path.join(g.output_path, f"lmr_{g.local_merge_ratio}_gmr_{g.global_merge_ratio}_alpha_t_{g.alpha_t}_opt_{name}")
             save_config(config, path, gene=True)

@@ -78,8 +78,16 @@ def load_config(argv=None, print_config=True):
     ap.add_argument("--prompt", "-p", type=str, default=None, help="prompt for video relighting, for a fast usage")
     ap.add_argument("--negative_prompt", "-n", type=str, default=None, help="negative prompt, for a fast usage")
     ap.add_argument("--multi_axis", action="store_true", help="use multi-axis denoising, for a fast usage")
+    # not in the reference's run.py: IC-Light's own "Lighting Preference" (generation.init_latent / init_strength, generate.py DEFAULTS)
+    ap.add_argument("--light", choices=("left", "right", "top", "bottom", "source"), default=None,
+                    help="start the denoise from a light gradient of that side (or the source frames), for a fast usage")
+    ap.add_argument("--strength", type=float, default=None, help="how far the relight may move from that start, in (0, 1], for a fast usage")
     a = ap.parse_args(argv)
     cfg = load_yaml_chain(a.config, a.base_config)
+    if a.light is not None:
+        cfg.generation.init_latent = a.light
+    if a.strength is not None:
+        cfg.generation.init_strength = a.strength
     if a.input_path is not None and cfg.data.scene_type.lower() == "video":
         cfg.data.rgb_path = a.input_path
     if a.multi_axis:

@@ -2,6 +2,8 @@
 
   prepare_data -> _prepare_prompts_and_conditions -> ddim_sample{pred_noise per xy-chunk; temporal_denoise (yt-plane);
   scheduler.step} -> decode_latents_batch -> exposure_align -> unique_tensor_optimization        (generate.py:560-611)
+generation.init_latent (not in the reference's run.py; IC-Light's "Lighting Preference", gradio_demo_iclight.py:235-299): build_start replaces the noise
+start by an img2img one and ddim_sample enters a longer schedule part-way; the loop itself is the same.
 
 Python sequences kernel launches and collectives; tensors never leave the device inside the timed region and there is no
 per-iteration host sync (the reference syncs on loss.item() and moves the token bank through the CPU).
@@ -42,6 +44,11 @@ DEFAULTS = dict(  # configs/tclight_default.yaml (generation / post_opt sections
     latents_path=None, model_key="iclight", frame_ids=None,
     # ^ generation.latents_path (generate.py:563-566): saved start latents `<latents_path>/<model_key>/noisy_latents_<first timestep>.pt`, a tensor
     #   over the video's frames of which `frame_ids` (None: all) are this run's; when the file exists it replaces the random start noise.
+    init_latent="none", init_strength=0.9,
+    # ^ IC-Light's "Lighting Preference" (gradio_demo_iclight.py:235-299: bg_source, lowres_denoise): left | right | top | bottom start the denoise from
+    #   the VAE latent of a light gradient, `source` from the frames' own clean latents, noised to init_strength -- the scheduler is set to
+    #   round(n_timesteps / init_strength) steps and entered at the index that leaves int(steps * init_strength) of them (HL.img2img_schedule).
+    #   "none": the start is noise (or latents_path) and init_strength changes nothing.  Otherwise latents_path is not consulted.
     max_tokens_per_pass=None)
     # ^ None: TCL_MAX_TOKENS_PER_PASS (read when the Generator is built), else min(16 M, 80 % of the device's free memory / 10.5 KB) -- a block-major pass
     #   peaks at ~10.4 KB of activations per level-0 token (90 GB for the 8.64 M tokens of 300 frames at 1280x720): a 288 GB MI355X gets the 16 M
@@ -81,6 +88,10 @@ class Generator:
         t = self.unet.tome
         t.args.update(local_merge_ratio=c.local_merge_ratio, merge_global=c.merge_global, global_merge_ratio=c.global_merge_ratio,
                       global_rand=c.global_rand, align_batch=bool(c.align_batch))
+        c.init_latent, c.init_strength = HL.check_init(c.init_latent, c.init_strength, c.n_timesteps)
+        self.img2img = c.init_latent != "none"
+        # (scheduler steps, begin index, steps executed): the whole n_timesteps schedule unless the start is an img2img one
+        self.schedule = HL.img2img_schedule(c.n_timesteps, c.init_strength) if self.img2img else (c.n_timesteps, 0, c.n_timesteps)
         self.batch_size = 2
         self.timing = {}
         if c.max_tokens_per_pass is None:
@@ -101,17 +112,55 @@ class Generator:
         self.h, self.w = H // 8, W // 8
         self.n_total = getattr(self, "n_total", None) or n * self.dist.world
         self.rng_dev = torch.Generator(device=self.dev).manual_seed(int(c.seed))
-        if c.latents_path is not None and self._load_start_latents(n):
+        self.start_noise = None
+        if self.img2img:
+            if c.latents_path is not None:
+                print(f"[INFO] init_latent '{c.init_latent}': the start is built from it, generation.latents_path is not consulted.")
+        elif c.latents_path is not None and self._load_start_latents(n):
             return
         if c.noise_mode.lower() == "same":        # prepare_latents(1, 4, H, W) repeated (generate.py:183-188)
             z = torch.randn(1, 4, self.h, self.w, generator=self.rng_dev, device=self.dev, dtype=torch.float32)
+            if self.img2img:
+                self.start_noise = z              # f32, one frame for all: build_start broadcasts it
+                return
             self.init_noise = (z * self.scheduler.init_noise_sigma).to(H16).repeat(n, 1, 1, 1).contiguous()
         elif c.noise_mode.lower() == "vanilla":
             z = torch.randn(self.n_total, 4, self.h, self.w, generator=self.rng_dev, device=self.dev, dtype=torch.float32)
             lo, hi = self.dist.range(self.n_total)
+            if self.img2img:
+                self.start_noise = z[lo:hi]       # f32, this rank's block
+                return
             self.init_noise = (z[lo:hi] * self.scheduler.init_noise_sigma).to(H16).contiguous()
         else:
             raise NotImplementedError(f"Noise mode '{c.noise_mode}' is not supported.")
+
+    def light_gradient(self, side, H, W):
+        """The demo's bg_source image (gradio_demo_iclight.py:241-256) in VAEEngine.encode's [0,1] convention: [1,3,H,W] f32 = uint8(linspace)/254."""
+        img = torch.empty(1, 3, H, W, dtype=torch.float32, device=self.dev)
+        self.L.tcl_light_gradient_f32(img, H, W, HL.INIT_LATENTS.index(side) - 1, stream())
+        return img
+
+    def build_start(self, concat_conds):
+        """img2img start (gradio_demo_iclight.py:283-299 -> the img2img pipeline's add_noise): init_noise = alpha*x0 + sigma_t*z at the first executed
+        sigma, with z the f32 draw of prepare_data and x0 the light gradient's latent (encoded once, shared by all frames) or, for `source`,
+        the frames' own clean latents `concat_conds` [n_local,4,h,w] f16."""
+        c, sch = self.cfg, self.scheduler
+        n_sched, begin, _ = self.schedule
+        sch.set_timesteps(n_sched, begin)
+        alpha, sigma_t = (float(np.float32(v)) for v in sch.add_noise_coefficients())
+        n, chw = self.frames.shape[0], 4 * self.h * self.w
+        if c.init_latent == "source":
+            x0, x0_stride = concat_conds.contiguous(), chw
+            if tuple(x0.shape) != (n, 4, self.h, self.w) or x0.dtype != H16:
+                raise ValueError(f"init_latent 'source': clean latents {tuple(x0.shape)} {x0.dtype}, expected {(n, 4, self.h, self.w)} f16")
+        else:
+            x0, x0_stride = self.vae.encode(self.light_gradient(c.init_latent, *self.frames.shape[-2:])).contiguous(), 0
+        same = c.noise_mode.lower() == "same"
+        z = self.start_noise.contiguous()
+        assert z.shape[0] == (1 if same else n)
+        self.init_noise = torch.empty(n, 4, self.h, self.w, dtype=H16, device=self.dev)
+        self.L.tcl_light_start_f16(self.init_noise, x0, x0_stride, z, 0 if same else chw, n, chw, alpha, sigma_t, stream())
+        return self.init_noise
 
     def _load_start_latents(self, n):
         """generate.py:563-566, 191-194: start from the saved latents of the scheduler's first timestep when they exist (-> True); nothing is
@@ -213,7 +262,10 @@ class Generator:
     def ddim_sample(self, x, conds, conds_t, concat_conds):
         c, d = self.cfg, self.dist
         sch = self.scheduler
-        sch.set_timesteps(c.n_timesteps)
+        if self.img2img:       # enter the longer schedule at its begin index: sch.timesteps are the executed steps, so the decay `alphas` and the
+            sch.set_timesteps(*self.schedule[:2])      # "no noise on the last step" rule below are taken over them, counted from 0
+        else:
+            sch.set_timesteps(c.n_timesteps)
         n_local = x.shape[0]
         noises = torch.zeros_like(x)
         noises_t = torch.zeros_like(x)
@@ -249,6 +301,8 @@ class Generator:
         t0 = ev()
         self.prepare_data(frames, background)
         concat_conds = self.vae.encode_imgs_batch(self.frames, self.batch_size)
+        if self.img2img:
+            self.build_start(concat_conds)
         t1 = ev()
         x = self.ddim_sample(self.init_noise.clone(), conds, conds_t, concat_conds)
         t2 = ev()
@@ -301,6 +355,7 @@ class Generator:
             t4 = t5 = t3
         self.timing = dict(encode=t1 - t0, denoise=t2 - t1, decode=t3 - t2, stage1=t4 - t3, stage2=t5 - t4, total=t5 - t0)
         info = dict(timing=self.timing, losses_exposure=losses1, losses_unique=losses2, total_time=t5 - t0,
-                    sec_per_frame=(t5 - t0) / self.n_total, total_number_of_frames=self.n_total,
+                    sec_per_frame=(t5 - t0) / self.n_total, total_number_of_frames=self.n_total, init_latent=c.init_latent,
+                    init_strength=c.init_strength, scheduler_steps=self.schedule[0], steps_executed=self.schedule[2],
                     max_memory_allocated=torch.cuda.max_memory_allocated(self.dev) / 1024.0 ** 2)
         return clean, info

@@ -77,6 +77,30 @@ def alpha_schedule(alpha_t, final_factor_t, n_steps):
     return [alpha_t * final_factor_t ** min(i / n_steps, 1) for i in range(n_steps)]
 
 
+INIT_LATENTS = ("none", "left", "right", "top", "bottom", "source")       # generation.init_latent; the four sides in the order of TCL_LIGHT_*
+
+
+def check_init(init_latent, init_strength, n_timesteps=None):
+    """generation.init_latent / init_strength as (str, float); anything else is a ValueError (run.py raises it before a model is loaded).
+    With n_timesteps: a schedule that would execute no step at all is refused too (diffusers' img2img pipeline does the same)."""
+    name = "none" if init_latent is None else str(init_latent).lower()
+    if name not in INIT_LATENTS:
+        raise ValueError(f"generation.init_latent {init_latent!r}: expected one of {' | '.join(INIT_LATENTS)}")
+    if isinstance(init_strength, bool) or not isinstance(init_strength, (int, float)) or not 0.0 < float(init_strength) <= 1.0:
+        raise ValueError(f"generation.init_strength {init_strength!r}: expected a number in (0, 1]")
+    if n_timesteps is not None and name != "none" and img2img_schedule(n_timesteps, init_strength)[2] < 1:
+        raise ValueError(f"generation.init_strength {init_strength} with n_timesteps {n_timesteps} leaves no step to execute")
+    return name, float(init_strength)
+
+
+def img2img_schedule(n, strength):
+    """-> (scheduler steps, begin index, steps executed) of an img2img start (gradio_demo_iclight.py:293 and diffusers' img2img get_timesteps,
+    restated): the scheduler is set to round(n / strength) steps and the loop runs the last int(steps * strength) of them -- n, give or take one."""
+    n_sched = int(round(n / strength))
+    run = min(int(n_sched * strength), n_sched)
+    return n_sched, n_sched - run, run
+
+
 def shard_range(n, rank, world):
     """Contiguous frame block of `rank` (sizes differ by at most one; SURVEY 8(d) config 3: 38/38/38/38/37/37/37/37)."""
     base, rem = divmod(n, world)

@@ -6,6 +6,11 @@ final_sigmas_type "zero".  diffusers==0.32.1 is not available here: this restate
 Surface kept from the reference's use (generate.py:561,211,235): set_timesteps(n), .timesteps, .init_noise_sigma,
 step(model_output, timestep, sample, noise=...) -- the noise tensor is explicit instead of a generator list.
 The update itself is one HIP kernel (tcl_dpm_sde_step_f16); this class only derives its scalar coefficients.
+
+set_timesteps(n, begin) enters the n-step schedule at index `begin` (the img2img start of IC-Light's demo, gradio_demo_iclight.py:235-299 ->
+diffusers' img2img get_timesteps + set_begin_index): .timesteps is timesteps[begin:], step k works on the absolute sigma index begin + k with an
+empty multistep history, add_noise_coefficients() gives the (alpha, sigma_t) the clean start is noised with.  The slice is [begin:], not
+[order*begin:]: diffusers' class attribute `order` of this scheduler is 1; `order` below is the SOLVER order.
 """
 import math
 
@@ -25,7 +30,9 @@ class DPMSolverSDEScheduler:
         self.num_train_timesteps = num_train_timesteps
         self.timesteps = None
 
-    def set_timesteps(self, n, device=None):
+    def set_timesteps(self, n, begin=0, device=None):
+        if not 0 <= begin < n:
+            raise ValueError(f"set_timesteps: begin index {begin} outside the {n} steps")
         ac = self.alphas_cumprod
         sig = ((1 - ac) / ac) ** 0.5
         log_sig = np.log(sig)
@@ -43,9 +50,10 @@ class DPMSolverSDEScheduler:
             w = min(max((lo - ls) / (lo - hi), 0.0), 1.0)
             ts.append((1 - w) * low + w * (low + 1))
         self.sigmas = np.concatenate([karras, [0.0]]).astype(np.float32)
-        self.timesteps = torch.from_numpy(np.array(ts).round().astype(np.int64))
+        self.timesteps = torch.from_numpy(np.array(ts).round().astype(np.int64))[begin:]
         self.num_inference_steps = n
-        self._i = 0
+        self.begin = begin
+        self._i = begin
         self._lower = 0
         self._m = [None, None]
 
@@ -76,11 +84,19 @@ class DPMSolverSDEScheduler:
             return st_cur, a_cur, ca, cB * (1 + 0.5 / r0), -cB * 0.5 / r0, cc
         return st_cur, a_cur, ca, cB, 0.0, cc
 
+    def add_noise_coefficients(self):
+        """(alpha, sigma_t) of the first executed sigma, sigmas[begin]: x_start = alpha*x0 + sigma_t*z (diffusers' add_noise)."""
+        return self._alpha_sigma(float(self.sigmas[self.begin]))
+
+    def next_step(self):
+        """(absolute sigma index, second order?) of the step that `step` runs next."""
+        i = self._i
+        last = i == self.num_inference_steps - 1
+        return i, (self._lower >= 1) and not last        # lower_order_final with final_sigmas_type == "zero"
+
     def step(self, model_output, timestep, sample, noise=None, return_dict=False):
         """In place on `sample` ([N,4,h,w] f16 device); model_output f16; noise f16 or None."""
-        i = self._i
-        last = i == len(self.timesteps) - 1
-        second = (self._lower >= 1) and not last         # lower_order_final with final_sigmas_type == "zero"
+        i, second = self.next_step()
         sig_t, al_t, ca, cb0, cb1, cc = self.coefficients(i, second)
         n = sample.numel()
         if self._m[0] is None:
