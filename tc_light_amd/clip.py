@@ -19,9 +19,14 @@ State dicts use OpenAI's key names.  `from_hf_state` / `to_hf_state` map to and 
 in_proj, the projections transposed).  Pinned against `transformers.CLIPModel` in f32 by tests/golden/clip.npz (tests/test_gpu_clip.py).
 
 `CLIPTextEngine` is the text tower alone, read at every position (ln_final on all rows, no projection): `transformers.CLIPTextModel`'s
-last_hidden_state, the prompt embeddings of SD-1.5 (`SD15_TEXT`, the text tower of CLIP ViT-L/14; tc_light_amd/text.py).  It shares the block sequence
-with CLIPEngine (`_Blocks`); `from_hf_text_state` / `to_hf_text_state` map a text_encoder checkpoint, `text_options` reads its config.json.  Pinned by
-tests/golden/text.npz (tests/test_gpu_text.py).
+last_hidden_state, the prompt embeddings of SD-1.5 (`SD15_TEXT`, the text tower of CLIP ViT-L/14; tc_light_amd/text.py).  `from_hf_text_state` /
+`to_hf_text_state` map a text_encoder checkpoint, `text_options` reads its config.json.  Pinned by tests/golden/text.npz (tests/test_gpu_text.py).
+
+Structure: `_tower_to_hf` / `_tower_from_hf` are the per-layer renaming, one per direction, under the four state-dict maps; `_prompt_ids` is the
+tokenizer front of `tokenize` and `tokenize_truncated`; `_check_tower` holds the rules on heads, activation and eps for `_Tower`, `pick_options` and
+`text_options`.  `_Blocks` is the launches of a block sequence, built from (device, act, eps).  `_TextTower` is a `_Blocks` with the token table,
+positional rows, ln_final and the text `_Tower`: CLIPTextEngine is one plus `hidden_states`; CLIPEngine, a `_Blocks` with the image side, holds one
+for `encode_text`.  tests/test_clip_trace_cpu.py pins the launches of both.
 """
 import hashlib
 import math
@@ -55,13 +60,27 @@ def _block_shapes(sh, prefix, width):
     sh[prefix + "mlp.c_fc.weight"] = (4 * width, width); sh[prefix + "mlp.c_fc.bias"] = (4 * width,)
     sh[prefix + "mlp.c_proj.weight"] = (width, 4 * width); sh[prefix + "mlp.c_proj.bias"] = (width,)
     sh[prefix + "ln_2.weight"] = (width,); sh[prefix + "ln_2.bias"] = (width,)
+    return sh
+
+
+_BLOCK_KEYS = tuple(_block_shapes({}, "", 0))                           # the twelve tensors of a block, as _Tower loads them
+
+
+def text_param_shapes(width=768, layers=12, context_length=77, vocab_size=49408):
+    """State-dict keys and shapes of a text tower alone, as CLIPTextEngine takes it (the defaults are SD15_TEXT): no text_projection, no visual.*."""
+    sh = {"token_embedding.weight": (vocab_size, width), "positional_embedding": (context_length, width)}
+    for i in range(layers):
+        _block_shapes(sh, f"transformer.resblocks.{i}.", width)
+    sh["ln_final.weight"] = (width,); sh["ln_final.bias"] = (width,)
+    return sh
 
 
 def clip_param_shapes(embed_dim=512, image_resolution=224, vision_layers=12, vision_width=768, vision_patch_size=32, context_length=77,
                       vocab_size=49408, transformer_width=512, transformer_layers=12):
-    """State-dict keys and shapes of clip/model.py's CLIP with a VisionTransformer tower (the defaults are ViT-B/32)."""
+    """State-dict keys and shapes of clip/model.py's CLIP with a VisionTransformer tower (the defaults are ViT-B/32).  The key order is the order
+    `_seeded` draws in, which the goldens were made from: the image tower, text_param_shapes' keys in their order, the two text-side scalars."""
     sh = {}
-    vw, tw = vision_width, transformer_width
+    vw = vision_width
     grid = image_resolution // vision_patch_size
     sh["visual.class_embedding"] = (vw,)
     sh["visual.positional_embedding"] = (grid * grid + 1, vw)
@@ -71,12 +90,8 @@ def clip_param_shapes(embed_dim=512, image_resolution=224, vision_layers=12, vis
         _block_shapes(sh, f"visual.transformer.resblocks.{i}.", vw)
     sh["visual.ln_post.weight"] = (vw,); sh["visual.ln_post.bias"] = (vw,)
     sh["visual.proj"] = (vw, embed_dim)
-    sh["token_embedding.weight"] = (vocab_size, tw)
-    sh["positional_embedding"] = (context_length, tw)
-    for i in range(transformer_layers):
-        _block_shapes(sh, f"transformer.resblocks.{i}.", tw)
-    sh["ln_final.weight"] = (tw,); sh["ln_final.bias"] = (tw,)
-    sh["text_projection"] = (tw, embed_dim)
+    sh.update(text_param_shapes(transformer_width, transformer_layers, context_length, vocab_size))
+    sh["text_projection"] = (transformer_width, embed_dim)
     sh["logit_scale"] = ()
     return sh
 
@@ -125,15 +140,6 @@ def seeded_state_dict(seed=6, **arch):
     return _seeded(clip_param_shapes(**arch), seed)
 
 
-def text_param_shapes(width=768, layers=12, context_length=77, vocab_size=49408):
-    """State-dict keys and shapes of a text tower alone, as CLIPTextEngine takes it (the defaults are SD15_TEXT): no text_projection, no visual.*."""
-    sh = {"token_embedding.weight": (vocab_size, width), "positional_embedding": (context_length, width)}
-    for i in range(layers):
-        _block_shapes(sh, f"transformer.resblocks.{i}.", width)
-    sh["ln_final.weight"] = (width,); sh["ln_final.bias"] = (width,)
-    return sh
-
-
 def seeded_text_state_dict(seed=8, **arch):
     """seeded_state_dict's recipe on the keys of text_param_shapes.  `arch` is an architecture dictionary such as SD15_TEXT; the entries that are not
     shapes (heads, act, eps) are CLIPTextEngine's business and are ignored here."""
@@ -158,20 +164,34 @@ def _layers(sd, prefix):
     return 1 + max(int(k[len(prefix):].split(".")[0]) for k in sd if k.startswith(prefix))
 
 
+def _tower_to_hf(out, take, n, oa, hf):
+    """n layers of a tower into `out`: OpenAI names under `oa`, read through `take` -> transformers names under `hf`; in_proj split into q / k / v."""
+    for i in range(n):
+        a, h = f"{oa}{i}.", f"{hf}{i}."
+        for kind in ("weight", "bias"):
+            for name, part in zip("qkv", take(a + "attn.in_proj_" + kind).chunk(3, 0)):
+                out[h + f"self_attn.{name}_proj." + kind] = part.contiguous()
+            for x, y in _HF_BLOCK:
+                out[h + y + kind] = take(a + x + kind)
+
+
+def _tower_from_hf(out, take, n, oa, hf):
+    """The inverse of _tower_to_hf: transformers names under `hf`, read through `take` -> OpenAI names under `oa`; q / k / v copied into in_proj."""
+    for i in range(n):
+        a, h = f"{oa}{i}.", f"{hf}{i}."
+        for kind in ("weight", "bias"):
+            out[a + "attn.in_proj_" + kind] = torch.cat([take(h + f"self_attn.{name}_proj." + kind) for name in "qkv"]).contiguous()
+            for x, y in _HF_BLOCK:
+                out[a + x + kind] = take(h + y + kind)
+
+
 def to_hf_state(sd):
     """OpenAI names -> `transformers.CLIPModel` names: in_proj split into q / k / v, `visual.proj` / `text_projection` transposed into Linear weights."""
     out = {hf: sd[oa] for oa, hf in _HF_TOP}
     out["visual_projection.weight"] = sd["visual.proj"].t().contiguous()
     out["text_projection.weight"] = sd["text_projection"].t().contiguous()
     for oa, hf in _HF_TOWERS:
-        for i in range(_layers(sd, oa)):
-            a, h = f"{oa}{i}.", f"{hf}{i}."
-            for kind in ("weight", "bias"):
-                q, k, v = sd[a + "attn.in_proj_" + kind].chunk(3, 0)
-                out[h + "self_attn.q_proj." + kind], out[h + "self_attn.k_proj." + kind], out[h + "self_attn.v_proj." + kind] = \
-                    q.contiguous(), k.contiguous(), v.contiguous()
-                for x, y in _HF_BLOCK:
-                    out[h + y + kind] = sd[a + x + kind]
+        _tower_to_hf(out, sd.__getitem__, _layers(sd, oa), oa, hf)
     return out
 
 
@@ -183,17 +203,12 @@ def from_hf_state(sd, consume=False):
     out["visual.proj"] = take("visual_projection.weight").t().contiguous()
     out["text_projection"] = take("text_projection.weight").t().contiguous()
     for oa, hf in _HF_TOWERS:
-        for i in range(_layers(sd, hf)):
-            a, h = f"{oa}{i}.", f"{hf}{i}."
-            for kind in ("weight", "bias"):
-                out[a + "attn.in_proj_" + kind] = torch.cat([take(h + f"self_attn.{n}_proj." + kind) for n in "qkv"]).contiguous()
-                for x, y in _HF_BLOCK:
-                    out[a + x + kind] = take(h + y + kind)
+        _tower_from_hf(out, take, _layers(sd, hf), oa, hf)
     return out
 
 
-_HF_TEXT_TOP = tuple((oa, hf) for oa, hf in _HF_TOP if hf.startswith("text_model."))
 _HF_TEXT = "text_model."
+_HF_TEXT_TOP = tuple((oa, hf) for oa, hf in _HF_TOP if hf.startswith(_HF_TEXT))
 
 
 def with_text_prefix(sd):
@@ -207,14 +222,7 @@ def to_hf_text_state(sd, prefix=_HF_TEXT):
     checkpoints, or "" for a transformers whose CLIPTextModel has no such level)."""
     out = {prefix + hf[len(_HF_TEXT):]: sd[oa] for oa, hf in _HF_TEXT_TOP}
     oa, hf = _HF_TOWERS[1]
-    for i in range(_layers(sd, oa)):
-        a, h = f"{oa}{i}.", f"{prefix}{hf[len(_HF_TEXT):]}{i}."
-        for kind in ("weight", "bias"):
-            q, k, v = sd[a + "attn.in_proj_" + kind].chunk(3, 0)
-            out[h + "self_attn.q_proj." + kind], out[h + "self_attn.k_proj." + kind], out[h + "self_attn.v_proj." + kind] = \
-                q.contiguous(), k.contiguous(), v.contiguous()
-            for x, y in _HF_BLOCK:
-                out[h + y + kind] = sd[a + x + kind]
+    _tower_to_hf(out, sd.__getitem__, _layers(sd, oa), oa, prefix + hf[len(_HF_TEXT):])
     return out
 
 
@@ -227,56 +235,51 @@ def from_hf_text_state(sd):
         raise KeyError(f"text encoder state dict lacks {missing[:3]} (transformers.CLIPTextModel's key names)")
     out = {oa: sd[hf] for oa, hf in _HF_TEXT_TOP}
     oa, hf = _HF_TOWERS[1]
-    for i in range(_layers(sd, hf)):
-        a, h = f"{oa}{i}.", f"{hf}{i}."
-        for kind in ("weight", "bias"):
-            out[a + "attn.in_proj_" + kind] = torch.cat([sd[h + f"self_attn.{n}_proj." + kind] for n in "qkv"]).contiguous()
-            for x, y in _HF_BLOCK:
-                out[a + x + kind] = sd[h + y + kind]
+    _tower_from_hf(out, sd.__getitem__, _layers(sd, hf), oa, hf)
     return out
 
 
 # ---- geometry and tokens
-def resize_geometry(H, W, side=224):
-    """The sizes of clip's `_transform(side)` for an H x W frame -> (resized height, resized width, crop top, crop left): Resize puts the short side at
-    `side` and the long one at int(side * long / short); CenterCrop starts at int(round((size - side) / 2.0)).  (tcl_clip_resize_geometry is the
-    same rule on the C side.)"""
+def resize_geometry_rule(H, W, side=224, crop="round"):
+    """The sizes of the preprocessing for an H x W frame -> (resized height, resized width, crop top, crop left).  Resize puts the short side at
+    `side` and the long one at int(side * long / short).  The crop rule is named: "round" is clip's CenterCrop, which starts at
+    int(round((size - side) / 2.0)); "floor" is transformers' `center_crop` (image_transforms.py: top = (size - side) // 2), the rule of the
+    processor PickScore is fed by.  The two differ by one row or column when size - side is 2 (mod 4), e.g. 227 -> 224.
+    (tcl_clip_resize_geometry_rule is the same on the C side.)"""
+    if crop not in CROPS:
+        raise ValueError(f"crop must be one of {sorted(CROPS)}, got {crop!r}")
     short, long_ = (W, H) if W <= H else (H, W)
     new_long = int(side * long_ / short)
     oh, ow = (new_long, side) if W <= H else (side, new_long)
+    if crop == "floor":
+        return oh, ow, (oh - side) // 2, (ow - side) // 2
     return oh, ow, int(round((oh - side) / 2.0)), int(round((ow - side) / 2.0))
 
 
-def resize_geometry_rule(H, W, side=224, crop="round"):
-    """resize_geometry with the crop rule named: "round" is clip's CenterCrop above; "floor" is transformers' `center_crop` (image_transforms.py:
-    top = (size - side) // 2), the rule of the processor PickScore is fed by.  The resize is the same; the two crops differ by one row or column
-    when size - side is 2 (mod 4), e.g. 227 -> 224.  (tcl_clip_resize_geometry_rule is the same on the C side.)"""
-    if crop not in CROPS:
-        raise ValueError(f"crop must be one of {sorted(CROPS)}, got {crop!r}")
-    oh, ow, top, left = resize_geometry(H, W, side)
-    return (oh, ow, top, left) if crop == "round" else (oh, ow, (oh - side) // 2, (ow - side) // 2)
+def resize_geometry(H, W, side=224):
+    """The sizes of clip's `_transform(side)`: resize_geometry_rule with the rounded crop (as tcl_clip_resize_geometry on the C side)."""
+    return resize_geometry_rule(H, W, side, "round")
 
 
-def _stand_in_ids(text, room):
-    seed = int.from_bytes(hashlib.sha256(text.encode()).digest()[:4], "little")
-    n = min(room, max(1, len(text.replace(",", " , ").replace(".", " . ").split())))
-    return np.random.default_rng(seed).integers(1000, 40000, n).tolist()
+def _prompt_ids(prompt, tokenizer, allow_random, setting):
+    """-> (the prompt's ids, the start id, the end id) from any tokenizer with the HF CLIP interface (`tokenizer(txt, truncation=False,
+    add_special_tokens=False)["input_ids"]`, `.bos_token_id`, `.eos_token_id`).  tokenizer None: an error naming `setting`, the caller's configuration
+    entry, unless `allow_random`, which gives a deterministic text-seeded id sequence (one id per word) with a warning."""
+    if tokenizer is not None:
+        return list(tokenizer(prompt, truncation=False, add_special_tokens=False)["input_ids"]), int(tokenizer.bos_token_id), int(tokenizer.eos_token_id)
+    if not allow_random:
+        raise FileNotFoundError(f"no CLIP tokenizer (models.{setting} / --{setting}); set models.allow_random / "
+                                "TCL_ALLOW_RANDOM_WEIGHTS=1 for deterministic stand-in token ids")
+    warnings.warn("CLIP tokenizer not found -> deterministic text-seeded stand-in token ids (allow_random)")
+    seed = int.from_bytes(hashlib.sha256(prompt.encode()).digest()[:4], "little")
+    n = max(1, len(prompt.replace(",", " , ").replace(".", " . ").split()))
+    return np.random.default_rng(seed).integers(1000, 40000, n).tolist(), SOT, EOT
 
 
 def tokenize(prompt, tokenizer, context=77, allow_random=False):
-    """clip.tokenize([prompt]) from any tokenizer with the HF CLIP interface (`tokenizer(txt, truncation=False, add_special_tokens=False)["input_ids"]`,
-    `.bos_token_id`, `.eos_token_id`): int64 [1, context] = [SOT] + ids + [EOT], zero-padded.  RuntimeError when the prompt does not fit, as
-    clip.tokenize raises (the caller then splits on '.', evaluate.py:43-49).  tokenizer None: an error unless `allow_random`, which gives a
-    deterministic text-seeded id sequence (one id per word) with a warning."""
-    if tokenizer is None:
-        if not allow_random:
-            raise FileNotFoundError("no CLIP tokenizer (models.clip_tokenizer / --clip_tokenizer); set models.allow_random / "
-                                    "TCL_ALLOW_RANDOM_WEIGHTS=1 for deterministic stand-in token ids")
-        warnings.warn("CLIP tokenizer not found -> deterministic text-seeded stand-in token ids (allow_random)")
-        ids, sot, eot = _stand_in_ids(prompt, 10 ** 9), SOT, EOT
-    else:
-        ids = list(tokenizer(prompt, truncation=False, add_special_tokens=False)["input_ids"])
-        sot, eot = int(tokenizer.bos_token_id), int(tokenizer.eos_token_id)
+    """clip.tokenize([prompt]): int64 [1, context] = [SOT] + ids + [EOT], zero-padded.  RuntimeError when the prompt does not fit, as clip.tokenize
+    raises (the caller then splits on '.', evaluate.py:43-49).  `tokenizer` and `allow_random`: see _prompt_ids."""
+    ids, sot, eot = _prompt_ids(prompt, tokenizer, allow_random, "clip_tokenizer")
     if len(ids) + 2 > context:
         raise RuntimeError(f"Input {prompt!r} is too long for context length {context}")
     out = torch.zeros(1, context, dtype=torch.int64)
@@ -286,17 +289,9 @@ def tokenize(prompt, tokenizer, context=77, allow_random=False):
 
 def tokenize_truncated(prompt, tokenizer, context=77, allow_random=False):
     """`processor(text=prompt, padding=True, truncation=True, max_length=context)` on one prompt (eval_utils.py:163-176 pick_score_func): int64
-    [1, n + 2] = [SOT] + ids[:context - 2] + [EOT], unpadded (one prompt is its own longest) and truncated, so nothing is "too long".  tokenizer None:
-    as in `tokenize`."""
-    if tokenizer is None:
-        if not allow_random:
-            raise FileNotFoundError("no CLIP tokenizer (models.pick_tokenizer / --pick_tokenizer); set models.allow_random / "
-                                    "TCL_ALLOW_RANDOM_WEIGHTS=1 for deterministic stand-in token ids")
-        warnings.warn("CLIP tokenizer not found -> deterministic text-seeded stand-in token ids (allow_random)")
-        ids, sot, eot = _stand_in_ids(prompt, 10 ** 9), SOT, EOT
-    else:
-        ids = list(tokenizer(prompt, truncation=False, add_special_tokens=False)["input_ids"])
-        sot, eot = int(tokenizer.bos_token_id), int(tokenizer.eos_token_id)
+    [1, n + 2] = [SOT] + ids[:context - 2] + [EOT], unpadded (one prompt is its own longest) and truncated, so nothing is "too long".  `tokenizer`
+    and `allow_random`: see _prompt_ids."""
+    ids, sot, eot = _prompt_ids(prompt, tokenizer, allow_random, "pick_tokenizer")
     return torch.tensor([[sot] + ids[:max(0, context - 2)] + [eot]], dtype=torch.int64)
 
 
@@ -308,22 +303,40 @@ def load_tokenizer(tok_dir):
 
 
 # ---- the engine
+HEAD_DIMS = tuple(range(16, 129, 16))                                    # what tcl_clip_attention_f16 takes
+_HF_FIELDS = ("num_attention_heads", "hidden_act", "layer_norm_eps")     # a transformers config.json's names for heads, act, eps
+
+
+def _check_tower(width, heads, act, eps=1e-5, head_dims=HEAD_DIMS, fields=("heads", "act", "eps"), where=""):
+    """What the kernels cover in one tower: a head count that divides the width into a head_dim of `head_dims`, an activation of ACTS, LayerNorms
+    at the eps they are tested at.  ValueError naming the field as the caller's source spells it (`fields`; `where` says which tower)."""
+    if not isinstance(heads, int) or heads <= 0 or width % heads or width // heads not in head_dims:
+        raise ValueError(f"{fields[0]}{where}: {heads!r} heads on width {width}; head_dim must be one of {list(head_dims)} (tcl_clip_attention_f16)")
+    if act not in ACTS:
+        raise ValueError(f"{fields[1]}{where}: {act!r}; the engine runs one of {sorted(ACTS)}")
+    if abs(float(eps) - 1e-5) > 1e-12:
+        raise ValueError(f"{fields[2]}{where}: {eps!r}; the engine's LayerNorms are tested at 1e-5")
+
+
+def _h16(t, dev):
+    return t.to(H16).contiguous().to(dev)
+
+
 class _Tower:
-    def __init__(self, sd, prefix, dev, heads=None):
-        self.layers = []
-        for i in range(_layers(sd, prefix)):
-            p = f"{prefix}{i}."
-            self.layers.append({k: sd[p + k].to(H16).contiguous().to(dev) for k in (
-                "ln_1.weight", "ln_1.bias", "attn.in_proj_weight", "attn.in_proj_bias", "attn.out_proj.weight", "attn.out_proj.bias",
-                "ln_2.weight", "ln_2.bias", "mlp.c_fc.weight", "mlp.c_fc.bias", "mlp.c_proj.weight", "mlp.c_proj.bias")})
-        self.width = self.layers[0]["ln_1.weight"].numel()
+    """The blocks' weights of one tower in f16 on the device, its width and head count (None: width // 64).  Refuses before anything is moved."""
+
+    def __init__(self, sd, prefix, dev, heads, act):
+        self.width = sd[prefix + "0.ln_1.weight"].numel()
         self.heads = self.width // HEAD_DIM if heads is None else int(heads)
-        if self.heads <= 0 or self.width % self.heads or (self.width // self.heads) % 16 or self.width // self.heads > 128:
-            raise ValueError(f"{prefix}: {heads} heads on width {self.width} (tcl_clip_attention_f16 takes a head_dim that is a multiple of 16 up to 128)")
+        _check_tower(self.width, self.heads, act, where=f" of {prefix}")
+        self.layers = [{k: _h16(sd[f"{prefix}{i}.{k}"], dev) for k in _BLOCK_KEYS} for i in range(_layers(sd, prefix))]
 
 
 class _Blocks:
-    """The launches both engines are made of.  Expects self.dev, self.L, self.act and self.eps (the LayerNorms')."""
+    """The launches both engines are made of, on `dev`: GEMM, LayerNorm at `eps`, attention, and the block sequence of a _Tower with `act`."""
+
+    def __init__(self, dev, act, eps):
+        self.dev, self.L, self.act, self.eps = torch.device(dev), lib(), act, float(eps)
 
     def _gemm(self, x, w, bias, resid, M, act=0):
         N, K = w.shape
@@ -355,17 +368,41 @@ class _Blocks:
             x = self._gemm(u, p["mlp.c_proj.weight"], p["mlp.c_proj.bias"], x, M)
         return x
 
-    def _token_rows(self, ids):
-        """ids int [B, T], checked -> (token + positional embedding rows [B*T, W] f16, B, T).  Expects self.table, self.tpos, self.vocab, self.context."""
+
+class _TextTower(_Blocks):
+    """A CLIP text tower on the device, from a state dict in f32 with OpenAI's names: the token table, the positional rows, the causal blocks
+    (`tower`) and ln_final.  What is read off the blocks' output -- one row or all -- is its user's business."""
+
+    def __init__(self, sd, dev, heads, act, eps):
+        self.tower = _Tower(sd, "transformer.resblocks.", dev, heads, act)
+        super().__init__(dev, act, eps)
+        self.table, self.tpos = _h16(sd["token_embedding.weight"], self.dev), _h16(sd["positional_embedding"], self.dev)
+        self.vocab, self.width = self.table.shape
+        self.context = self.tpos.shape[0]
+        self.ln_final = (_h16(sd["ln_final.weight"], self.dev), _h16(sd["ln_final.bias"], self.dev))
+        if self.width % 64:
+            raise ValueError(f"text width {self.width} must be a multiple of 64 (tcl_gemm_f16's K)")
+
+    def blocks(self, ids):
+        """ids int [B, T], 1 <= T <= context, inside the vocabulary (ValueError otherwise) -> (the rows after the last block [B*T, width] f16, B, T):
+        token + positional embedding, then the causal blocks."""
         if ids.dim() != 2 or not 1 <= ids.shape[1] <= self.context:
             raise ValueError(f"token ids must be [B, T] with 1 <= T <= {self.context}, got {tuple(ids.shape)}")
         if int(ids.min()) < 0 or int(ids.max()) >= self.vocab:
             raise ValueError(f"token ids outside the vocabulary [0, {self.vocab})")
-        B, T, W = ids.shape[0], ids.shape[1], self.table.shape[1]
+        B, T = ids.shape
         i32 = ids.to(self.dev).to(torch.int32).contiguous()
-        x = torch.empty(B * T, W, dtype=H16, device=self.dev)
-        self.L.tcl_clip_embed_f16(0, 0, i32, self.table, self.tpos, 0, 0, x, B, T, W, self.vocab, self.eps, stream())
-        return x, B, T
+        x = torch.empty(B * T, self.width, dtype=H16, device=self.dev)
+        self.L.tcl_clip_embed_f16(0, 0, i32, self.table, self.tpos, 0, 0, x, B, T, self.width, self.vocab, self.eps, stream())
+        return self._blocks(x, self.tower, B, T, True), B, T
+
+
+def nhwc_u8(frames):
+    """Frames (numpy or tensor, any device) as a tensor, checked to be uint8 [N,H,W,3]."""
+    t = frames if isinstance(frames, torch.Tensor) else torch.as_tensor(np.asarray(frames))
+    if t.dim() != 4 or t.shape[-1] != 3 or t.dtype != torch.uint8:
+        raise ValueError(f"frames must be uint8 [N,H,W,3], got {t.dtype} {tuple(t.shape)}")
+    return t
 
 
 class CLIPEngine(_Blocks):
@@ -375,21 +412,15 @@ class CLIPEngine(_Blocks):
     transformers' image processor).  The defaults are OpenAI's CLIP."""
 
     def __init__(self, state_dict, device, vision_heads=None, text_heads=None, act="quick_gelu", crop="round"):
-        if act not in ACTS:
-            raise ValueError(f"act must be one of {sorted(ACTS)}, got {act!r}")
         if crop not in CROPS:
             raise ValueError(f"crop must be one of {sorted(CROPS)}, got {crop!r}")
-        self.act, self.crop, self.eps = act, crop, 1e-5
         missing =[k for k in ("visual.conv1.weight", "visual.proj", "token_embedding.weight", "text_projection", "ln_final.weight") if k not in state_dict]
         if missing:
             raise KeyError(f"CLIP state dict lacks {missing} (OpenAI key names; a transformers checkpoint goes through from_hf_state)")
-        self.dev, self.L = torch.device(device), lib()
         sd = {k: v.float() for k, v in state_dict.items() if torch.is_tensor(v)}
-        d = self.dev
-
-        def h(k):
-            return sd[k].to(H16).contiguous().to(d)
-
+        self.visual = _Tower(sd, "visual.transformer.resblocks.", device, vision_heads, act)
+        super().__init__(device, act, 1e-5)
+        self.crop, d = crop, self.dev
         w = sd["visual.conv1.weight"]
         self.vwidth, self.patch = w.shape[0], w.shape[-1]
         self.kpatch = 3 * self.patch * self.patch
@@ -399,21 +430,17 @@ class CLIPEngine(_Blocks):
         self.conv1 = conv1.to(d)
         self.grid = int(round(math.sqrt(sd["visual.positional_embedding"].shape[0] - 1)))
         self.side = self.grid * self.patch
-        self.cls, self.vpos = h("visual.class_embedding"), h("visual.positional_embedding")
-        self.ln_pre = (h("visual.ln_pre.weight"), h("visual.ln_pre.bias"))
-        self.ln_post = (h("visual.ln_post.weight"), h("visual.ln_post.bias"))
-        self.vproj = sd["visual.proj"].t().to(H16).contiguous().to(d)                               # [embed, width]
-        self.visual = _Tower(sd, "visual.transformer.resblocks.", d, vision_heads)
-        self.table, self.tpos = h("token_embedding.weight"), h("positional_embedding")
-        self.vocab, self.twidth = self.table.shape
-        self.context = self.tpos.shape[0]
-        self.ln_final = (h("ln_final.weight"), h("ln_final.bias"))
-        self.tproj = sd["text_projection"].t().to(H16).contiguous().to(d)
-        self.text = _Tower(sd, "transformer.resblocks.", d, text_heads)
+        self.cls, self.vpos = _h16(sd["visual.class_embedding"], d), _h16(sd["visual.positional_embedding"], d)
+        self.ln_pre = (_h16(sd["visual.ln_pre.weight"], d), _h16(sd["visual.ln_pre.bias"], d))
+        self.ln_post = (_h16(sd["visual.ln_post.weight"], d), _h16(sd["visual.ln_post.bias"], d))
+        self.vproj = _h16(sd["visual.proj"].t(), d)                                                 # [embed, width]
+        self.ttower = _TextTower(sd, d, text_heads, act, self.eps)
+        self.text, self.twidth, self.context = self.ttower.tower, self.ttower.width, self.ttower.context
+        self.tproj = _h16(sd["text_projection"].t(), d)
         self.embed_dim = self.vproj.shape[0]
         self.logit_scale = float(sd["logit_scale"]) if "logit_scale" in sd else None               # the log, as stored (CLIP.logit_scale)
-        if self.vwidth % 64 or self.twidth % 64:
-            raise ValueError(f"widths {self.vwidth} / {self.twidth} must be multiples of 64 (tcl_gemm_f16's K)")
+        if self.vwidth % 64:
+            raise ValueError(f"vision width {self.vwidth} must be a multiple of 64 (tcl_gemm_f16's K)")
 
     # ---- the two encoders
     def preprocess(self, frames_u8, want_crop=False):
@@ -435,7 +462,7 @@ class CLIPEngine(_Blocks):
         T, W = self.grid * self.grid + 1, self.vwidth
         emb = self._gemm(patches, self.conv1, None, None, B * (T - 1))
         x = torch.empty(B * T, W, dtype=H16, device=self.dev)
-        self.L.tcl_clip_embed_f16(emb, self.cls, 0, 0, self.vpos, self.ln_pre[0], self.ln_pre[1], x, B, T, W, 0, 1e-5, stream())
+        self.L.tcl_clip_embed_f16(emb, self.cls, 0, 0, self.vpos, self.ln_pre[0], self.ln_pre[1], x, B, T, W, 0, self.eps, stream())
         x = self._blocks(x, self.visual, B, T, False)
         c = self._ln(x.view(B, T, W)[:, 0].contiguous(), self.ln_post, B, W)
         return self._gemm(c, self.vproj, None, None, B).float()
@@ -443,9 +470,7 @@ class CLIPEngine(_Blocks):
     @torch.no_grad()
     def encode_image(self, frames_u8, batch=64):
         """CLIP.encode_image(preprocess(frame)) for uint8 frames [N,H,W,3] (numpy or tensor, any device) -> [N, embed_dim] f32 on the device."""
-        t = frames_u8 if isinstance(frames_u8, torch.Tensor) else torch.as_tensor(np.asarray(frames_u8))
-        if t.dim() != 4 or t.shape[-1] != 3 or t.dtype != torch.uint8:
-            raise ValueError(f"frames must be uint8 [N,H,W,3], got {t.dtype} {tuple(t.shape)}")
+        t = nhwc_u8(frames_u8)
         out = []
         for s in range(0, t.shape[0], max(1, batch)):
             f = t[s:s + batch].to(self.dev).contiguous()
@@ -458,47 +483,30 @@ class CLIPEngine(_Blocks):
         """CLIP.encode_text: ids int [B, T], 1 <= T <= context (clip.tokenize's padded layout, or tokenize_truncated's unpadded row, which uses the
         first T positional rows) -> [B, embed_dim] f32 on the device: the row of the end-of-text token, the largest id of its row."""
         ids = torch.as_tensor(ids)
-        x, B, T = self._token_rows(ids)
+        x, B, T = self.ttower.blocks(ids)
         W = self.twidth
-        x = self._blocks(x, self.text, B, T, True)
         eot = ids.to(self.dev).argmax(-1)
-        c = self._ln(x.view(B, T, W)[torch.arange(B, device=self.dev), eot].contiguous(), self.ln_final, B, W)
+        c = self._ln(x.view(B, T, W)[torch.arange(B, device=self.dev), eot].contiguous(), self.ttower.ln_final, B, W)
         return self._gemm(c, self.tproj, None, None, B).float()
 
 
-class CLIPTextEngine(_Blocks):
+class CLIPTextEngine(_TextTower):
     """A CLIP text tower alone, read at every position: `transformers.CLIPTextModel(...).last_hidden_state`, what SD-1.5 conditions its UNet on
     (SD15_TEXT: the text tower of CLIP ViT-L/14).  The state dict holds token_embedding.weight, positional_embedding, transformer.resblocks.* and
     ln_final.* in OpenAI's names (a transformers checkpoint goes through from_hf_text_state); a text_projection or an image tower is not needed and
     not read.  heads None: width // 64; act: "quick_gelu" or "gelu"; eps: the LayerNorms'."""
 
     def __init__(self, state_dict, device, heads=None, act="quick_gelu", eps=1e-5):
-        if act not in ACTS:
-            raise ValueError(f"act must be one of {sorted(ACTS)}, got {act!r}")
-        self.act, self.eps = act, float(eps)
         missing = [k for k in ("token_embedding.weight", "positional_embedding", "ln_final.weight", "ln_final.bias") if k not in state_dict]
         if missing:
             raise KeyError(f"CLIP text state dict lacks {missing} (OpenAI key names; a transformers checkpoint goes through from_hf_text_state)")
-        self.dev, self.L = torch.device(device), lib()
-        sd = {k: v.float() for k, v in state_dict.items() if torch.is_tensor(v)}
-
-        def h(k):
-            return sd[k].to(H16).contiguous().to(self.dev)
-
-        self.table, self.tpos = h("token_embedding.weight"), h("positional_embedding")
-        self.vocab, self.width = self.table.shape
-        self.context = self.tpos.shape[0]
-        self.ln_final = (h("ln_final.weight"), h("ln_final.bias"))
-        self.text = _Tower(sd, "transformer.resblocks.", self.dev, heads)
-        if self.width % 64:
-            raise ValueError(f"width {self.width} must be a multiple of 64 (tcl_gemm_f16's K)")
+        super().__init__({k: v.float() for k, v in state_dict.items() if torch.is_tensor(v)}, device, heads, act, eps)
 
     @torch.no_grad()
     def hidden_states(self, ids):
         """ids int [B, T], 1 <= T <= context -> [B, T, width] f16 on the device: token + positional embedding, the causal blocks, ln_final on every
         row; no projection and no pooling.  Row t depends on ids[:, :t + 1] only."""
-        x, B, T = self._token_rows(torch.as_tensor(ids))
-        x = self._blocks(x, self.text, B, T, True)
+        x, B, T = self.blocks(torch.as_tensor(ids))
         return self._ln(x, self.ln_final, B * T, self.width).view(B, T, self.width)
 
 
@@ -539,25 +547,18 @@ def pick_options(config=None, vision_width=None, text_width=None, patch=None):
     text_config: num_attention_heads, hidden_act, layer_norm_eps, patch_size; a field that is absent has transformers' default), else PICKSCORE_V1.
     ValueError, naming the field, for what the kernels do not cover: an activation other than quick_gelu / gelu, a head_dim outside {64, 80}, a
     LayerNorm eps other than 1e-5, and a patch_size that is not the checkpoint's.  Host-side: no device is touched."""
-    A = PICKSCORE_V1
+    A, D = PICKSCORE_V1, _HF_DEFAULTS
     vw, tw = vision_width or A["vision_width"], text_width or A["transformer_width"]
-    if config is None:
-        heads, acts, eps, psz = (A["vision_heads"], A["text_heads"]), (A["act"], A["act"]), (A["eps"], A["eps"]), A["vision_patch_size"]
-    else:
-        vc, tc = config.get("vision_config") or {}, config.get("text_config") or {}
-        D = _HF_DEFAULTS
-        heads = (vc.get("num_attention_heads", D["num_attention_heads"][0]), tc.get("num_attention_heads", D["num_attention_heads"][1]))
-        acts = (vc.get("hidden_act", D["hidden_act"]), tc.get("hidden_act", D["hidden_act"]))
-        eps = (vc.get("layer_norm_eps", D["layer_norm_eps"]), tc.get("layer_norm_eps", D["layer_norm_eps"]))
-        psz = vc.get("patch_size", D["patch_size"])
-    if acts[0] != acts[1] or acts[0] not in ACTS:
-        raise ValueError(f"hidden_act {acts[0]!r} (vision) / {acts[1]!r} (text): the engine runs one of {sorted(ACTS)} in both towers")
-    for tower, w, h in (("vision", vw, heads[0]), ("text", tw, heads[1])):
-        if not isinstance(h, int) or h <= 0 or w % h or w // h not in (64, 80):
-            raise ValueError(f"num_attention_heads {h!r} on the {tower} width {w}: head_dim must be 64 or 80 (what tcl_clip_attention_f16 is tested at)")
-    for tower, e in zip(("vision", "text"), eps):
-        if abs(float(e) - 1e-5) > 1e-12:
-            raise ValueError(f"layer_norm_eps {e!r} ({tower}): the engine's LayerNorms run at 1e-5")
+    config = to_hf_config(A) if config is None else config
+    vc, tc = config.get("vision_config") or {}, config.get("text_config") or {}
+    heads = (vc.get("num_attention_heads", D["num_attention_heads"][0]), tc.get("num_attention_heads", D["num_attention_heads"][1]))
+    acts = (vc.get("hidden_act", D["hidden_act"]), tc.get("hidden_act", D["hidden_act"]))
+    eps = (vc.get("layer_norm_eps", D["layer_norm_eps"]), tc.get("layer_norm_eps", D["layer_norm_eps"]))
+    psz = vc.get("patch_size", D["patch_size"])
+    if acts[0] != acts[1]:
+        raise ValueError(f"hidden_act {acts[0]!r} (vision) / {acts[1]!r} (text): the engine runs one activation in both towers")
+    for tower, w, h, a, e in zip(("vision", "text"), (vw, tw), heads, acts, eps):                 # head_dim 64 / 80: what the engine is tested at
+        _check_tower(w, h, a, e, (64, 80), _HF_FIELDS, f" ({tower})")
     if patch is not None and int(psz) != int(patch):
         raise ValueError(f"patch_size {psz!r} of the config, but the checkpoint's patch embedding is {patch} x {patch}")
     return dict(vision_heads=int(heads[0]), text_heads=int(heads[1]), act=acts[0], crop="floor")
@@ -591,12 +592,7 @@ def text_options(config=None):
     w, h = c["hidden_size"], c["num_attention_heads"]
     if not isinstance(w, int) or w <= 0 or w % 64:
         raise ValueError(f"hidden_size {w!r}: the width must be a positive multiple of 64 (tcl_gemm_f16's K)")
-    if not isinstance(h, int) or h <= 0 or w % h or (w // h) % 16 or w // h > 128:
-        raise ValueError(f"num_attention_heads {h!r} on hidden_size {w}: head_dim must be a multiple of 16 up to 128 (tcl_clip_attention_f16)")
-    if c["hidden_act"] not in ACTS:
-        raise ValueError(f"hidden_act {c['hidden_act']!r}: the engine runs one of {sorted(ACTS)}")
-    if abs(float(c["layer_norm_eps"]) - 1e-5) > 1e-12:
-        raise ValueError(f"layer_norm_eps {c['layer_norm_eps']!r}: the engine's LayerNorms are tested at 1e-5")
+    _check_tower(w, h, c["hidden_act"], c["layer_norm_eps"], fields=_HF_FIELDS)
     if c["intermediate_size"] != 4 * w:
         raise ValueError(f"intermediate_size {c['intermediate_size']!r}: the MLP must be 4 x hidden_size = {4 * w} wide")
     return (dict(heads=h, act=c["hidden_act"], eps=1e-5),

@@ -27,6 +27,7 @@ import os
 import numpy as np
 import torch
 
+from . import clip
 from .lib import lib, stream
 from .memflow import _pad8
 from .raft import estimate_flows_raft
@@ -127,13 +128,6 @@ def warp_ssim_from_flows(edit_u8, fut, past, batch=4):
     return float(np.mean(per)), per
 
 
-def _nhwc_u8(frames):
-    t = torch.as_tensor(np.asarray(frames)) if not isinstance(frames, torch.Tensor) else frames
-    if t.dim() != 4 or t.shape[-1] != 3 or t.dtype != torch.uint8:
-        raise ValueError(f"frames must be uint8 [N,H,W,3], got {t.dtype} {tuple(t.shape)}")
-    return t
-
-
 def resize_like(source_u8, H, W):
     """PIL Image.resize((W, H)) with its default filter on every frame (evaluate.py:34-35), uint8 [N,h,w,3] -> [N,H,W,3]."""
     from PIL import Image
@@ -146,7 +140,7 @@ def warp_ssim(edit_u8, source_u8, raft_engine, batch=4):
     """The reference's SaveWarpingImage with RAFT flows (flow lists None): edit_u8 / source_u8 uint8 [N,H,W,3] (numpy or tensors) ->
     (warp-error-ssim, per-pair float64 array).  Source frames of another size are resized to the edit size first (PIL, default filter)."""
     from .raft import check_size
-    edit, src = _nhwc_u8(edit_u8), _nhwc_u8(source_u8)
+    edit, src = clip.nhwc_u8(edit_u8), clip.nhwc_u8(source_u8)
     N, H, W = edit.shape[:3]
     if N < 2 or len(src) < N:
         raise ValueError(f"warp-error-ssim needs at least 2 edit frames and as many source frames, got {N} / {len(src)}")
@@ -166,11 +160,15 @@ def warp_ssim(edit_u8, source_u8, raft_engine, batch=4):
 
 
 # ---- the CLIP figures
+def _features(edit_u8, engine, batch, features):
+    """The image features of the frames (encode_image checks them: uint8 [N,H,W,3]), unless the caller has them already."""
+    return engine.encode_image(edit_u8, batch=batch) if features is None else features
+
+
 @torch.no_grad()
 def clip_frame(edit_u8, engine, batch=64, features=None):
     """eu.clip_frame (eval_utils.py:146-161): the sum of the off-diagonal cosines between the frame features / (N (N - 1)).  edit_u8 uint8 [N,H,W,3]."""
-    from . import clip
-    feats = engine.encode_image(_nhwc_u8(edit_u8), batch=batch) if features is None else features
+    feats = _features(edit_u8, engine, batch, features)
     if feats.shape[0] < 2:
         raise ValueError(f"clip-frame needs at least 2 frames, got {feats.shape[0]}")
     return clip.scores(feats)[0]
@@ -179,23 +177,21 @@ def clip_frame(edit_u8, engine, batch=64, features=None):
 def prompt_id_rows(prompt, tokenizer, context=77, allow_random=False):
     """The token rows clip-text is computed from: the whole prompt when it fits the context, else (evaluate.py:43-49) its non-empty parts between
     full stops, whose scores are averaged."""
-    from .clip import tokenize
     try:
-        return [tokenize(prompt, tokenizer, context, allow_random)]
+        return [clip.tokenize(prompt, tokenizer, context, allow_random)]
     except RuntimeError:
         print(f"[WARN] Prompt too long: '{prompt}', splitting.")
-        return [tokenize(p, tokenizer, context, allow_random) for p in prompt.split(".") if p.strip()]
+        return [clip.tokenize(p, tokenizer, context, allow_random) for p in prompt.split(".") if p.strip()]
 
 
 def _text_score(feats, ids, engine):
-    from . import clip
     return clip.scores(feats, engine.encode_text(ids)[0])[1]
 
 
 @torch.no_grad()
 def clip_text(edit_u8, prompt, engine, tokenizer, allow_random=False, batch=64, features=None):
     """eu.clip_text (eval_utils.py:129-144) with evaluate.py:41-49's fallback: the mean cosine of the frame features to the prompt's text feature."""
-    feats = engine.encode_image(_nhwc_u8(edit_u8), batch=batch) if features is None else features
+    feats = _features(edit_u8, engine, batch, features)
     rows = prompt_id_rows(prompt, tokenizer, engine.context, allow_random)
     if not rows:
         raise ValueError(f"empty prompt {prompt!r}: nothing to score")
@@ -207,10 +203,9 @@ def clip_text(edit_u8, prompt, engine, tokenizer, allow_random=False, batch=64, 
 def pick_score(edit_u8, prompt, engine, tokenizer, allow_random=False, batch=64, features=None):
     """eu.pick_score_func (eval_utils.py:163-176) averaged over the frames (evaluate.py:52-56): exp(logit_scale) times the cosine of the prompt's
     text embedding to every frame's image embedding.  `engine` is clip.pick_engine's; `features` are its image features when already computed."""
-    from . import clip
     if engine.logit_scale is None:
         raise ValueError("pick-score needs the checkpoint's logit_scale, which this state dict lacks")
-    feats = engine.encode_image(_nhwc_u8(edit_u8), batch=batch) if features is None else features
+    feats = _features(edit_u8, engine, batch, features)
     ids = clip.tokenize_truncated(prompt, tokenizer, engine.context, allow_random)
     return clip.pick_scores(feats, engine.encode_text(ids)[0], engine.logit_scale)[0]
 
@@ -224,7 +219,7 @@ def frame_lpips(edit_u8, source_u8, engine, batch=4):
     (InputPadder) before the distance.  Source frames of another size are resized to the edit size first, as for the other figures.  `engine` is a
     lpips.LPIPSEngine; `batch` pairs run at a time."""
     from .lpips import pad8_u8
-    edit, src = _nhwc_u8(edit_u8), _nhwc_u8(source_u8)
+    edit, src = clip.nhwc_u8(edit_u8), clip.nhwc_u8(source_u8)
     N, H, W = edit.shape[:3]
     if N < 2 or len(src) < N - 1:
         raise ValueError(f"frame-lpips leaves the last frame out: it needs at least 2 edit frames and one source frame fewer, got {N} / {len(src)}")

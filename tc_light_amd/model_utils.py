@@ -8,6 +8,7 @@ A missing or mistyped weight path raises FileNotFoundError: the engine never sil
 tensors of the same architecture (bench / tests: no network, no checkpoints in the images) must be asked for explicitly with
 `models.allow_random: true` in the YAML or `TCL_ALLOW_RANDOM_WEIGHTS=1` in the environment.
 """
+import json
 import os
 import warnings
 
@@ -36,6 +37,25 @@ def _missing(what, path, allow):
 def _load_safetensors(path):
     from safetensors.torch import load_file
     return load_file(path)
+
+
+def _plain(raw):
+    """A loaded checkpoint -> plain {name: tensor}: a `state_dict` level unwrapped and DataParallel's `module.` prefix stripped, where there is one."""
+    raw = raw["state_dict"] if isinstance(raw.get("state_dict"), dict) else raw
+    return {(k[7:] if k.startswith("module.") else k): v for k, v in raw.items()}
+
+
+def _read_state(path):
+    """A weight file (`.safetensors`, else a pickled tensor dict) -> plain {name: tensor} on the CPU, the tensors in their stored dtype."""
+    return _plain(_load_safetensors(path) if path.endswith(".safetensors") else torch.load(path, map_location="cpu", weights_only=True))
+
+
+def _read_config(directory):
+    """The config.json dictionary of a snapshot directory, or None when it has none."""
+    cfg = os.path.join(directory, "config.json")
+    if os.path.isfile(cfg):
+        with open(cfg) as f:
+            return json.load(f)
 
 
 def _with_lora(sd, lora):
@@ -98,8 +118,7 @@ def load_memflow_state(path=None, seed=4, allow=False):
     if not (path and os.path.exists(path)):
         _missing("MemFlowNet", path, allow)
         return memflow.seeded_state_dict(memflow.memflow_param_shapes(), seed)
-    raw = torch.load(path, map_location="cpu", weights_only=True)
-    return {(k[7:] if k.startswith("module.") else k): v for k, v in raw.items()}
+    return _read_state(path)
 
 
 def load_raft_state(path=None, seed=5, allow=False):
@@ -108,8 +127,7 @@ def load_raft_state(path=None, seed=5, allow=False):
     if not (path and os.path.exists(path)):
         _missing("RAFT", path, allow)
         return raft.seeded_state_dict(seed)
-    raw = torch.load(path, map_location="cpu", weights_only=True)
-    return {(k[7:] if k.startswith("module.") else k): v for k, v in raw.items()}
+    return _read_state(path)
 
 
 def load_clip_state(path=None, seed=6, allow=False):
@@ -120,13 +138,11 @@ def load_clip_state(path=None, seed=6, allow=False):
         _missing("CLIP", path, allow)
         return clip.seeded_state_dict(seed)
     if path.endswith(".safetensors"):
-        return clip.from_hf_state({k: v for k, v in _load_safetensors(path).items()})
+        return clip.from_hf_state(_read_state(path))
     try:
-        raw = torch.jit.load(path, map_location="cpu").state_dict()
+        sd = _plain(torch.jit.load(path, map_location="cpu").state_dict())
     except RuntimeError:
-        raw = torch.load(path, map_location="cpu", weights_only=True)
-        raw = raw.get("state_dict", raw) if isinstance(raw, dict) else raw
-    sd = {(k[7:] if k.startswith("module.") else k): v for k, v in raw.items()}
+        sd = _read_state(path)
     return clip.from_hf_state(sd) if "visual_projection.weight" in sd else sd
 
 
@@ -136,17 +152,13 @@ def load_pick_state(path=None, seed=7, allow=False):
     the shards model-0000x-of-0000y.safetensors with model.safetensors.index.json, or pytorch_model.bin) or a single .safetensors / .bin file.  The
     tensors keep their stored dtype and the transformers-named ones are released as they are renamed: the 3.9 GB f32 checkpoint is held once."""
     import glob
-    import json
     from . import clip
     if not (path and os.path.exists(path)):
         _missing("PickScore", path, allow)
         return clip.seeded_state_dict(seed, **clip.arch_shapes(clip.PICKSCORE_V1)), None
     config, files = None, [path]
     if os.path.isdir(path):
-        cfg = os.path.join(path, "config.json")
-        if os.path.isfile(cfg):
-            with open(cfg) as f:
-                config = json.load(f)
+        config = _read_config(path)
         index = os.path.join(path, "model.safetensors.index.json")
         if os.path.isfile(index):
             with open(index) as f:
@@ -160,8 +172,7 @@ def load_pick_state(path=None, seed=7, allow=False):
                                                                        "no model.safetensors, shards or pytorch_model.bin"))
     raw = {}
     for p in files:
-        part = _load_safetensors(p) if p.endswith(".safetensors") else torch.load(p, map_location="cpu", weights_only=True)
-        raw.update(part.get("state_dict", part) if not p.endswith(".safetensors") and isinstance(part, dict) else part)
+        raw.update(_read_state(p))
     if "visual_projection.weight" not in raw:
         raise KeyError(f"{path!r} does not hold a transformers.CLIPModel (no visual_projection.weight)")
     return clip.from_hf_state(raw, consume=True), config
@@ -180,9 +191,7 @@ def load_lpips_state(vgg_path=None, lin_path=None, allow=False, seed=8):
             stand_in = lpips.seeded_state(seed)
             sd.update({k: stand_in[k] for k in shapes})
             continue
-        raw = _load_safetensors(path) if path.endswith(".safetensors") else torch.load(path, map_location="cpu", weights_only=True)
-        raw = raw.get("state_dict", raw) if isinstance(raw, dict) else raw
-        raw = {(k[7:] if k.startswith("module.") else k): v for k, v in raw.items()}
+        raw = _read_state(path)
         for k, s in shapes.items():
             if k not in raw:
                 raise KeyError(f"{what} file {path!r} lacks {k}")
@@ -198,20 +207,15 @@ def load_text_state(enc_dir):
     pytorch_model.bin, the first that exists) -> (state dict in transformers' key names with the leading `text_model.`, f32;  CLIPTextEngine's
     keyword arguments).  Read without transformers.  config.json is checked first and on the host (clip.text_options: ValueError naming the field
     for what the kernels do not cover), then against the tensors' shapes; a directory without weights is a FileNotFoundError naming it."""
-    import json
     from . import clip
-    config = None
-    cfg = os.path.join(enc_dir, "config.json")
-    if os.path.isfile(cfg):
-        with open(cfg) as f:
-            config = json.load(f)
+    config = _read_config(enc_dir)
     options, promised = clip.text_options(config)
     names = ("model.safetensors", "model.fp16.safetensors", "pytorch_model.bin")
     path = next((p for p in (os.path.join(enc_dir, n) for n in names) if os.path.isfile(p)), None)
     if path is None:
         raise FileNotFoundError(f"CLIP text encoder directory {enc_dir!r} holds none of {', '.join(names)} (models.text_encoder)")
-    raw = _load_safetensors(path) if path.endswith(".safetensors") else torch.load(path, map_location="cpu", weights_only=True)
-    sd = {k: (v.float() if v.is_floating_point() else v) for k, v in clip.with_text_prefix(raw).items() if not k.endswith("embeddings.position_ids")}
+    raw = clip.with_text_prefix(_read_state(path))
+    sd = {k: (v.float() if v.is_floating_point() else v) for k, v in raw.items() if not k.endswith("embeddings.position_ids")}
     pos = sd.get("text_model.embeddings.position_embedding.weight")
     if pos is None:
         raise KeyError(f"{path!r} does not hold a transformers.CLIPTextModel (no embeddings.position_embedding.weight)")
@@ -220,7 +224,7 @@ def load_text_state(enc_dir):
         fields = dict(width="hidden_size", layers="num_hidden_layers", context_length="max_position_embeddings")
         for k, name in fields.items():
             if found[k] != promised[k]:
-                raise ValueError(f"{name} {promised[k]!r} of {cfg!r}, but the tensors of {path!r} say {found[k]}")
+                raise ValueError(f"{name} {promised[k]!r} of the config.json in {enc_dir!r}, but the tensors of {path!r} say {found[k]}")
     else:                                                                  # no config.json: the head count comes from the width, OpenAI's rule
         options["heads"] = None
     return sd, options
@@ -232,8 +236,7 @@ def load_rmbg_state(path=None, seed=3, allow=False):
     if not (path and os.path.exists(path)):
         _missing("BriaRMBG", path, allow)
         return rmbg.random_state_dict(seed)
-    raw = _load_safetensors(path) if path.endswith(".safetensors") else torch.load(path, map_location="cpu", weights_only=True)
-    return {k: v for k, v in raw.items()}
+    return _read_state(path)
 
 
 def init_iclight(device="cuda", models=None, seed=12345, lora=None):
