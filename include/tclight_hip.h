@@ -232,6 +232,25 @@ int tcl_light_gradient_f32(float* out, int H, int W, int side, hipStream_t st);
  * accesses when chw and the strides are multiples of 8 and the pointers 16 B aligned.  alpha = 1/sqrt(sigma^2 + 1), sigma_t = sigma*alpha (host f64 -> f32). */
 int tcl_light_start_f16(void* out, const void* x0, long x0_stride, const float* z, long z_stride, int N, long chw, float alpha, float sigma_t,
                         hipStream_t st);
+/* The highres pass (gradio_demo_iclight.py:301-334: highres_scale, highres_denoise; csrc/resize.hip): decoded frames -> u8 -> PIL's LANCZOS resize
+ * -> the [0,1]-convention image the VAE encoder takes.
+ * tcl_frames_to_u8: frames [N,3,H,W] f32 (what VAEEngine.decode returns) -> out [N,H,W,3] u8, u = trunc(clamp(fl32(255*p), 0, 255)): one f32 product
+ *   (no fma contraction), clamp, truncation; NaN -> 0.  16 B loads when H*W % 4 == 0 and frames is 16 B aligned.  3*N*H*W >= 2^31 returns TCL_EINVAL.
+ * tcl_u8_to_frames_f32: u8 [N,H,W,3] -> out [N,3,H,W] f32 = u / denom (one IEEE division; denom 254: the demo's u/127 - 1 under VAEEngine.encode's 2x - 1).
+ * tcl_resize_lanczos_table (HOST, no device work): the table of one axis resampled from `in` to `out` samples, PIL's precompute_coeffs +
+ *   normalize_coeffs_8bpc operation for operation in f64 with the C library's sin: scale = in/out, filterscale = max(scale, 1), support = 3*filterscale,
+ *   ksize = 2*ceil(support) + 1, window int(center -/+ support + 0.5) clamped to [0, in], Lanczos-3 weights normalised by their sum and rounded half
+ *   away from zero to 22-bit fixed point.  h_table: out*2 ints (first input index, tap count) followed by out*ksize ints (taps, zero past the count);
+ *   tcl_resize_lanczos_table_ints(in, out) = out*(2 + ksize) is its length, 0 for in == out (that axis is not resampled) or an unsupported ratio.
+ * tcl_resize_lanczos_u8: src [N,H,W,3] u8 -> dst [N,Ho,Wo,3] u8, bit-identical to PIL.Image.resize((Wo, Ho), Image.LANCZOS) frame by frame:
+ *   accumulators start at 1 << 21, are shifted right by 22 and clipped to u8, the horizontal pass is clipped to u8 before the vertical pass, an axis
+ *   whose size does not change is not resampled (both: a copy).  tx / ty (DEVICE): the tables of the W -> Wo and H -> Ho axes (ignored, may be NULL, for an
+ *   unchanged axis).  Per-axis in/out from 0.25 to 2; other ratios, null pointers, non-positive sizes, N > 65535 and 3*N*Ho*Wo >= 2^31 return TCL_EINVAL. */
+int tcl_frames_to_u8(const float* frames, void* out, int N, int H, int W, hipStream_t st);
+int tcl_u8_to_frames_f32(const void* u8, float* out, int N, int H, int W, float denom, hipStream_t st);
+size_t tcl_resize_lanczos_table_ints(int in, int out);
+int tcl_resize_lanczos_table(int in, int out, int* h_table);
+int tcl_resize_lanczos_u8(const void* src, void* dst, int N, int H, int W, int Ho, int Wo, const int* tx, const int* ty, hipStream_t st);
 /* layout conversions around the VAE (generate_utils.py:140-172): 2*img-1 -> NHWC8 f16; clamp(y/2+0.5) -> [B,3,H,W] f32.
  * ldc = row stride in halves, >= the channels read or written (tcl_nchw_to_nhwc_f16 zeroes columns C..ldc-1); empty batches and narrower strides
  * return TCL_EINVAL.  tcl_transpose_f16: in [batch,R,ldi] -> out [batch,Cc,ldo], ldi >= Cc, ldo >= R, padding columns of out are left untouched. */

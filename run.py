@@ -1,5 +1,7 @@
 """Entry point with the reference's surface (run.py:8-32): python run.py --config Y | -i video -p prompt [-n neg] [--multi_axis],
-plus [--light left|right|top|bottom|source] [--strength F]: IC-Light's "Lighting Preference" start (generation.init_latent / init_strength).
+plus [--light left|right|top|bottom|source] [--strength F]: IC-Light's "Lighting Preference" start (generation.init_latent / init_strength),
+and [--highres_scale F] [--highres_denoise F]: IC-Light's highres pass (generation.highres_scale / highres_denoise) -- the relit frames are resized
+with PIL's LANCZOS filter to multiples of 64 and refined by a second img2img denoise; flows, masks, ids, output_gt and the result live at that size.
 data.scene_type picks the parser (generate.py:84-95): video (VideoDataParser) or sceneflow (SceneFlowDataParser: ground-truth depth, poses and
 flows -> voxelised Unique Video Tensor ids); carla and interiornet are not built.
 
@@ -17,10 +19,10 @@ import sys
 import numpy as np
 import torch
 
-from tc_light_amd.config_utils import load_config, save_config
+from tc_light_amd.config_utils import Config, load_config, save_config
 from tc_light_amd.dataparser import VideoDataParser, get_frame_ids, save_loss_curve, save_video
 from tc_light_amd.generate import DEFAULTS, Generator
-from tc_light_amd.hostlogic import check_init
+from tc_light_amd.hostlogic import check_highres, check_highres_tokens, check_init, highres_size
 from tc_light_amd.model_utils import allow_random, init_iclight
 from tc_light_amd.parallel import Dist
 from tc_light_amd.text import encode_prompt_pair
@@ -47,6 +49,16 @@ def main(argv=None):
     config.generation.init_latent, config.generation.init_strength = check_init(
         config.generation.get("init_latent", DEFAULTS["init_latent"]), config.generation.get("init_strength", DEFAULTS["init_strength"]),
         config.generation.get("n_timesteps", DEFAULTS["n_timesteps"]))
+    # IC-Light's highres pass (generation.highres_scale / highres_denoise; --highres_scale / --highres_denoise): refused here when malformed
+    config.generation.highres_scale, config.generation.highres_denoise = check_highres(
+        config.generation.get("highres_scale", DEFAULTS["highres_scale"]), config.generation.get("highres_denoise", DEFAULTS["highres_denoise"]),
+        config.generation.get("n_timesteps", DEFAULTS["n_timesteps"]), bool(config.generation.get("background_cond")))
+    highres = config.generation.highres_scale != 1.0
+    data_hr = None
+    if highres:       # the final size; the producers (flows, masks, ids) and output_gt live there, so a second parser is built at that size
+        H2, W2 = highres_size(config.data["height"], config.data["width"], config.generation.highres_scale)
+        check_highres_tokens(H2, W2, config.generation.get("chunk_size", DEFAULTS["chunk_size"]))
+        data_hr = Config(dict(config.data, height=H2, width=W2))
     lora = None
     if config.generation.get("use_lora"):         # generate_utils.py:95-96; the file is read and its layout checked before any model is loaded
         from tc_light_amd.lora import from_config
@@ -66,16 +78,22 @@ def main(argv=None):
         parser = SceneFlowDataParser(config.data, dev)
     else:
         parser = VideoDataParser(config.data, dev)
+    parser_hr = type(parser)(data_hr, dev) if highres else parser       # where stage 1 / 2 run
     g = config.generation
     frame_ids = get_frame_ids(g.frame_range, parser.n_frames, g.frame_ids)
     config.total_number_of_frames = len(frame_ids)
     d = Dist(rank, world)
     lo, hi = d.range(len(frame_ids))
     frames_all = parser.load_video(frame_ids)
+    frames_out = frames_all                       # the source frames at the size of the result
+    if highres:
+        if scene_type == "video":
+            parser_hr._all = parser._all          # the clip is read once
+        frames_out = parser_hr.load_video(frame_ids)
     flows = scene = None
     if config.post_opt.apply_opt and scene_type == "sceneflow":
         # every rank reads the files itself: ground-truth (or RAFT) flows, masks and the voxelised ids all come from load_data
-        scene = parser.load_data(frame_ids, models=models, allow_random=ok_random)
+        scene = parser_hr.load_data(frame_ids, models=models, allow_random=ok_random)
     elif config.post_opt.apply_opt:
         # rank 0 owns the flow cache (read, or estimated with MemFlowNet / RAFT (data.flow_model) and written: video_dataparser.py:63-110); the other ranks
         # receive the tensors.  A failure on rank 0 (e.g. missing MemFlow weights) is announced before the payload so that every
@@ -83,9 +101,10 @@ def main(argv=None):
         err = None
         if rank == 0:
             try:
-                flows = parser.load_flow_cache(frame_ids)
+                # the on-disk cache belongs to the working size: with the highres pass on it is neither read nor written
+                flows = None if highres else parser.load_flow_cache(frame_ids)
                 if flows is None:
-                    flows = parser.estimate_and_cache_flow(frames_all, frame_ids, parser.make_flow_engine(models, ok_random))
+                    flows = parser_hr.estimate_and_cache_flow(frames_out, frame_ids, parser_hr.make_flow_engine(models, ok_random), save_flow=not highres)
             except Exception as e:            # noqa: BLE001 - re-raised below on every rank
                 err = e
         if world > 1:
@@ -94,7 +113,7 @@ def main(argv=None):
             if int(ok.item()) == 0:
                 torch.distributed.destroy_process_group()
                 raise err if err is not None else RuntimeError("rank 0 failed to load / estimate the optical flow (see its traceback)")
-            flows = flows if rank == 0 else tuple(torch.empty(len(frame_ids), 2, parser.h, parser.w, device=dev) for _ in range(2))
+            flows = flows if rank == 0 else tuple(torch.empty(len(frame_ids), 2, parser_hr.h, parser_hr.w, device=dev) for _ in range(2))
             for t in flows:
                 torch.distributed.broadcast(t, src=0)
         elif err is not None:
@@ -119,13 +138,17 @@ def main(argv=None):
         elif config.post_opt.apply_opt:
             from tc_light_amd.flow_ids import soft_masks_and_ids
             fut, past = flows
-            masks, inv, k = soft_masks_and_ids(frames_all, fut, past, alpha=parser.alpha)
-        out, info = gen(frames_all[lo:hi], conds, conds_t, past, masks, inv, n_total=len(frame_ids), k=k, background=background)
+            masks, inv, k = soft_masks_and_ids(frames_out, fut, past, alpha=parser.alpha)
+        out, info = gen(frames_all[lo:hi], conds, conds_t, past, masks, inv, n_total=len(frame_ids), k=k, background=background,
+                        frames_hr=frames_out[lo:hi] if highres else None)
         if rank == 0:
             config.total_time += info["total_time"]
             config.sec_per_frame = config.total_time / len(frame_ids)
             config.max_memory_allocated = max(config.max_memory_allocated, info["max_memory_allocated"])
             g.scheduler_steps, g.steps_executed = info["scheduler_steps"], info["steps_executed"]      # init_latent / init_strength are in g already
+            if highres:                           # total_time / sec_per_frame cover both passes
+                g.highres_size = list(info["highres_size"])
+                g.highres_scheduler_steps, g.highres_steps_executed = info["highres_scheduler_steps"], info["highres_steps_executed"]
             # generate.py:613-630: save_name, config.yaml, output.mp4 (+ frames), output_gt.mp4, loss curves
             path = os.path.join(g.output_path, f"lmr_{g.local_merge_ratio}_gmr_{g.global_merge_ratio}_alpha_t_{g.alpha_t}_opt_{name}")
             save_config(config, path, gene=True)
@@ -138,7 +161,7 @@ def main(argv=None):
             save_video(out, path, save_frame=bool(g.get("save_frame", False)), fps=parser.fps, gif=False)
             gt_path = os.path.join(path, "gt")
             if not os.path.exists(gt_path) or len(os.listdir(gt_path)) != len(frame_ids):
-                save_video(frames_all, path, save_frame=False, post_fix="_gt", fps=parser.fps, gif=False)
+                save_video(frames_out, path, save_frame=False, post_fix="_gt", fps=parser.fps, gif=False)
             print(f"[INFO] {len(frame_ids)} frames in {info['total_time']:.1f} s ({1 / config.sec_per_frame:.3f} frames/s) -> {path}")
     if world > 1:
         torch.distributed.destroy_process_group()

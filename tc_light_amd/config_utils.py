@@ -82,8 +82,16 @@ def load_config(argv=None, print_config=True):
     ap.add_argument("--light", choices=("left", "right", "top", "bottom", "source"), default=None,
                     help="start the denoise from a light gradient of that side (or the source frames), for a fast usage")
     ap.add_argument("--strength", type=float, default=None, help="how far the relight may move from that start, in (0, 1], for a fast usage")
+    # IC-Light's highres pass (generation.highres_scale / highres_denoise, generate.py DEFAULTS)
+    ap.add_argument("--highres_scale", type=float, default=None, help="resize the relit frames by this factor in [1, 3] (to multiples of 64) and "
+                    "refine them with a second denoise; 1.0 is off, for a fast usage")
+    ap.add_argument("--highres_denoise", type=float, default=None, help="strength of that second denoise, in (0, 1], for a fast usage")
     a = ap.parse_args(argv)
     cfg = load_yaml_chain(a.config, a.base_config)
+    if a.highres_scale is not None:
+        cfg.generation.highres_scale = a.highres_scale
+    if a.highres_denoise is not None:
+        cfg.generation.highres_denoise = a.highres_denoise
     if a.light is not None:
         cfg.generation.init_latent = a.light
     if a.strength is not None:

@@ -4,6 +4,9 @@
   scheduler.step} -> decode_latents_batch -> exposure_align -> unique_tensor_optimization        (generate.py:560-611)
 generation.init_latent (not in the reference's run.py; IC-Light's "Lighting Preference", gradio_demo_iclight.py:235-299): build_start replaces the noise
 start by an img2img one and ddim_sample enters a longer schedule part-way; the loop itself is the same.
+generation.highres_scale > 1 (the second half of the same function, :301-334): highres_pass sits between ddim_sample and the decode -- decode ->
+u8 -> PIL-exact LANCZOS resize (csrc/resize.hip) -> encode -> img2img start -> the same ddim_sample at the larger size; decode and stages 1 / 2 then
+run on the frames the user gets.
 
 Python sequences kernel launches and collectives; tensors never leave the device inside the timed region and there is no
 per-iteration host sync (the reference syncs on loss.item() and moves the token bank through the CPU).
@@ -44,6 +47,11 @@ DEFAULTS = dict(  # configs/tclight_default.yaml (generation / post_opt sections
     latents_path=None, model_key="iclight", frame_ids=None,
     # ^ generation.latents_path (generate.py:563-566): saved start latents `<latents_path>/<model_key>/noisy_latents_<first timestep>.pt`, a tensor
     #   over the video's frames of which `frame_ids` (None: all) are this run's; when the file exists it replaces the random start noise.
+    highres_scale=1.0, highres_denoise=0.5,
+    # ^ IC-Light's highres pass (gradio_demo_iclight.py:301-334): scale in [1, 3], 1.0 = off (the demo always runs it; here the default leaves every
+    #   path, RNG draw and output bit as it was).  On: the relit frames are decoded, quantised to u8, resized with PIL's LANCZOS filter to
+    #   HL.highres_size (multiples of 64), encoded again and refined by a second img2img denoise of strength highres_denoise at that size; stage 1 / 2
+    #   run at the final size, so the caller hands flows, masks and ids of that size and the source frames at both sizes.
     init_latent="none", init_strength=0.9,
     # ^ IC-Light's "Lighting Preference" (gradio_demo_iclight.py:235-299: bg_source, lowres_denoise): left | right | top | bottom start the denoise from
     #   the VAE latent of a light gradient, `source` from the frames' own clean latents, noised to init_strength -- the scheduler is set to
@@ -92,6 +100,10 @@ class Generator:
         self.img2img = c.init_latent != "none"
         # (scheduler steps, begin index, steps executed): the whole n_timesteps schedule unless the start is an img2img one
         self.schedule = HL.img2img_schedule(c.n_timesteps, c.init_strength) if self.img2img else (c.n_timesteps, 0, c.n_timesteps)
+        c.highres_scale, c.highres_denoise = HL.check_highres(c.highres_scale, c.highres_denoise, c.n_timesteps)
+        self.highres = c.highres_scale != 1.0
+        self.schedule_highres = HL.img2img_schedule(c.n_timesteps, c.highres_denoise) if self.highres else None      # the second pass's schedule
+        self._lanczos = {}                 # (in, out) -> device table of that axis
         self.batch_size = 2
         self.timing = {}
         if c.max_tokens_per_pass is None:
@@ -161,6 +173,88 @@ class Generator:
         self.init_noise = torch.empty(n, 4, self.h, self.w, dtype=H16, device=self.dev)
         self.L.tcl_light_start_f16(self.init_noise, x0, x0_stride, z, 0 if same else chw, n, chw, alpha, sigma_t, stream())
         return self.init_noise
+
+    # ------------------------------------------------------------------ highres pass (gradio_demo_iclight.py:301-334)
+    def frames_to_u8(self, frames):
+        """[n,3,H,W] f32 as decode_latents_batch returns it -> [n,H,W,3] u8, u = trunc(clamp(fl32(255 p), 0, 255)) (the demo's pytorch2numpy
+        computes y * 127.5 + 127.5 on the [-1,1] image: the same value up to f32 rounding at integer boundaries)."""
+        n, _, H, W = frames.shape
+        out = torch.empty(n, H, W, 3, dtype=torch.uint8, device=self.dev)
+        self.L.tcl_frames_to_u8(frames.float().contiguous(), out, n, H, W, stream())
+        return out
+
+    def _lanczos_table(self, n_in, n_out):
+        """The device table of one resampled axis (host f64, C library: csrc/resize.hip), made once per size pair; None for an unchanged axis."""
+        if n_in == n_out:
+            return None
+        if (n_in, n_out) not in self._lanczos:
+            ints = self.L.tcl_resize_lanczos_table_ints(n_in, n_out)
+            if ints == 0:
+                raise ValueError(f"LANCZOS resize {n_in} -> {n_out}: the ratio is outside [0.25, 2]")
+            t = torch.empty(ints, dtype=I32)
+            self.L.tcl_resize_lanczos_table(n_in, n_out, t)
+            self._lanczos[(n_in, n_out)] = t.to(self.dev)
+        return self._lanczos[(n_in, n_out)]
+
+    def resize_lanczos_u8(self, u8, H2, W2):
+        """[n,H,W,3] u8 -> [n,H2,W2,3] u8, PIL's Image.resize((W2, H2), Image.LANCZOS) of every frame, bit for bit."""
+        n, H, W, _ = u8.shape
+        tx, ty = self._lanczos_table(W, W2), self._lanczos_table(H, H2)
+        out = torch.empty(n, H2, W2, 3, dtype=torch.uint8, device=self.dev)
+        self.L.tcl_resize_lanczos_u8(u8.contiguous(), out, n, H, W, H2, W2, 0 if tx is None else tx, 0 if ty is None else ty, stream())
+        return out
+
+    def u8_to_frames(self, u8):
+        """[n,H,W,3] u8 -> [n,3,H,W] f32 = u/254: VAEEngine.encode's 2x - 1 is then the demo's u/127 - 1 (numpy2pytorch), as in light_gradient."""
+        n, H, W, _ = u8.shape
+        out = torch.empty(n, 3, H, W, dtype=torch.float32, device=self.dev)
+        self.L.tcl_u8_to_frames_f32(u8.contiguous(), out, n, H, W, 254.0, stream())
+        return out
+
+    def highres_upscale(self, decoded):
+        """decoded [n,3,H,W] f32 (the first pass's frames) -> (u8 [n,H2,W2,3], x0 [n,4,H2/8,W2/8] f16): quantise, LANCZOS resize to
+        HL.highres_size, back to float as u/254, VAE encode in batches of batch_size."""
+        H2, W2 = HL.highres_size(*decoded.shape[-2:], self.cfg.highres_scale)
+        up = self.resize_lanczos_u8(self.frames_to_u8(decoded), H2, W2)
+        x0 = torch.cat([self.vae.encode(self.u8_to_frames(b)) for b in up.split(self.batch_size, dim=0)])
+        return up, x0
+
+    def highres_start(self, x0):
+        """The second pass's start latents: alpha*x0 + sigma_t*z at the first executed sigma of schedule_highres, z a fresh f32 draw from rng_dev
+        (noise_mode same: one frame for all; vanilla: n_total frames, this rank's block taken, as prepare_data does)."""
+        c, sch = self.cfg, self.scheduler
+        n, _, h2, w2 = x0.shape
+        sch.set_timesteps(*self.schedule_highres[:2])
+        alpha, sigma_t = (float(np.float32(v)) for v in sch.add_noise_coefficients())
+        same = c.noise_mode.lower() == "same"
+        if same:
+            z = torch.randn(1, 4, h2, w2, generator=self.rng_dev, device=self.dev, dtype=torch.float32)
+        else:
+            lo, hi = self.dist.range(self.n_total)
+            z = torch.randn(self.n_total, 4, h2, w2, generator=self.rng_dev, device=self.dev, dtype=torch.float32)[lo:hi].contiguous()
+        assert z.shape[0] == (1 if same else n)
+        chw = 4 * h2 * w2
+        start = torch.empty(n, 4, h2, w2, dtype=H16, device=self.dev)
+        self.L.tcl_light_start_f16(start, x0.contiguous(), chw, z, 0 if same else chw, n, chw, alpha, sigma_t, stream())
+        return start
+
+    def highres_pass(self, x, frames_hr, conds, conds_t):
+        """x: the first pass's latents [n_local,4,h,w]; frames_hr: this rank's source frames at the final size [n_local,3,H2,W2] f32 in [0,1] (the
+        project's own loader at that size, not the demo's LANCZOS crop).  -> the refined latents [n_local,4,H2/8,W2/8]; the Generator's working
+        size is the final one from here on."""
+        n = x.shape[0]
+        H2, W2 = HL.highres_size(8 * self.h, 8 * self.w, self.cfg.highres_scale)
+        if frames_hr is None or tuple(frames_hr.shape) != (n, 3, H2, W2):
+            raise ValueError(f"highres pass: source frames at the final size {None if frames_hr is None else tuple(frames_hr.shape)}, "
+                             f"expected {(n, 3, H2, W2)}")
+        if getattr(self.unet.tome, "enabled", True):
+            HL.check_highres_tokens(H2, W2, self.cfg.chunk_size)
+        self.upscaled_u8, x0 = self.highres_upscale(self.vae.decode_latents_batch(x, self.batch_size))
+        self.frames = frames_hr.float().contiguous()
+        concat_conds = self.vae.encode_imgs_batch(self.frames, self.batch_size)
+        start = self.highres_start(x0)
+        self.h, self.w = H2 // 8, W2 // 8
+        return self.ddim_sample(start, conds, conds_t, concat_conds, schedule=self.schedule_highres)
 
     def _load_start_latents(self, n):
         """generate.py:563-566, 191-194: start from the saved latents of the scheduler's first timestep when they exist (-> True); nothing is
@@ -259,10 +353,13 @@ class Generator:
 
     # ------------------------------------------------------------------ hot loop 1
     @torch.no_grad()
-    def ddim_sample(self, x, conds, conds_t, concat_conds):
+    def ddim_sample(self, x, conds, conds_t, concat_conds, schedule=None):
+        """schedule: (scheduler steps, begin index, steps executed) of an img2img entry other than the first pass's own (the highres pass)."""
         c, d = self.cfg, self.dist
         sch = self.scheduler
-        if self.img2img:       # enter the longer schedule at its begin index: sch.timesteps are the executed steps, so the decay `alphas` and the
+        if schedule is not None:
+            sch.set_timesteps(*schedule[:2])
+        elif self.img2img:     # enter the longer schedule at its begin index: sch.timesteps are the executed steps, so the decay `alphas` and the
             sch.set_timesteps(*self.schedule[:2])      # "no noise on the last step" rule below are taken over them, counted from 0
         else:
             sch.set_timesteps(c.n_timesteps)
@@ -291,11 +388,15 @@ class Generator:
         return x
 
     # ------------------------------------------------------------------ end to end
-    def __call__(self, frames, conds, conds_t, past_flows, mask_bwds, unq_inv, n_total=None, k=None, background=None):
+    def __call__(self, frames, conds, conds_t, past_flows, mask_bwds, unq_inv, n_total=None, k=None, background=None, frames_hr=None):
         """frames: local block [n_local,3,H,W]; conds / conds_t: [2,L,768] f16 (uncond, cond) text embeddings for the xy / yt
         passes (generate.py:553-555); past_flows / mask_bwds / unq_inv: stage-2 inputs for ALL frames (device).
-        Returns (relit frames [N,3,H,W] f32, info dict)."""
+        Returns (relit frames [N,3,H,W] f32, info dict).
+        With generation.highres_scale > 1: frames_hr is the local block at HL.highres_size [n_local,3,H2,W2], the stage-2 inputs live at that size
+        and so do the returned frames."""
         c, d = self.cfg, self.dist
+        if self.highres and background is not None:
+            raise ValueError("generation.background_cond together with generation.highres_scale > 1 is not supported")
         self.n_total = n_total or frames.shape[0] * d.world
         ev = lambda: (torch.cuda.synchronize(self.dev), time.perf_counter())[1]
         t0 = ev()
@@ -305,7 +406,11 @@ class Generator:
             self.build_start(concat_conds)
         t1 = ev()
         x = self.ddim_sample(self.init_noise.clone(), conds, conds_t, concat_conds)
-        t2 = ev()
+        self.latents = x                   # the first pass's result (with highres on: what the second pass starts from)
+        t2 = t2a = ev()
+        if self.highres:
+            x = self.highres_pass(x, frames_hr, conds, conds_t)
+            t2 = ev()
         mode = "shard" if c.shard_post_opt else str(c.post_opt_mode)
         if mode not in ("replicated", "replicated_all", "global", "shard"):
             raise ValueError(f"post_opt_mode {mode!r}: expected replicated | replicated_all | global | shard")
@@ -353,9 +458,13 @@ class Generator:
             t5 = ev()
         else:
             t4 = t5 = t3
-        self.timing = dict(encode=t1 - t0, denoise=t2 - t1, decode=t3 - t2, stage1=t4 - t3, stage2=t5 - t4, total=t5 - t0)
+        self.timing = dict(encode=t1 - t0, denoise=t2a - t1, decode=t3 - t2, stage1=t4 - t3, stage2=t5 - t4, total=t5 - t0)
         info = dict(timing=self.timing, losses_exposure=losses1, losses_unique=losses2, total_time=t5 - t0,
                     sec_per_frame=(t5 - t0) / self.n_total, total_number_of_frames=self.n_total, init_latent=c.init_latent,
                     init_strength=c.init_strength, scheduler_steps=self.schedule[0], steps_executed=self.schedule[2],
                     max_memory_allocated=torch.cuda.max_memory_allocated(self.dev) / 1024.0 ** 2)
+        if self.highres:                   # decode -> u8 -> resize -> encode -> second denoise, between `denoise` and `decode`
+            self.timing["highres"] = t2 - t2a
+            info.update(highres_scale=c.highres_scale, highres_denoise=c.highres_denoise, highres_size=[8 * self.h, 8 * self.w],
+                        highres_scheduler_steps=self.schedule_highres[0], highres_steps_executed=self.schedule_highres[2])
         return clean, info

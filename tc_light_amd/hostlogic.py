@@ -101,6 +101,49 @@ def img2img_schedule(n, strength):
     return n_sched, n_sched - run, run
 
 
+def highres_size(H, W, scale):
+    """(H2, W2) of the highres pass (gradio_demo_iclight.py:310-312): every side goes to int(round(side * scale / 64.0)) * 64 with Python's round
+    (half to even: 960 * 1.5 -> 1408, not 1472); a side below 64 is a ValueError."""
+    out = tuple(int(round(int(s) * float(scale) / 64.0)) * 64 for s in (H, W))
+    if min(out) < 64:
+        raise ValueError(f"generation.highres_scale {scale} takes {int(H)}x{int(W)} to {out[0]}x{out[1]}: a side below 64")
+    return out
+
+
+def check_highres(highres_scale, highres_denoise, n_timesteps=None, background_cond=False):
+    """generation.highres_scale / highres_denoise as (float, float); anything else is a ValueError (run.py raises it before a model is loaded).
+    scale in [1, 3], 1.0 = off; denoise in (0, 1].  With the pass on: a schedule that would execute no step is refused (as check_init does), and so
+    is background compositing (generation.background_cond), which the highres pass does not cover."""
+    for key, v in (("highres_scale", highres_scale), ("highres_denoise", highres_denoise)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or v != v:
+            raise ValueError(f"generation.{key} {v!r}: expected a number")
+    scale, denoise = float(highres_scale), float(highres_denoise)
+    if not 1.0 <= scale <= 3.0:
+        raise ValueError(f"generation.highres_scale {highres_scale!r}: expected a number in [1, 3] (1.0 = off)")
+    if not 0.0 < denoise <= 1.0:
+        raise ValueError(f"generation.highres_denoise {highres_denoise!r}: expected a number in (0, 1]")
+    if scale != 1.0:
+        if n_timesteps is not None and img2img_schedule(n_timesteps, denoise)[2] < 1:
+            raise ValueError(f"generation.highres_denoise {highres_denoise} with n_timesteps {n_timesteps} leaves no step to execute")
+        if background_cond:
+            raise ValueError("generation.background_cond together with generation.highres_scale > 1 is not supported: the highres pass does not "
+                             "composite backgrounds")
+    return scale, denoise
+
+
+TOME_MAX_SRC_TOKENS = 64 * 1024          # tcl_tome_match_f16 / _affine_f16: source tokens of one match (csrc/merge.hip)
+
+
+def check_highres_tokens(H2, W2, chunk_size):
+    """The second pass runs VidToMe on chunks of `chunk_size` frames at (H2, W2): one frame is the destination, the others' level-0 tokens are the
+    sources of one match, and the match kernels take at most TOME_MAX_SRC_TOKENS of them.  1920x1088 with chunk_size 4 (97 920) is refused here,
+    before a model is loaded, instead of inside the loop; chunk_size 2 (32 640) or a smaller scale fits."""
+    n = (int(chunk_size) - 1) * (int(H2) // 8) * (int(W2) // 8)
+    if n > TOME_MAX_SRC_TOKENS:
+        raise ValueError(f"generation.highres_scale: the final size {H2}x{W2} with generation.chunk_size {chunk_size} gives {n} source tokens per VidToMe "
+                         f"match, more than the {TOME_MAX_SRC_TOKENS} the match kernels take -- lower highres_scale or chunk_size")
+
+
 def shard_range(n, rank, world):
     """Contiguous frame block of `rank` (sizes differ by at most one; SURVEY 8(d) config 3: 38/38/38/38/37/37/37/37)."""
     base, rem = divmod(n, world)
