@@ -194,6 +194,16 @@ int tcl_timestep_embed_f16(float t, int dim, void* out, hipStream_t st);
  * UNet input [2F,H',W',8] NHWC.  mode 0: xy-plane, idx = frame ids; mode 1: yt-plane ('n c h w -> w c n h', generate.py:267),
  * idx = latent columns, frames sl..sl+nwin. */
 int tcl_pack_latents_f16(const void* x, const void* cond, const int* idx, int F, int mode, int sl, int nwin, int h, int w, void* out, hipStream_t st);
+/* The same assembly for the background-conditioned IC-Light model (utils/model_utils.py:97-179, init_iclight_bg: a 12-channel conv_in, and
+ * `torch.cat([sample, c_concat], dim=1)` of its hooked forward with c_concat = foreground latent | background latent): x / cond_fg [N,4,h,w] f16,
+ * cond_bg [bg_frames,4,h,w] f16 -> out [2F,H',W',12] NHWC, channels 0-3 x, 4-7 cond_fg, 8-11 cond_bg, both CFG halves written (cfg_pair holds).  Modes,
+ * idx, sl, nwin as tcl_pack_latents_f16.  bg_frames == 1: the one background latent is read for every frame (never repeated in memory); any other
+ * value is the frame count N of cond_bg, the same as x's.  Records are 24 B: one 16 B and one 8 B store per pixel; `out` 8 B aligned.
+ * TCL_EINVAL: null pointers, F <= 0, h, w <= 0, another mode, a misaligned out, bg_frames < 1, and in yt mode nwin <= 0, sl < 0 or a per-frame
+ * background shorter than the window (1 < bg_frames < sl + nwin).  N itself is not an argument (as in the 8-channel entry), so in xy mode a
+ * bg_frames other than 1 or N is the caller's to refuse (Generator does). */
+int tcl_pack_latents12_f16(const void* x, const void* cond_fg, const void* cond_bg, int bg_frames, const int* idx, int F, int mode, int sl, int nwin,
+                           int h, int w, void* out, hipStream_t st);
 /* CFG combine uncond + g*(cond - uncond) (generate.py:349-350) scattered back to noises[N,4,h,w]; in mode 1 frames
  * n < scale_upto are multiplied by `scale` (the sqrt(0.5) overlap rule, generate.py:276-278) and only the first nkeep
  * frames of the window are written (the rest is overwritten by the next window in the reference's sequential order). */
@@ -232,6 +242,18 @@ int tcl_light_gradient_f32(float* out, int H, int W, int side, hipStream_t st);
  * accesses when chw and the strides are multiples of 8 and the pointers 16 B aligned.  alpha = 1/sqrt(sigma^2 + 1), sigma_t = sigma*alpha (host f64 -> f32). */
 int tcl_light_start_f16(void* out, const void* x0, long x0_stride, const float* z, long z_stride, int N, long chw, float alpha, float sigma_t,
                         hipStream_t st);
+/* Inputs of the background-conditioned model (generation.iclight_model: fbc; IC-Light's background demo, whose constants are restated in DESIGN
+ * section 6; csrc/light.hip).
+ * tcl_bg_ramp_f32 (replaces the demo's `np.linspace(start, stop, n)` tiled to an image for bg_source left / right / top / bottom / grey): out
+ *   [3,H,W] f32 (16 B aligned) = u/254, the same plane three times, u = uint8(np.linspace(start, stop, n)) with start at index 0 of the axis `side`
+ *   names (x, n = W for TCL_LIGHT_LEFT / RIGHT; y, n = H for TOP / BOTTOM) -- the linspace rule of tcl_light_gradient_f32.  start == stop is a
+ *   constant image.  start, stop outside [0, 255] and whatever tcl_light_gradient_f32 refuses return TCL_EINVAL.
+ * tcl_matte_grey_f32 (replaces the demo's run_rmbg composite `127 + (img - 127) * alpha` clipped to uint8, and numpy2pytorch): frames [n,3,H,W]
+ *   f32 in [0,1], alpha [n,1,H,W] f32 (RMBGEngine.estimate_alpha) -> out [n,3,H,W] f32.  Per channel in f32, no fma contraction: u = 255 f;
+ *   v = 127 + (u - 127) a; q = trunc(clamp(v, 0, 255)) (NaN -> 0); out = q/254, whose 2x - 1 (VAEEngine.encode) is the demo's q/127 - 1.  16 B
+ *   accesses when H*W % 4 == 0 and the three pointers are 16 B aligned. */
+int tcl_bg_ramp_f32(float* out, int H, int W, int side, int start, int stop, hipStream_t st);
+int tcl_matte_grey_f32(const float* frames, const float* alpha, float* out, int n, int H, int W, hipStream_t st);
 /* The highres pass (gradio_demo_iclight.py:301-334: highres_scale, highres_denoise; csrc/resize.hip): decoded frames -> u8 -> PIL's LANCZOS resize
  * -> the [0,1]-convention image the VAE encoder takes.
  * tcl_frames_to_u8: frames [N,3,H,W] f32 (what VAEEngine.decode returns) -> out [N,H,W,3] u8, u = trunc(clamp(fl32(255*p), 0, 255)): one f32 product

@@ -1,5 +1,7 @@
 """Entry point with the reference's surface (run.py:8-32): python run.py --config Y | -i video -p prompt [-n neg] [--multi_axis],
 plus [--light left|right|top|bottom|source] [--strength F]: IC-Light's "Lighting Preference" start (generation.init_latent / init_strength),
+[--iclight_model fc|fbc] [--bg_source upload|upload_flip|left|right|top|bottom|grey]: IC-Light's background-conditioned model
+(generation.iclight_model / bg_source / fbc_matting; models.iclight_offset is then the fbc file) -- the UNet sees the foreground and a background latent,
 and [--highres_scale F] [--highres_denoise F]: IC-Light's highres pass (generation.highres_scale / highres_denoise) -- the relit frames are resized
 with PIL's LANCZOS filter to multiples of 64 and refined by a second img2img denoise; flows, masks, ids, output_gt and the result live at that size.
 data.scene_type picks the parser (generate.py:84-95): video (VideoDataParser) or sceneflow (SceneFlowDataParser: ground-truth depth, poses and
@@ -22,7 +24,8 @@ import torch
 from tc_light_amd.config_utils import Config, load_config, save_config
 from tc_light_amd.dataparser import VideoDataParser, get_frame_ids, save_loss_curve, save_video
 from tc_light_amd.generate import DEFAULTS, Generator
-from tc_light_amd.hostlogic import check_highres, check_highres_tokens, check_init, highres_size
+from tc_light_amd.hostlogic import (check_fbc, check_highres, check_highres_tokens, check_init, cond_channels, fbc_background_per_frame,
+                                    highres_size)
 from tc_light_amd.model_utils import allow_random, init_iclight
 from tc_light_amd.parallel import Dist
 from tc_light_amd.text import encode_prompt_pair
@@ -53,6 +56,15 @@ def main(argv=None):
     config.generation.highres_scale, config.generation.highres_denoise = check_highres(
         config.generation.get("highres_scale", DEFAULTS["highres_scale"]), config.generation.get("highres_denoise", DEFAULTS["highres_denoise"]),
         config.generation.get("n_timesteps", DEFAULTS["n_timesteps"]), bool(config.generation.get("background_cond")))
+    # IC-Light's background-conditioned model (generation.iclight_model / bg_source / fbc_matting; --iclight_model / --bg_source): what it does not
+    # cover (init_latent, the highres pass, background_cond) is refused here by name
+    config.generation.iclight_model, config.generation.bg_source = check_fbc(
+        config.generation.get("iclight_model", DEFAULTS["iclight_model"]), config.generation.get("bg_source", DEFAULTS["bg_source"]),
+        config.generation.init_latent, config.generation.highres_scale, bool(config.generation.get("background_cond")))
+    config.generation.fbc_matting = bool(config.generation.get("fbc_matting", DEFAULTS["fbc_matting"]))
+    fbc = config.generation.iclight_model == "fbc"
+    if fbc and config.generation.bg_source in ("upload", "upload_flip") and not config.generation.get("background_image_path"):
+        raise ValueError(f"generation.bg_source {config.generation.bg_source} needs generation.background_image_path")
     highres = config.generation.highres_scale != 1.0
     data_hr = None
     if highres:       # the final size; the producers (flows, masks, ids) and output_gt live there, so a second parser is built at that size
@@ -71,7 +83,8 @@ def main(argv=None):
         torch.distributed.init_process_group("nccl", device_id=dev)
     models = config.get("models") or {}
     ok_random = allow_random(models)
-    pipe, scheduler, config.model_key = init_iclight(dev, models, seed=config.seed, lora=lora)
+    pipe, scheduler, config.model_key = init_iclight(dev, models, seed=config.seed, lora=lora,
+                                                     cond_channels=cond_channels(config.generation.iclight_model))
     config.max_memory_allocated, config.total_time = 0, 0
     if scene_type == "sceneflow":
         from tc_light_amd.sceneflow import SceneFlowDataParser
@@ -120,13 +133,19 @@ def main(argv=None):
             raise err
     cfg = dict(g); cfg.update(config.post_opt); cfg["seed"] = config.seed
     cfg["frame_ids"], cfg["model_key"] = frame_ids, config.model_key      # generation.latents_path: which saved start latents are this run's
-    rmbg = background = None
-    if g.get("background_cond"):                               # generate.py:68-69, 147-167
+    rmbg = background = bg_per_frame = None
+    if g.get("background_cond") or (fbc and g.fbc_matting):    # generate.py:68-69, 147-167; fbc: the alpha of the grey matte
         from tc_light_amd.model_utils import load_rmbg_state
         from tc_light_amd.rmbg import RMBGEngine
         rmbg = RMBGEngine(load_rmbg_state(models.get("rmbg"), allow=ok_random), dev)
+    if g.get("background_cond"):
         background = parser.load_video(path=g.background_image_path)
         if background.shape[0] == len(frame_ids) and world > 1:     # a per-frame background video: this rank's block of it
+            background = background[lo:hi]
+    elif fbc and g.bg_source in ("upload", "upload_flip"):     # the background the fbc model is conditioned on: one frame for all, or one per frame
+        background = parser.load_video(path=g.background_image_path)
+        bg_per_frame = fbc_background_per_frame(background.shape[0], len(frame_ids), g.bg_source)      # the same answer on every rank
+        if bg_per_frame and world > 1:
             background = background[lo:hi]
     gen = Generator(pipe.unet, pipe.vae, cfg, dist=d, scheduler=scheduler, rmbg=rmbg)
     for name, prompt in g.prompt.items():
@@ -140,7 +159,7 @@ def main(argv=None):
             fut, past = flows
             masks, inv, k = soft_masks_and_ids(frames_out, fut, past, alpha=parser.alpha)
         out, info = gen(frames_all[lo:hi], conds, conds_t, past, masks, inv, n_total=len(frame_ids), k=k, background=background,
-                        frames_hr=frames_out[lo:hi] if highres else None)
+                        frames_hr=frames_out[lo:hi] if highres else None, background_per_frame=bg_per_frame)
         if rank == 0:
             config.total_time += info["total_time"]
             config.sec_per_frame = config.total_time / len(frame_ids)

@@ -86,8 +86,18 @@ def load_config(argv=None, print_config=True):
     ap.add_argument("--highres_scale", type=float, default=None, help="resize the relit frames by this factor in [1, 3] (to multiples of 64) and "
                     "refine them with a second denoise; 1.0 is off, for a fast usage")
     ap.add_argument("--highres_denoise", type=float, default=None, help="strength of that second denoise, in (0, 1], for a fast usage")
+    # IC-Light's background-conditioned model (generation.iclight_model / bg_source, generate.py DEFAULTS)
+    ap.add_argument("--iclight_model", choices=("fc", "fbc"), default=None, help="fc: the foreground-conditioned model; fbc: foreground and "
+                    "background, the background is the lighting condition (models.iclight_offset must be that model's file), for a fast usage")
+    ap.add_argument("--bg_source", choices=("upload", "upload_flip", "left", "right", "top", "bottom", "grey"), default=None,
+                    help="the background of the fbc model: generation.background_image_path (as it is or flipped), a grey ramp or flat grey, "
+                    "for a fast usage")
     a = ap.parse_args(argv)
     cfg = load_yaml_chain(a.config, a.base_config)
+    if a.iclight_model is not None:
+        cfg.generation.iclight_model = a.iclight_model
+    if a.bg_source is not None:
+        cfg.generation.bg_source = a.bg_source
     if a.highres_scale is not None:
         cfg.generation.highres_scale = a.highres_scale
     if a.highres_denoise is not None:

@@ -379,6 +379,86 @@ __global__ void k_pack_latents(const _Float16* __restrict__ x, const _Float16* _
         *(h8*)(out + ((long)(F + j) * per + r) * 8) = v;
     }
 }
+// 12-channel records of the background-conditioned IC-Light model (utils/model_utils.py:97-179, init_iclight_bg): x | cond_fg | cond_bg, 24 B per
+// pixel, written as one 16 B and one 8 B store, the 16 B one on whichever side of the record is 16 B aligned (`out` is 8 B aligned: host check).
+typedef _Float16 h4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void store_rec12(_Float16* p, h4 a, h4 b, h4 c) {
+    if (((uintptr_t)p & 15) == 0) {
+        *(h8*)p = __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7); *(h4*)(p + 8) = c;
+    } else {
+        *(h4*)p = a; *(h8*)(p + 4) = __builtin_shufflevector(b, c, 0, 1, 2, 3, 4, 5, 6, 7);
+    }
+}
+// xy: image j = frame idx[j].  One lane per pixel, consecutive lanes on consecutive wx: every one of the 12 NCHW plane reads is a contiguous
+// 128 B per wave; a lane's record goes out twice (uncond, cond half).  bg_one: the single background latent serves every frame.
+__global__ __launch_bounds__(256) void k_pack_latents12_xy(const _Float16* __restrict__ x, const _Float16* __restrict__ fg,
+                                                           const _Float16* __restrict__ bg, int bg_one, const int* __restrict__ idx, int F,
+                                                           int h, int w, _Float16* __restrict__ out) {
+    const long per = (long)h * w, total = (long)F * per;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int j = (int)(i / per); const long r = i - (long)j * per;
+        const long n = idx[j], nb = bg_one ? 0 : n;
+        h4 a, b, c;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            a[k] = x[(n * 4 + k) * per + r]; b[k] = fg[(n * 4 + k) * per + r]; c[k] = bg[(nb * 4 + k) * per + r];
+        }
+        store_rec12(out + ((long)j * per + r) * 12, a, b, c);
+        store_rec12(out + ((long)(F + j) * per + r) * 12, a, b, c);
+    }
+}
+// yt ('n c h w -> w c n h'): image j = latent column idx[j], rows = frames sl..sl+nwin, cols = hy.  The output runs along hy, the NCHW source
+// along wx = idx[j], so a tile of PK12_T columns x PK12_T rows of one frame is transposed through LDS: read with consecutive lanes on consecutive
+// j (a chunk's columns are consecutive: contiguous 64 B runs), written with consecutive lanes on consecutive hy (contiguous 24 B records).
+// LDS row stride 12*PK12_T + 4 halves = 194 dwords: the 32 lanes of a read-phase row land in 32 different banks, records stay 8 B aligned.
+#define PK12_T 32
+#define PK12_LD (12 * PK12_T + 4)
+__global__ __launch_bounds__(256) void k_pack_latents12_yt(const _Float16* __restrict__ x, const _Float16* __restrict__ fg,
+                                                           const _Float16* __restrict__ bg, int bg_one, const int* __restrict__ idx, int F,
+                                                           int sl, int nwin, int h, int w, _Float16* __restrict__ out) {
+    __shared__ __attribute__((aligned(16))) _Float16 tile[PK12_T * PK12_LD];
+    const int tj = (F + PK12_T - 1) / PK12_T, th = (h + PK12_T - 1) / PK12_T;
+    const long tiles = (long)nwin * tj * th, plane = (long)h * w, per = (long)nwin * h;
+    const int lo = threadIdx.x & (PK12_T - 1), hi = threadIdx.x >> 5;          // 256 threads: 32 x 8
+    for (long t = blockIdx.x; t < tiles; t += gridDim.x) {                     // block-uniform trip count: the barriers below are safe
+        const int yy = (int)(t / ((long)tj * th)), rem = (int)(t - (long)yy * tj * th);
+        const int j0 = (rem / th) * PK12_T, h0 = (rem % th) * PK12_T;
+        const long n = sl + yy, nb = bg_one ? 0 : n;
+        {   // read phase: lane -> column j0 + lo, rows h0 + hi, hi + 8, ...
+            const int j = j0 + lo;
+            const int wx = j < F ? idx[j] : 0;
+#pragma unroll
+            for (int p = 0; p < PK12_T / 8; ++p) {
+                const int hl = p * 8 + hi, hy = h0 + hl;
+                const bool ok = j < F && hy < h;
+                _Float16* d = tile + lo * PK12_LD + hl * 12;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const long off = (long)hy * w + wx;
+                    d[k] = ok ? x[(n * 4 + k) * plane + off] : (_Float16)0.f;
+                    d[4 + k] = ok ? fg[(n * 4 + k) * plane + off] : (_Float16)0.f;
+                    d[8 + k] = ok ? bg[(nb * 4 + k) * plane + off] : (_Float16)0.f;
+                }
+            }
+        }
+        __syncthreads();
+        {   // write phase: lane -> row h0 + lo, columns j0 + hi, hi + 8, ...
+            const int hy = h0 + lo;
+#pragma unroll
+            for (int p = 0; p < PK12_T / 8; ++p) {
+                const int jl = p * 8 + hi, j = j0 + jl;
+                if (j < F && hy < h) {
+                    const _Float16* s = tile + jl * PK12_LD + lo * 12;
+                    const h4 a = *(const h4*)s, b = *(const h4*)(s + 4), c = *(const h4*)(s + 8);
+                    const long r = (long)yy * h + hy;
+                    store_rec12(out + ((long)j * per + r) * 12, a, b, c);
+                    store_rec12(out + ((long)(F + j) * per + r) * 12, a, b, c);
+                }
+            }
+        }
+        __syncthreads();
+    }
+}
 // eps [2F, Hh, Ww, 4] -> noise[n][c][hy][wx] = (u + g*(c - u)) * scale(frame)   (generate.py:349-350, :273-278)
 __global__ void k_unpack_cfg(const _Float16* __restrict__ eps, const int* __restrict__ idx, int F, int mode, int sl, int nwin, int h, int w,
                              float guidance, int scale_upto, float scale, int nkeep, _Float16* __restrict__ noise) {
@@ -639,6 +719,23 @@ int tcl_pack_latents_f16(const void* x, const void* cond, const int* idx, int F,
     TCL_CHECK_ARG(x && cond && idx && out && F > 0);
     long total = (long)F * (mode ? (long)nwin * h : (long)h * w);
     hipLaunchKernelGGL(k_pack_latents, dim3(stream_grid(total, 256, 1)), dim3(256), 0, st, (const _Float16*)x, (const _Float16*)cond, idx, F, mode, sl, nwin, h, w, (_Float16*)out);
+    TCL_LAUNCH_RET();
+}
+int tcl_pack_latents12_f16(const void* x, const void* cond_fg, const void* cond_bg, int bg_frames, const int* idx, int F, int mode, int sl, int nwin,
+                           int h, int w, void* out, hipStream_t st) {
+    TCL_CHECK_ARG(x && cond_fg && cond_bg && idx && out && F > 0 && h > 0 && w > 0 && (mode == 0 || mode == 1) && ((uintptr_t)out & 7) == 0);
+    TCL_CHECK_ARG(bg_frames >= 1);
+    const int bg_one = bg_frames == 1;
+    if (mode) {
+        TCL_CHECK_ARG(sl >= 0 && nwin > 0);
+        TCL_CHECK_ARG(bg_one || bg_frames >= sl + nwin);          // a per-frame background covers every frame the window reads
+        const long tiles = (long)nwin * cdiv(F, PK12_T) * cdiv(h, PK12_T);
+        hipLaunchKernelGGL(k_pack_latents12_yt, dim3((unsigned)(tiles > 8192 ? 8192 : tiles)), dim3(256), 0, st, (const _Float16*)x,
+                           (const _Float16*)cond_fg, (const _Float16*)cond_bg, bg_one, idx, F, sl, nwin, h, w, (_Float16*)out);
+    } else {
+        hipLaunchKernelGGL(k_pack_latents12_xy, dim3(stream_grid((long)F * h * w, 256, 1)), dim3(256), 0, st, (const _Float16*)x,
+                           (const _Float16*)cond_fg, (const _Float16*)cond_bg, bg_one, idx, F, h, w, (_Float16*)out);
+    }
     TCL_LAUNCH_RET();
 }
 int tcl_unpack_cfg_f16(const void* eps, const int* idx, int F, int mode, int sl, int nwin, int h, int w, float guidance, int scale_upto,

@@ -57,6 +57,12 @@ DEFAULTS = dict(  # configs/tclight_default.yaml (generation / post_opt sections
     #   the VAE latent of a light gradient, `source` from the frames' own clean latents, noised to init_strength -- the scheduler is set to
     #   round(n_timesteps / init_strength) steps and entered at the index that leaves int(steps * init_strength) of them (HL.img2img_schedule).
     #   "none": the start is noise (or latents_path) and init_strength changes nothing.  Otherwise latents_path is not consulted.
+    iclight_model="fc", bg_source="upload", fbc_matting=True,
+    # ^ IC-Light's second model, iclight_sd15_fbc (utils/model_utils.py:97-179, init_iclight_bg): "fbc" conditions the 12-channel UNet on the
+    #   foreground latent AND a background latent, the background being the lighting condition.  bg_source: upload | upload_flip (the frames handed
+    #   in as `background`, as they are or mirrored) | left | right | top | bottom | grey (a ramp or a flat grey built on the device, HL.BG_RAMPS).
+    #   fbc_matting: the foreground is matted onto 127-grey with BriaRMBG's alpha before it is encoded (the background demo's run_rmbg); false feeds
+    #   the frames as they are and needs no RMBGEngine.  "fc" (default): none of this is consulted and every path is bit for bit what it was.
     max_tokens_per_pass=None)
     # ^ None: TCL_MAX_TOKENS_PER_PASS (read when the Generator is built), else min(16 M, 80 % of the device's free memory / 10.5 KB) -- a block-major pass
     #   peaks at ~10.4 KB of activations per level-0 token (90 GB for the 8.64 M tokens of 300 frames at 1280x720): a 288 GB MI355X gets the 16 M
@@ -103,6 +109,13 @@ class Generator:
         c.highres_scale, c.highres_denoise = HL.check_highres(c.highres_scale, c.highres_denoise, c.n_timesteps)
         self.highres = c.highres_scale != 1.0
         self.schedule_highres = HL.img2img_schedule(c.n_timesteps, c.highres_denoise) if self.highres else None      # the second pass's schedule
+        c.iclight_model, c.bg_source = HL.check_fbc(c.iclight_model, c.bg_source, c.init_latent, c.highres_scale, bool(cfg.get("background_cond")))
+        self.fbc = c.iclight_model == "fbc"
+        self.bg_per_frame = None           # __call__'s background_per_frame: whether the fbc background is one frame per frame (None: by its length)
+        cin = getattr(self.unet, "w", {}).get("conv_in", (None, None, None))[2]      # a stand-in engine may carry no weights
+        if cin is not None and cin != 4 + HL.cond_channels(c.iclight_model):
+            raise ValueError(f"generation.iclight_model {c.iclight_model}: the UNet's conv_in takes {cin} channels, expected "
+                             f"{4 + HL.cond_channels(c.iclight_model)} (init_iclight(..., cond_channels={HL.cond_channels(c.iclight_model)}))")
         self._lanczos = {}                 # (in, out) -> device table of that axis
         self.batch_size = 2
         self.timing = {}
@@ -112,9 +125,12 @@ class Generator:
     # ------------------------------------------------------------------ data
     def prepare_data(self, frames, background=None):
         """frames: this rank's block [n_local,3,H,W] f32 in [0,1] on the device (generate.py:138-204).  background [1|n_local,3,H,W]:
-        background compositing (generate.py:147-167): alpha from BriaRMBG on the resized frames, `alpha*fg + (1-alpha)*bg`."""
+        background compositing (generate.py:147-167): alpha from BriaRMBG on the resized frames, `alpha*fg + (1-alpha)*bg`.
+        Under iclight_model fbc nothing is composited: prepare_fbc builds the two condition images and self.frames stays the source."""
         c = self.cfg
-        if background is not None:
+        if self.fbc:
+            self.prepare_fbc(frames, background)
+        elif background is not None:
             if self.rmbg is None:
                 raise RuntimeError("background compositing needs an RMBGEngine (Generator(..., rmbg=...))")
             alpha = self.rmbg.estimate_alpha(frames, self.batch_size)
@@ -145,6 +161,40 @@ class Generator:
             self.init_noise = (z[lo:hi] * self.scheduler.init_noise_sigma).to(H16).contiguous()
         else:
             raise NotImplementedError(f"Noise mode '{c.noise_mode}' is not supported.")
+
+    def bg_ramp(self, source, H, W):
+        """bg_source left | right | top | bottom | grey as the [0,1]-convention image VAEEngine.encode takes: [1,3,H,W] f32 = uint8(linspace)/254."""
+        side, start, stop = HL.BG_RAMPS[source]
+        img = torch.empty(1, 3, H, W, dtype=torch.float32, device=self.dev)
+        self.L.tcl_bg_ramp_f32(img, H, W, side, start, stop, stream())
+        return img
+
+    def matte_grey(self, frames, alpha):
+        """The background demo's run_rmbg composite: frames [n,3,H,W] f32, alpha [n,1,H,W] f32 -> trunc(clamp(127 + (255 f - 127) a))/254."""
+        n, _, H, W = frames.shape
+        out = torch.empty(n, 3, H, W, dtype=torch.float32, device=self.dev)
+        self.L.tcl_matte_grey_f32(frames.float().contiguous(), alpha.float().contiguous(), out, n, H, W, stream())
+        return out
+
+    def prepare_fbc(self, frames, background):
+        """The two condition images of the fbc model: fg_frames [n_local,3,H,W] (matted onto grey, or as given) and bg_frames [1|n_local,3,H,W]
+        (bg_source).  A background of one frame serves every frame and is encoded once."""
+        c = self.cfg
+        n, _, H, W = frames.shape
+        if c.fbc_matting:
+            if self.rmbg is None:
+                raise RuntimeError("generation.fbc_matting needs an RMBGEngine (Generator(..., rmbg=...)); fbc_matting: false feeds the frames as they are")
+            self.fg_frames = self.matte_grey(frames, self.rmbg.estimate_alpha(frames, self.batch_size))
+        else:
+            self.fg_frames = frames.float().contiguous()
+        if c.bg_source in HL.BG_RAMPS:
+            self.bg_frames = self.bg_ramp(c.bg_source, H, W)
+        else:
+            if background is None or background.dim() != 4 or background.shape[0] not in (1, n) or tuple(background.shape[1:]) != (3, H, W):
+                raise ValueError(f"generation.bg_source {c.bg_source}: background frames {None if background is None else tuple(background.shape)}, "
+                                 f"expected {(1, 3, H, W)} or {(n, 3, H, W)}")
+            bg = background.to(frames).float()
+            self.bg_frames = (torch.flip(bg, dims=[-1]) if c.bg_source == "upload_flip" else bg).contiguous()
 
     def light_gradient(self, side, H, W):
         """The demo's bg_source image (gradio_demo_iclight.py:241-256) in VAEEngine.encode's [0,1] convention: [1,3,H,W] f32 = uint8(linspace)/254."""
@@ -311,6 +361,10 @@ class Generator:
             frames = [f for c in grp for f in c]
             n = len(frames)
             idx = torch.tensor(frames, dtype=I32, device=self.dev)
+            if self.fbc:                   # cc = (foreground latents [n_local,4,h,w], background latents [1|n_local,4,h,w])
+                xin = torch.empty(2 * n, self.h, self.w, 12, dtype=H16, device=self.dev)
+                L.tcl_pack_latents12_f16(x, cc[0], cc[1], cc[1].shape[0], idx, n, 0, 0, 0, self.h, self.w, xin, stream())
+                return xin, idx, n
             xin = torch.empty(2 * n, self.h, self.w, 8, dtype=H16, device=self.dev)
             L.tcl_pack_latents_f16(x, cc, idx, n, 0, 0, 0, self.h, self.w, xin, stream())
             return xin, idx, n
@@ -329,6 +383,10 @@ class Generator:
             cols = [c for ch in grp for c in ch]
             n = len(cols)
             idx = torch.tensor(cols, dtype=I32, device=self.dev)
+            if self.fbc:                   # cc_full = (foreground latents of all frames, background latents of one frame or of all)
+                xin = torch.empty(2 * n, nwin, self.h, 12, dtype=H16, device=self.dev)
+                L.tcl_pack_latents12_f16(x_full, cc_full[0], cc_full[1], cc_full[1].shape[0], idx, n, 1, sl, nwin, self.h, self.w, xin, stream())
+                return xin, idx, n
             xin = torch.empty(2 * n, nwin, self.h, 8, dtype=H16, device=self.dev)
             L.tcl_pack_latents_f16(x_full, cc_full, idx, n, 1, sl, nwin, self.h, self.w, xin, stream())
             return xin, idx, n
@@ -351,6 +409,20 @@ class Generator:
                 items.append((sl, nwin, ch, up, nkeep))
         return items
 
+    def _check_fbc_conds(self, x, concat_conds):
+        """fbc: concat_conds is the pair (foreground [n_local,4,h,w], background [1|n_local,4,h,w]) of contiguous f16 latents -- the pack kernel
+        reads them by frame index, so their extents are checked here, on the host, once per denoise."""
+        n = x.shape[0]
+        if not isinstance(concat_conds, (tuple, list)) or len(concat_conds) != 2:
+            raise ValueError("iclight_model fbc: concat_conds is the pair (foreground latents, background latents)")
+        fg, bg = concat_conds
+        per_frame = bg.shape[0] > 1 if self.bg_per_frame is None else self.bg_per_frame      # __call__'s background_per_frame, when it was given
+        ok_bg = bg.shape[0] == (n if per_frame else 1) and tuple(bg.shape[1:]) == (4, self.h, self.w)
+        if tuple(fg.shape) != (n, 4, self.h, self.w) or not ok_bg or fg.dtype != H16 or bg.dtype != H16 or not (fg.is_contiguous() and bg.is_contiguous()):
+            raise ValueError(f"iclight_model fbc: foreground latents {tuple(fg.shape)} {fg.dtype}, background latents {tuple(bg.shape)} {bg.dtype}; "
+                             f"expected {(n, 4, self.h, self.w)} and {(n if per_frame else 1, 4, self.h, self.w)} contiguous f16")
+        return per_frame
+
     # ------------------------------------------------------------------ hot loop 1
     @torch.no_grad()
     def ddim_sample(self, x, conds, conds_t, concat_conds, schedule=None):
@@ -369,7 +441,13 @@ class Generator:
         alphas = HL.alpha_schedule(c.alpha_t, c.final_factor_t, len(sch.timesteps))
         xy_sampler = HL.ChunkSampler(c.seed + 7919 * d.rank, c.chunk_size, c.merge_global, c.chunk_ord)
         yt_sampler = HL.ChunkSampler(c.seed + 1, c.chunk_size, c.merge_global, c.chunk_ord)
-        cc_full = d.gather_frames(concat_conds, self.n_total) if c.alpha_t > 0 else None
+        per_frame = self._check_fbc_conds(x, concat_conds) if self.fbc else False
+        cc_full = None
+        if c.alpha_t > 0 and self.fbc:     # the foreground latents of all frames; the background's only when it is per-frame
+            fg, bg = concat_conds
+            cc_full = (d.gather_frames(fg, self.n_total), d.gather_frames(bg, self.n_total) if per_frame else bg)
+        elif c.alpha_t > 0:
+            cc_full = d.gather_frames(concat_conds, self.n_total)
         lo, hi = d.range(self.n_total)
         for i, t in enumerate(sch.timesteps.tolist()):
             self._unet_xy(x, concat_conds, xy_sampler.get_chunks(n_local), conds, t, noises)
@@ -388,20 +466,28 @@ class Generator:
         return x
 
     # ------------------------------------------------------------------ end to end
-    def __call__(self, frames, conds, conds_t, past_flows, mask_bwds, unq_inv, n_total=None, k=None, background=None, frames_hr=None):
+    def __call__(self, frames, conds, conds_t, past_flows, mask_bwds, unq_inv, n_total=None, k=None, background=None, frames_hr=None,
+                 background_per_frame=None):
         """frames: local block [n_local,3,H,W]; conds / conds_t: [2,L,768] f16 (uncond, cond) text embeddings for the xy / yt
         passes (generate.py:553-555); past_flows / mask_bwds / unq_inv: stage-2 inputs for ALL frames (device).
         Returns (relit frames [N,3,H,W] f32, info dict).
         With generation.highres_scale > 1: frames_hr is the local block at HL.highres_size [n_local,3,H2,W2], the stage-2 inputs live at that size
-        and so do the returned frames."""
+        and so do the returned frames.
+        With generation.iclight_model fbc: background [1|n_local,3,H,W] is the bg_source upload / upload_flip image (one frame for all, or this
+        rank's block of a per-frame clip); background_per_frame says which when the block alone cannot (None: more than one frame handed in) --
+        every rank must give the same answer, since a per-frame background is all-gathered for the yt pass."""
         c, d = self.cfg, self.dist
+        self.bg_per_frame = None if background_per_frame is None else bool(background_per_frame)
         if self.highres and background is not None:
             raise ValueError("generation.background_cond together with generation.highres_scale > 1 is not supported")
         self.n_total = n_total or frames.shape[0] * d.world
         ev = lambda: (torch.cuda.synchronize(self.dev), time.perf_counter())[1]
         t0 = ev()
         self.prepare_data(frames, background)
-        concat_conds = self.vae.encode_imgs_batch(self.frames, self.batch_size)
+        if self.fbc:                       # (foreground, background) latents: model_utils.py:97-179 concat_conds, kept apart (one background frame stays one)
+            concat_conds = (self.vae.encode_imgs_batch(self.fg_frames, self.batch_size), self.vae.encode_imgs_batch(self.bg_frames, self.batch_size))
+        else:
+            concat_conds = self.vae.encode_imgs_batch(self.frames, self.batch_size)
         if self.img2img:
             self.build_start(concat_conds)
         t1 = ev()
@@ -461,6 +547,7 @@ class Generator:
         self.timing = dict(encode=t1 - t0, denoise=t2a - t1, decode=t3 - t2, stage1=t4 - t3, stage2=t5 - t4, total=t5 - t0)
         info = dict(timing=self.timing, losses_exposure=losses1, losses_unique=losses2, total_time=t5 - t0,
                     sec_per_frame=(t5 - t0) / self.n_total, total_number_of_frames=self.n_total, init_latent=c.init_latent,
+                    iclight_model=c.iclight_model,
                     init_strength=c.init_strength, scheduler_steps=self.schedule[0], steps_executed=self.schedule[2],
                     max_memory_allocated=torch.cuda.max_memory_allocated(self.dev) / 1024.0 ** 2)
         if self.highres:                   # decode -> u8 -> resize -> encode -> second denoise, between `denoise` and `decode`

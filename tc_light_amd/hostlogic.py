@@ -131,6 +131,50 @@ def check_highres(highres_scale, highres_denoise, n_timesteps=None, background_c
     return scale, denoise
 
 
+ICLIGHT_MODELS = ("fc", "fbc")            # generation.iclight_model: foreground-conditioned (8-channel conv_in) | foreground + background (12)
+BG_SOURCES = ("upload", "upload_flip", "left", "right", "top", "bottom", "grey")       # generation.bg_source (fbc only)
+# bg_source -> (TCL_LIGHT_* side naming the axis, first sample, last sample) of uint8(np.linspace(first, last, n)): IC-Light's background demo
+BG_RAMPS = {"left": (0, 224, 32), "right": (1, 32, 224), "top": (2, 224, 32), "bottom": (3, 32, 224), "grey": (0, 64, 64)}
+
+
+def cond_channels(iclight_model):
+    """Latent channels conv_in takes beside the 4 of x: 4 (fc: the foreground) or 8 (fbc: foreground, then background)."""
+    return 8 if iclight_model == "fbc" else 4
+
+
+def check_fbc(iclight_model, bg_source, init_latent="none", highres_scale=1.0, background_cond=False, inversion=False):
+    """generation.iclight_model / bg_source as (str, str); anything else is a ValueError (run.py, invert.py and Generator raise it before a model
+    is loaded).  Under fbc the background is the lighting condition, so what this engine has not built for it is refused by name: an img2img
+    start (init_latent), the highres pass, background compositing (background_cond) and DDIM inversion."""
+    model = "fc" if iclight_model is None else str(iclight_model).lower()
+    if model not in ICLIGHT_MODELS:
+        raise ValueError(f"generation.iclight_model {iclight_model!r}: expected one of {' | '.join(ICLIGHT_MODELS)}")
+    source = "upload" if bg_source is None else str(bg_source).lower()
+    if source not in BG_SOURCES:
+        raise ValueError(f"generation.bg_source {bg_source!r}: expected one of {' | '.join(BG_SOURCES)}")
+    if model == "fbc":
+        if inversion:
+            raise ValueError("generation.iclight_model fbc: DDIM inversion (invert.py) is not supported for the background-conditioned model")
+        if init_latent is not None and str(init_latent).lower() != "none":
+            raise ValueError(f"generation.iclight_model fbc together with generation.init_latent {init_latent!r} is not supported: the background "
+                             "is the lighting condition")
+        if isinstance(highres_scale, bool) or not isinstance(highres_scale, (int, float)) or float(highres_scale) != 1.0:
+            raise ValueError(f"generation.iclight_model fbc together with generation.highres_scale {highres_scale!r} is not supported")
+        if background_cond:
+            raise ValueError("generation.iclight_model fbc together with generation.background_cond is not supported: fbc takes the background "
+                             "as a condition (generation.bg_source) instead of compositing it")
+    return model, source
+
+
+def fbc_background_per_frame(n_background, n_frames, bg_source="upload"):
+    """The uploaded background of the fbc model is one frame for all (-> False) or exactly one per frame of the run (-> True; with a single frame:
+    False); any other length is a ValueError.  The answer depends on the run's totals only, so every rank gives the same one."""
+    if n_background not in (1, n_frames):
+        raise ValueError(f"generation.background_image_path yields {n_background} frames: generation.bg_source {bg_source} takes 1 or "
+                         f"exactly {n_frames} (the frames of this run)")
+    return n_background == n_frames and n_frames > 1
+
+
 TOME_MAX_SRC_TOKENS = 64 * 1024          # tcl_tome_match_f16 / _affine_f16: source tokens of one match (csrc/merge.hip)
 
 

@@ -30,6 +30,7 @@ import torch
 from .config_utils import save_config
 from .dataparser import VideoDataParser, get_latents_dir, latent_file, save_frames
 from .generate import default_max_tokens_per_pass
+from .hostlogic import check_fbc
 from .lib import lib, stream
 from .vidtome import VidToMe
 
@@ -54,6 +55,8 @@ def check_config(config):
         raise NotImplementedError(f"data.scene_type '{scene_type}': this dataparser is not yet built in tc_light_amd (video and sceneflow are)")
     if scene_type not in ("video", "sceneflow"):
         raise NotImplementedError(f"Scene type '{scene_type}' is not supported.")
+    gen = config.get("generation") or {}          # the background-conditioned model is not inverted (hostlogic.check_fbc names it)
+    check_fbc(gen.get("iclight_model"), gen.get("bg_source"), inversion=True)
     world = int(os.environ.get("WORLD_SIZE", 1))
     if world > 1:
         raise NotImplementedError(f"WORLD_SIZE={world}: DDIM inversion runs in one process (frames are independent; sharding them over ranks is "

@@ -142,7 +142,7 @@ def _delta(name, W, down, up):
         got = (up.shape[0], down.shape[1]) if tuple(down.shape[2:]) == (1, 1) else None
     else:
         got = (up.shape[0],) + tuple(down.shape[1:])
-    narrow = name == "conv_in.weight" and got == (want[0], 4) + want[2:] and want[1] == 8
+    narrow = name == "conv_in.weight" and got == (want[0], 4) + want[2:] and want[1] in (8, 12)
     if got != want and not narrow:
         raise ValueError(f"LoRA {name}: up @ down gives {got if got else tuple(down.shape)}, the weight is {want}")
     d = up.float().flatten(1) @ down.float().flatten(1)        # [out, r] @ [r, in * kh * kw]
@@ -153,7 +153,7 @@ def merge_into(sd, entries, weight=1.0, part="unet"):
     """W += weight * (alpha / r) * up @ down (alpha = r when absent) for every entry of `part` ("unet": lora_unet_*, "te": lora_te_*), in f32
     on the host; entries of the other part are left to the other state dict.  Linear: [out, r] @ [r, in]; 1x1 convolutions the same on the
     squeezed kernel; 3x3 (LoCon): down [r, in, 3, 3], up [out, r, 1, 1], contracted over r.  A conv_in LoRA with 4 input channels goes to
-    the first 4 input channels of the 8-channel IC-Light conv_in.  Everything is checked before anything is written; the merged tensors
+    the first 4 input channels of the 8-channel (fc) or 12-channel (fbc) IC-Light conv_in.  Everything is checked before anything is written; the merged tensors
     replace their entries in `sd` (f32), which is returned.  weight == 0 leaves `sd` untouched."""
     todo = []
     for key, (name, down, up, alpha) in _resolve(sd, entries, part):

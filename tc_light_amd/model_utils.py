@@ -67,26 +67,35 @@ def _with_lora(sd, lora):
     return L.merge_into(sd, entries, weight, part="unet")
 
 
-def load_unet_state(unet_path=None, offset_path=None, seed=1, allow=False, lora=None):
+def load_unet_state(unet_path=None, offset_path=None, seed=1, allow=False, lora=None, cond_channels=4):
     """utils/model_utils.py:14-54: SD-1.5 UNet state dict with the 8-channel conv_in and the IC-Light offsets added to EVERY key; then
-    `lora` (the generation.lora block or lora.LoRASet; None: nothing) merged in f32: base -> conv_in widening -> offsets -> LoRA."""
-    shapes = sd15.unet_param_shapes()
+    `lora` (the generation.lora block or lora.LoRASet; None: nothing) merged in f32: base -> conv_in widening -> offsets -> LoRA.
+    cond_channels: latent channels conv_in takes beside the 4 of x -- 4 (iclight_sd15_fc: the foreground) or 8 (iclight_sd15_fbc, :97-179
+    init_iclight_bg: foreground then background, a 12-channel conv_in); the offset file must be the one of that width."""
+    if cond_channels not in (4, 8):
+        raise ValueError(f"cond_channels {cond_channels!r}: expected 4 (fc) or 8 (fbc)")
+    cin = 4 + cond_channels
+    shapes = sd15.unet_param_shapes() if cond_channels == 4 else sd15.unet_param_shapes(in_channels=cin)      # fc: the call as it always was
     if not (unet_path and os.path.exists(unet_path)):
         _missing("SD-1.5 UNet", unet_path, allow)
         return _with_lora(sd15.random_state_dict(shapes, seed), lora)
     sd = {k: v.float() for k, v in _load_safetensors(unet_path).items()}
     w = sd["conv_in.weight"]
-    if w.shape[1] == 4:                                    # new_conv_in: zero weights for the 4 concat channels (:21-26)
-        w8 = torch.zeros(w.shape[0], 8, w.shape[2], w.shape[3])
+    if w.shape[1] == 4:                                    # new_conv_in: zero weights for the concat channels (:21-26, :106-111)
+        w8 = torch.zeros(w.shape[0], cin, w.shape[2], w.shape[3])
         w8[:, :4] = w
         sd["conv_in.weight"] = w8
     if not (offset_path and os.path.exists(offset_path)):
-        _missing("IC-Light offset (iclight_sd15_fc.safetensors)", offset_path, allow)
+        _missing(f"IC-Light offset (iclight_sd15_{'fbc' if cond_channels == 8 else 'fc'}.safetensors)", offset_path, allow)
     else:
         off = _load_safetensors(offset_path)
         missing = [k for k in sd if k not in off]
         if missing:
             raise KeyError(f"IC-Light offset file lacks keys {missing[:3]} (reference merges strictly, model_utils.py:50-54)")
+        got, want = tuple(off["conv_in.weight"].shape), tuple(sd["conv_in.weight"].shape)
+        if got != want and got in ((320, 8, 3, 3), (320, 12, 3, 3)) and want in ((320, 8, 3, 3), (320, 12, 3, 3)):
+            raise KeyError(f"IC-Light offset conv_in.weight is {got} (the {'fbc' if got[1] == 12 else 'fc'} model's), but generation.iclight_model "
+                           f"{'fbc' if want[1] == 12 else 'fc'} takes {want}: point models.iclight_offset at that model's file")
         bad = [k for k in sd if tuple(off[k].shape) != tuple(sd[k].shape)]
         if bad:
             raise KeyError(f"IC-Light offset shape mismatch on {bad[:3]}: {tuple(off[bad[0]].shape)} vs {tuple(sd[bad[0]].shape)}")
@@ -239,12 +248,13 @@ def load_rmbg_state(path=None, seed=3, allow=False):
     return _read_state(path)
 
 
-def init_iclight(device="cuda", models=None, seed=12345, lora=None):
-    """-> (pipe-like namespace with .unet/.vae/.scheduler, scheduler, 'iclight').  `lora`: see load_unet_state."""
+def init_iclight(device="cuda", models=None, seed=12345, lora=None, cond_channels=4):
+    """-> (pipe-like namespace with .unet/.vae/.scheduler, scheduler, 'iclight').  `lora`, `cond_channels`: see load_unet_state."""
     from types import SimpleNamespace
     m = models or {}
     ok = allow_random(m)
-    unet = UNetEngine(load_unet_state(m.get("unet"), m.get("iclight_offset"), allow=ok, lora=lora), device, VidToMe(device, seed=seed))
+    unet = UNetEngine(load_unet_state(m.get("unet"), m.get("iclight_offset"), allow=ok, lora=lora, cond_channels=cond_channels), device,
+                      VidToMe(device, seed=seed))
     vae = VAEEngine(load_vae_state(m.get("vae"), allow=ok), device)
     scheduler = DPMSolverSDEScheduler(num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012)
     return SimpleNamespace(unet=unet, vae=vae, scheduler=scheduler), scheduler, "iclight"

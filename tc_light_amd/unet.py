@@ -458,7 +458,7 @@ class UNetEngine:
         L.tcl_im2col3x3_small_f16(x_in, col, Bh, Hh, Ww, w["conv_in"][2], 128, stream())
         h = o.gemm(col, w["conv_in"][0], w["conv_in"][1])
         del col
-        self._fl(2.0 * Hh * Ww * 72 * 320, B, Bh)
+        self._fl(2.0 * Hh * Ww * 9 * w["conv_in"][2] * 320, B, Bh)
         sizes = [(Hh, Ww)]
         skips = [(torch.cat([h, h]) if half else h, 320)]
         hh, ww, c = Hh, Ww, 320
