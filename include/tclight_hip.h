@@ -254,6 +254,26 @@ int tcl_light_start_f16(void* out, const void* x0, long x0_stride, const float* 
  *   accesses when H*W % 4 == 0 and the three pointers are 16 B aligned. */
 int tcl_bg_ramp_f32(float* out, int H, int W, int side, int start, int stop, hipStream_t st);
 int tcl_matte_grey_f32(const float* frames, const float* alpha, float* out, int n, int H, int W, hipStream_t st);
+/* generation.normal: the background demo's "Compute Normal" (process_normal) on the fbc model -- four relights of one foreground under the left /
+ * right / bottom / top ramps, one seed, turned into a surface normal (csrc/light.hip).
+ * tcl_matte_grey_sigma_f32 (the demo's run_rmbg(img, sigma=16)): tcl_matte_grey_f32 with v = 127 + ((u - 127) + sigma) a -- the same f32 operation
+ *   order, no fma contraction, q = trunc(clamp(v, 0, 255)) (NaN -> 0), out = q/254.  (u - 127) + 0 is exact, so sigma = 0 is tcl_matte_grey_f32 bit for
+ *   bit.  A NaN sigma returns TCL_EINVAL.
+ * tcl_fbc_normal: left / right / bottom / top [n,3,H,W] f32 (what VAEEngine.decode_latents_batch returns), alpha [n,1,H,W] f32 or NULL (= 1
+ *   everywhere) -> normal_u8 [n,H,W,3] u8 (required; RGB = (u, v, h)), normal_f32 [n,3,H,W] f32 and ambient [n,3,H,W] f32 (each may be NULL).  Per
+ *   pixel in f32, no fma contraction, IEEE division and square root; L, R, B, T = the inputs clamped to [0,1], NaN -> 0.  Per channel c:
+ *   A = (((L+R)+B)+T) * 0.25;  q(X) = (X + e)/(A + e) - 1, e = 1e-5f;  u_c = (q(R) - q(L)) * 0.5;  v_c = (q(T) - q(B)) * 0.5.  Across channels:
+ *   u = ((u_0+u_1)+u_2)/3, v likewise;  s = clamp((1 - u*u) - v*v, 0, 1e5);  h = s^5 as s2 = s*s, s4 = s2*s2, h = s4*s (the demo's exponent
+ *   0.5 * sigma with sigma = 10; no powf);  len = sqrt((u*u + v*v) + h*h);  N = (u, v, h)/len;  m = trunc(clamp(alpha*255, 0, 255))/255 (the demo's
+ *   u8 round trip of the matte; its Lanczos resize is the identity at the working size);  out = N*m + (0, 0, 1)*(1 - m);
+ *   normal_u8 = trunc(clamp(out*127.5 + 127.5, 0, 255));  normal_f32 = out;  ambient = A per channel.
+ *   Bounds the design rests on: every clamped relight is at most 4A, so q lies in [-1, 3]; u^2 + v^2 + h^2 >= 0.30 (the minimum of r + (1 - r)^10
+ *   over r = u^2 + v^2), so no division can produce NaN or Inf for finite input.
+ *   One thread handles four consecutive pixels of a frame and issues all its loads before the arithmetic; 16 B loads when H*W % 4 == 0, the f32
+ *   pointers are 16 B and normal_u8 4 B aligned, a scalar path otherwise.  Null required pointers, n, H, W <= 0 and 3*n*H*W >= 2^31 return TCL_EINVAL. */
+int tcl_matte_grey_sigma_f32(const float* frames, const float* alpha, float* out, int n, int H, int W, float sigma, hipStream_t st);
+int tcl_fbc_normal(const float* left, const float* right, const float* bottom, const float* top, const float* alpha, void* normal_u8,
+                   float* normal_f32, float* ambient, int n, int H, int W, hipStream_t st);
 /* The highres pass (gradio_demo_iclight.py:301-334: highres_scale, highres_denoise; csrc/resize.hip): decoded frames -> u8 -> PIL's LANCZOS resize
  * -> the [0,1]-convention image the VAE encoder takes.
  * tcl_frames_to_u8: frames [N,3,H,W] f32 (what VAEEngine.decode returns) -> out [N,H,W,3] u8, u = trunc(clamp(fl32(255*p), 0, 255)): one f32 product

@@ -4,6 +4,8 @@ plus [--light left|right|top|bottom|source] [--strength F]: IC-Light's "Lighting
 (generation.iclight_model / bg_source / fbc_matting; models.iclight_offset is then the fbc file) -- the UNet sees the foreground and a background latent,
 and [--highres_scale F] [--highres_denoise F]: IC-Light's highres pass (generation.highres_scale / highres_denoise) -- the relit frames are resized
 with PIL's LANCZOS filter to multiples of 64 and refined by a second img2img denoise; flows, masks, ids, output_gt and the result live at that size.
+[--normal]: IC-Light's "Compute Normal" on the fbc model (generation.normal) -- four relights under the left / right / bottom / top ramps with one seed
+become normal.npy / normal.mp4 (per-frame surface normals), relit_<side>.npy and the ambient video as output.*; no stage 1 / 2.
 data.scene_type picks the parser (generate.py:84-95): video (VideoDataParser) or sceneflow (SceneFlowDataParser: ground-truth depth, poses and
 flows -> voxelised Unique Video Tensor ids); carla and interiornet are not built.
 
@@ -24,8 +26,8 @@ import torch
 from tc_light_amd.config_utils import Config, load_config, save_config
 from tc_light_amd.dataparser import VideoDataParser, get_frame_ids, save_loss_curve, save_video
 from tc_light_amd.generate import DEFAULTS, Generator
-from tc_light_amd.hostlogic import (check_fbc, check_highres, check_highres_tokens, check_init, cond_channels, fbc_background_per_frame,
-                                    highres_size)
+from tc_light_amd.hostlogic import (check_fbc, check_highres, check_highres_tokens, check_init, check_normal, cond_channels,
+                                    fbc_background_per_frame, highres_size)
 from tc_light_amd.model_utils import allow_random, init_iclight
 from tc_light_amd.parallel import Dist
 from tc_light_amd.text import encode_prompt_pair
@@ -33,6 +35,32 @@ from tc_light_amd.text import encode_prompt_pair
 
 def seed_everything(seed):
     torch.manual_seed(seed); torch.cuda.manual_seed_all(seed); random.seed(seed); np.random.seed(seed)
+
+
+def _save_normal_run(config, g, name, nrm, ambient, relit, info, frames_gt, frame_ids, fps):
+    """The run directory of generation.normal: normal.npy first (u8 [N,H,W,3], RGB = (u, v, h)), normal.mp4, relit_<side>.npy, the ambient video as
+    output.* beside output_gt.* (what evaluate.py looks for) and config.yaml."""
+    config.total_time += info["total_time"]
+    config.sec_per_frame = config.total_time / len(frame_ids)
+    config.max_memory_allocated = max(config.max_memory_allocated, info["max_memory_allocated"])
+    g.scheduler_steps, g.steps_executed = info["scheduler_steps"], info["steps_executed"]
+    g.normal_denoise_seconds = {s: float(t) for s, t in info["denoise_per_direction"].items()}
+    path = os.path.join(g.output_path, f"lmr_{g.local_merge_ratio}_gmr_{g.global_merge_ratio}_alpha_t_{g.alpha_t}_opt_{name}")
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "normal.npy"), nrm.cpu().numpy())      # first: survives whatever fails behind it
+    save_config(config, path, gene=True)
+    for side, frames in relit.items():
+        np.save(os.path.join(path, f"relit_{side}.npy"), (frames.clamp(0, 1) * 255).byte().permute(0, 2, 3, 1).cpu().numpy())
+    ambient = ambient.clamp(0, 1)
+    np.save(os.path.join(path, "output.npy"), (ambient * 255).byte().permute(0, 2, 3, 1).cpu().numpy())
+    # save_video quantises trunc(255 x): (u + 0.5)/255 comes back as u whatever the rounding of the division
+    save_video((nrm.permute(0, 3, 1, 2).float() + 0.5) / 255, path, save_frame=False, stem="normal", fps=fps, gif=False)
+    save_video(ambient, path, save_frame=bool(g.get("save_frame", False)), fps=fps, gif=False)
+    gt_path = os.path.join(path, "gt")
+    if not os.path.exists(gt_path) or len(os.listdir(gt_path)) != len(frame_ids):
+        save_video(frames_gt, path, save_frame=False, post_fix="_gt", fps=fps, gif=False)
+    print(f"[INFO] normals of {len(frame_ids)} frames (4 relights each) in {info['total_time']:.1f} s "
+          f"({1 / config.sec_per_frame:.3f} frames/s) -> {path}")
 
 
 def main(argv=None):
@@ -63,7 +91,18 @@ def main(argv=None):
         config.generation.init_latent, config.generation.highres_scale, bool(config.generation.get("background_cond")))
     config.generation.fbc_matting = bool(config.generation.get("fbc_matting", DEFAULTS["fbc_matting"]))
     fbc = config.generation.iclight_model == "fbc"
-    if fbc and config.generation.bg_source in ("upload", "upload_flip") and not config.generation.get("background_image_path"):
+    # IC-Light's "Compute Normal" (generation.normal; --normal): needs the fbc model, refused here otherwise
+    config.generation.normal = config.generation.get("normal", DEFAULTS["normal"])
+    normal = bool(check_normal(config.generation.normal, config.generation.iclight_model, config.generation.fbc_matting,
+                               config.post_opt.get("apply_opt", DEFAULTS["apply_opt"])))
+    if normal:
+        print("[INFO] generation.normal: the four ramps left / right / bottom / top are the backgrounds; generation.bg_source and "
+              "generation.background_image_path are not consulted.")
+        if config.post_opt.get("apply_opt", DEFAULTS["apply_opt"]):
+            print("[INFO] generation.normal: stage 1 / 2 do not run on the four relights and no flows are estimated (exposure alignment per direction "
+                  "would bias their ratios); post_opt.apply_opt is recorded as false.")
+        config.post_opt.apply_opt = False
+    if fbc and not normal and config.generation.bg_source in ("upload", "upload_flip") and not config.generation.get("background_image_path"):
         raise ValueError(f"generation.bg_source {config.generation.bg_source} needs generation.background_image_path")
     highres = config.generation.highres_scale != 1.0
     data_hr = None
@@ -142,7 +181,7 @@ def main(argv=None):
         background = parser.load_video(path=g.background_image_path)
         if background.shape[0] == len(frame_ids) and world > 1:     # a per-frame background video: this rank's block of it
             background = background[lo:hi]
-    elif fbc and g.bg_source in ("upload", "upload_flip"):     # the background the fbc model is conditioned on: one frame for all, or one per frame
+    elif fbc and not normal and g.bg_source in ("upload", "upload_flip"):     # the background the fbc model is conditioned on: one frame for all, or one per frame
         background = parser.load_video(path=g.background_image_path)
         bg_per_frame = fbc_background_per_frame(background.shape[0], len(frame_ids), g.bg_source)      # the same answer on every rank
         if bg_per_frame and world > 1:
@@ -151,6 +190,11 @@ def main(argv=None):
     for name, prompt in g.prompt.items():
         conds = encode_prompt_pair(prompt, g.negative_prompt, dev, models.get("text_encoder"), allow_random=ok_random, lora=lora)
         conds_t = encode_prompt_pair(g.prompt_t, g.negative_prompt_t, dev, models.get("text_encoder"), allow_random=ok_random, lora=lora)
+        if normal:
+            nrm, ambient, relit, info = gen.normals(frames_all[lo:hi], conds, conds_t, n_total=len(frame_ids))
+            if rank == 0:
+                _save_normal_run(config, g, name, nrm, ambient, relit, info, frames_out, frame_ids, parser.fps)
+            continue
         masks = inv = k = past = None
         if scene is not None:
             masks, inv, k, past = scene["masks"], scene["inv"], scene["k"], scene["past_flows"]

@@ -92,8 +92,13 @@ def load_config(argv=None, print_config=True):
     ap.add_argument("--bg_source", choices=("upload", "upload_flip", "left", "right", "top", "bottom", "grey"), default=None,
                     help="the background of the fbc model: generation.background_image_path (as it is or flipped), a grey ramp or flat grey, "
                     "for a fast usage")
+    # IC-Light's "Compute Normal" on the fbc model (generation.normal, generate.py DEFAULTS)
+    ap.add_argument("--normal", action="store_true", help="fbc only: relight under the left / right / bottom / top ramps with one seed and write "
+                    "per-frame normal maps and the ambient video instead of one relight, for a fast usage")
     a = ap.parse_args(argv)
     cfg = load_yaml_chain(a.config, a.base_config)
+    if a.normal:
+        cfg.generation.normal = True
     if a.iclight_model is not None:
         cfg.generation.iclight_model = a.iclight_model
     if a.bg_source is not None:

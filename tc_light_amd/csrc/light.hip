@@ -1,7 +1,9 @@
 // IC-Light's "Lighting Preference" start (gradio_demo_iclight.py:235-299: bg_source, lowres_denoise, the img2img call), gfx950:
 //   * the left / right / top / bottom light gradient as the [0,1]-convention image the VAE encoder takes;
 //   * the img2img start latents  x_start = alpha*x0 + sigma_t*z  of the first executed sigma (diffusers' add_noise);
-//   * for the background-conditioned model (generation.iclight_model: fbc): the background ramps of bg_source and the foreground's grey matte.
+//   * for the background-conditioned model (generation.iclight_model: fbc): the background ramps of bg_source and the foreground's grey matte;
+//   * for generation.normal (the background demo's "Compute Normal", process_normal): the matte with its sigma offset and the kernel that turns the
+//     four directional relights into a surface normal and the ambient image.
 // Both run once per relight, in front of the denoise loop; every rounding is spelled out because the tests ask for the bits numpy gives.
 #include "common.h"
 #include "../../include/tclight_hip.h"
@@ -84,10 +86,11 @@ __global__ __launch_bounds__(256) void k_light_start(_Float16* __restrict__ out,
 // IC-Light's background demo mattes the foreground onto 127-grey before the VAE sees it (run_rmbg: 127 + (img - 127) * alpha, clipped to uint8).
 // frames [n,3,hw] f32 in [0,1], alpha [n,1,hw] f32: u = fl32(255 f); v = fl32(127 + fl32(fl32(u - 127) a)); q = trunc(clamp(v, 0, 255)), NaN -> 0;
 // out = q/254 (the u/254 convention of light_sample).  A lane owns V consecutive pixels of one frame: one alpha load serves the three planes.
-__device__ __forceinline__ float matte_sample(float f, float a) {
+// sigma: process_normal's run_rmbg(img, sigma=16) adds it to (u - 127) before the alpha; (u - 127) + 0 is exact, so sigma = 0 is the plain matte.
+__device__ __forceinline__ float matte_sample(float f, float a, float sigma) {
 #pragma clang fp contract(off)
     const float u = 255.f * f;
-    const float d = u - 127.f;
+    const float d = (u - 127.f) + sigma;
     const float m = d * a;
     const float v = 127.f + m;
     const float q = truncf(fminf(fmaxf(v, 0.f), 255.f));
@@ -95,7 +98,7 @@ __device__ __forceinline__ float matte_sample(float f, float a) {
 }
 template <bool VEC>
 __global__ __launch_bounds__(256) void k_matte_grey(const float* __restrict__ frames, const float* __restrict__ alpha, float* __restrict__ out,
-                                                    long n, long hw) {
+                                                    long n, long hw, float sigma) {
     constexpr int V = VEC ? 4 : 1;
     const long per = hw / V, total = n * per;
     for (long g = (long)blockIdx.x * blockDim.x + threadIdx.x; g < total; g += (long)gridDim.x * blockDim.x) {
@@ -106,17 +109,148 @@ __global__ __launch_bounds__(256) void k_matte_grey(const float* __restrict__ fr
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
                 const float4 x = *(const float4*)(frames + (f * 3 + c) * hw + i);
-                *(float4*)(out + (f * 3 + c) * hw + i) = make_float4(matte_sample(x.x, a.x), matte_sample(x.y, a.y), matte_sample(x.z, a.z),
-                                                                     matte_sample(x.w, a.w));
+                *(float4*)(out + (f * 3 + c) * hw + i) = make_float4(matte_sample(x.x, a.x, sigma), matte_sample(x.y, a.y, sigma),
+                                                                     matte_sample(x.z, a.z, sigma), matte_sample(x.w, a.w, sigma));
             }
         } else {
             const float a = *pa;
-            for (int c = 0; c < 3; ++c) out[(f * 3 + c) * hw + i] = matte_sample(frames[(f * 3 + c) * hw + i], a);
+            for (int c = 0; c < 3; ++c) out[(f * 3 + c) * hw + i] = matte_sample(frames[(f * 3 + c) * hw + i], a, sigma);
+        }
+    }
+}
+
+// process_normal of IC-Light's background demo on the four decoded relights of one pixel (left, right, bottom, top; 3 channels each) and its matting
+// alpha.  Every operation in f32, rounded on its own.  The inputs are clamped to [0,1] (NaN -> 0), so each is at most 4A and q lies in [-1, 3];
+// u^2 + v^2 + h^2 >= 0.30 (h = (1 - u^2 - v^2)^5 where that is positive), so neither division meets a zero and finite input gives finite output.
+struct NormalPx { float n[3]; float amb[3]; };
+__device__ __forceinline__ float clamp01(float x) { return fminf(fmaxf(x, 0.f), 1.f); }      // NaN -> 0
+__device__ __forceinline__ NormalPx normal_sample(const float l[3], const float r[3], const float b[3], const float t[3], float a) {
+#pragma clang fp contract(off)
+    const float e = 1e-5f;
+    NormalPx o;
+    float uc[3], vc[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float L = clamp01(l[c]), R = clamp01(r[c]), B = clamp01(b[c]), T = clamp01(t[c]);
+        const float A = (((L + R) + B) + T) * 0.25f;
+        const float den = A + e;
+        const float ql = (L + e) / den - 1.f, qr = (R + e) / den - 1.f, qb = (B + e) / den - 1.f, qt = (T + e) / den - 1.f;
+        uc[c] = (qr - ql) * 0.5f;
+        vc[c] = (qt - qb) * 0.5f;
+        o.amb[c] = A;
+    }
+    const float u = ((uc[0] + uc[1]) + uc[2]) / 3.f, v = ((vc[0] + vc[1]) + vc[2]) / 3.f;
+    const float uu = u * u, vv = v * v;
+    const float s = fminf(fmaxf((1.f - uu) - vv, 0.f), 1e5f);
+    const float s2 = s * s, s4 = s2 * s2, h = s4 * s;          // the demo's ** (0.5 * sigma), sigma = 10
+    const float len = sqrtf((uu + vv) + h * h);
+    const float m = truncf(fminf(fmaxf(a * 255.f, 0.f), 255.f)) / 255.f;      // the demo's u8 round trip of the matte; NaN -> 0
+    const float k = 1.f - m;
+    o.n[0] = (u / len) * m + 0.f * k;                          // the (0, 0, 1) of the blend: -0 becomes +0, as in the stated formula
+    o.n[1] = (v / len) * m + 0.f * k;
+    o.n[2] = (h / len) * m + k;
+    return o;
+}
+__device__ __forceinline__ unsigned normal_quant(float x) {
+#pragma clang fp contract(off)
+    const float y = x * 127.5f;
+    return (unsigned)truncf(fminf(fmaxf(y + 127.5f, 0.f), 255.f));
+}
+
+// left / right / bottom / top [n,3,hw] f32, alpha [n,1,hw] f32 or NULL (= 1) -> nu8 [n,hw,3] u8, nf32 / amb [n,3,hw] f32 (either may be NULL).
+// HBM-bound (52 B in, up to 27 B out per pixel).  A lane owns 4 consecutive pixels of one frame and issues its 13 loads before the first operation
+// on them.  VEC: hw % 4 == 0 and every pointer aligned -> 16 B loads, the 12 u8 as three dwords, 16 B stores of the f32 planes.  Otherwise dword loads at
+// indices clamped to the frame (a lane of the last group loads the last pixel again, and stores only its own).  ALPHA: false = no matte, alpha is 1.
+template <bool VEC, bool ALPHA>
+__global__ __launch_bounds__(256) void k_fbc_normal(const float* __restrict__ left, const float* __restrict__ right, const float* __restrict__ bottom,
+                                                    const float* __restrict__ top, const float* __restrict__ alpha, uint8_t* __restrict__ nu8,
+                                                    float* __restrict__ nf32, float* __restrict__ amb, long n, long hw) {
+    const long per = (hw + 3) / 4, total = n * per;
+    for (long g = (long)blockIdx.x * blockDim.x + threadIdx.x; g < total; g += (long)gridDim.x * blockDim.x) {
+        const long f = g / per, i = (g - f * per) * 4;
+        const float* src[4] = {left, right, bottom, top};
+        float x[4][3][4], a[4] = {1.f, 1.f, 1.f, 1.f};
+        if (VEC) {
+            if (ALPHA) {
+                const float4 q = *(const float4*)(alpha + f * hw + i);
+                a[0] = q.x; a[1] = q.y; a[2] = q.z; a[3] = q.w;
+            }
+#pragma unroll
+            for (int d = 0; d < 4; ++d)
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    const float4 q = *(const float4*)(src[d] + (f * 3 + c) * hw + i);
+                    x[d][c][0] = q.x; x[d][c][1] = q.y; x[d][c][2] = q.z; x[d][c][3] = q.w;
+                }
+        } else {
+            long p[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) p[j] = i + j < hw ? i + j : hw - 1;
+            if (ALPHA) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) a[j] = alpha[f * hw + p[j]];
+            }
+#pragma unroll
+            for (int d = 0; d < 4; ++d)
+#pragma unroll
+                for (int c = 0; c < 3; ++c)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) x[d][c][j] = src[d][(f * 3 + c) * hw + p[j]];
+        }
+        __builtin_amdgcn_sched_barrier(0);      // nothing below is scheduled in front of a load: the scheduler otherwise trickles them in behind the divisions
+        NormalPx o[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float l[3], r[3], b[3], t[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) { l[c] = x[0][c][j]; r[c] = x[1][c][j]; b[c] = x[2][c][j]; t[c] = x[3][c][j]; }
+            o[j] = normal_sample(l, r, b, t, a[j]);
+        }
+        unsigned q[12];
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) q[j * 3 + c] = normal_quant(o[j].n[c]);
+        if (VEC) {
+            unsigned* pu = (unsigned*)(nu8 + (f * hw + i) * 3);
+#pragma unroll
+            for (int w = 0; w < 3; ++w) pu[w] = q[4 * w] | (q[4 * w + 1] << 8) | (q[4 * w + 2] << 16) | (q[4 * w + 3] << 24);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                if (nf32) *(float4*)(nf32 + (f * 3 + c) * hw + i) = make_float4(o[0].n[c], o[1].n[c], o[2].n[c], o[3].n[c]);
+                if (amb) *(float4*)(amb + (f * 3 + c) * hw + i) = make_float4(o[0].amb[c], o[1].amb[c], o[2].amb[c], o[3].amb[c]);
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (i + j < hw) {
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) {
+                        nu8[(f * hw + i + j) * 3 + c] = (uint8_t)q[j * 3 + c];
+                        if (nf32) nf32[(f * 3 + c) * hw + i + j] = o[j].n[c];
+                        if (amb) amb[(f * 3 + c) * hw + i + j] = o[j].amb[c];
+                    }
+                }
+            }
         }
     }
 }
 
 extern "C" {
+
+int tcl_fbc_normal(const float* left, const float* right, const float* bottom, const float* top, const float* alpha, void* normal_u8,
+                   float* normal_f32, float* ambient, int n, int H, int W, hipStream_t st) {
+    TCL_CHECK_ARG(left && right && bottom && top && normal_u8 && n > 0 && H > 0 && W > 0);
+    TCL_CHECK_ARG(3L * n * H * W < (1L << 31));
+    const long hw = (long)H * W;
+    const uintptr_t p16 = (uintptr_t)left | (uintptr_t)right | (uintptr_t)bottom | (uintptr_t)top | (uintptr_t)alpha | (uintptr_t)normal_f32 |
+                          (uintptr_t)ambient;      // a null optional pointer adds no bit
+    const bool vec = hw % 4 == 0 && (p16 & 15) == 0 && ((uintptr_t)normal_u8 & 3) == 0;
+    const int grid = stream_grid(n * ((hw + 3) / 4), 256, 1);
+    auto k = vec ? (alpha ? k_fbc_normal<true, true> : k_fbc_normal<true, false>) : (alpha ? k_fbc_normal<false, true> : k_fbc_normal<false, false>);
+    hipLaunchKernelGGL(k, dim3(grid), dim3(256), 0, st, left, right, bottom, top, alpha, (uint8_t*)normal_u8, normal_f32, ambient, (long)n, hw);
+    TCL_LAUNCH_RET();
+}
 
 int tcl_light_gradient_f32(float* out, int H, int W, int side, hipStream_t st) {
     TCL_CHECK_ARG(out && H > 0 && W > 0 && side >= TCL_LIGHT_LEFT && side <= TCL_LIGHT_BOTTOM && ((uintptr_t)out & 15) == 0);
@@ -135,15 +269,19 @@ int tcl_bg_ramp_f32(float* out, int H, int W, int side, int start, int stop, hip
     TCL_LAUNCH_RET();
 }
 
-int tcl_matte_grey_f32(const float* frames, const float* alpha, float* out, int n, int H, int W, hipStream_t st) {
-    TCL_CHECK_ARG(frames && alpha && out && n > 0 && H > 0 && W > 0);
+int tcl_matte_grey_sigma_f32(const float* frames, const float* alpha, float* out, int n, int H, int W, float sigma, hipStream_t st) {
+    TCL_CHECK_ARG(frames && alpha && out && n > 0 && H > 0 && W > 0 && sigma == sigma);
     const long hw = (long)H * W;
     const bool vec = hw % 4 == 0 && (((uintptr_t)frames | (uintptr_t)alpha | (uintptr_t)out) & 15) == 0;
     if (vec)
-        hipLaunchKernelGGL(k_matte_grey<true>, dim3(stream_grid(n * (hw / 4), 256, 1)), dim3(256), 0, st, frames, alpha, out, (long)n, hw);
+        hipLaunchKernelGGL(k_matte_grey<true>, dim3(stream_grid(n * (hw / 4), 256, 1)), dim3(256), 0, st, frames, alpha, out, (long)n, hw, sigma);
     else
-        hipLaunchKernelGGL(k_matte_grey<false>, dim3(stream_grid(n * hw, 256, 1)), dim3(256), 0, st, frames, alpha, out, (long)n, hw);
+        hipLaunchKernelGGL(k_matte_grey<false>, dim3(stream_grid(n * hw, 256, 1)), dim3(256), 0, st, frames, alpha, out, (long)n, hw, sigma);
     TCL_LAUNCH_RET();
+}
+
+int tcl_matte_grey_f32(const float* frames, const float* alpha, float* out, int n, int H, int W, hipStream_t st) {
+    return tcl_matte_grey_sigma_f32(frames, alpha, out, n, H, W, 0.f, st);
 }
 
 int tcl_light_start_f16(void* out, const void* x0, long x0_stride, const float* z, long z_stride, int N, long chw, float alpha, float sigma_t,

@@ -181,10 +181,11 @@ def save_frames(frames, path, ext="png", frame_ids=None):
         Image.fromarray(fr).save(os.path.join(path, "{:04}.{}".format(i, ext)))
 
 
-def save_video(frames, path, frame_ids=None, save_frame=False, gif=True, post_fix="", fps=30):
+def save_video(frames, path, frame_ids=None, save_frame=False, gif=True, post_fix="", fps=30, stem="output"):
     """utils/VidToMe/utils.py:147-179.  Returns the path of what was written.  Encoders are probed in the reference's order (torchvision
     write_video libx264 crf 23 / medium for .mp4, imageio for .gif, PIL as the gif fallback); with none importable the uint8 frames are
-    written as `output{post_fix}.npy` and as PNGs so nothing is lost."""
+    written as `output{post_fix}.npy` and as PNGs so nothing is lost.  stem: the file name in place of `output` (run.py's normal.mp4)."""
+    fdir = f"frames{post_fix}" if stem == "output" else f"{stem}_frames{post_fix}"
     os.makedirs(path, exist_ok=True)
     ids = list(frame_ids) if frame_ids is not None else list(range(len(frames)))
     frames = frames[ids]
@@ -215,7 +216,7 @@ def save_video(frames, path, frame_ids=None, save_frame=False, gif=True, post_fi
 
     # an encoder that is missing OR fails (a torchvision / PyAV build without libx264, a cv2 writer error) must not lose a finished
     # relight: every failure falls through to the next writer and finally to .npy + PNG frames
-    dst = os.path.join(path, f"output{post_fix}.gif" if gif else f"output{post_fix}.mp4")
+    dst = os.path.join(path, f"{stem}{post_fix}.gif" if gif else f"{stem}{post_fix}.mp4")
     for writer in ((_gif_imageio, _gif_pil) if gif else (_mp4_torchvision, _mp4_cv2)):
         try:
             writer(dst)
@@ -228,23 +229,23 @@ def save_video(frames, path, frame_ids=None, save_frame=False, gif=True, post_fi
                 os.remove(dst)
     if out is None and not gif:                        # no H.264 encoder: one playable file all the same (Motion-JPEG AVI through PIL)
         try:
-            out = os.path.join(path, f"output{post_fix}.avi")
+            out = os.path.join(path, f"{stem}{post_fix}.avi")
             write_mjpeg_avi(out, proc, fps=fps)
-            print(f"[INFO] no H.264 encoder (torchvision / cv2) in this environment: wrote Motion-JPEG {out} instead of output{post_fix}.mp4")
+            print(f"[INFO] no H.264 encoder (torchvision / cv2) in this environment: wrote Motion-JPEG {out} instead of {stem}{post_fix}.mp4")
         except Exception as e:            # noqa: BLE001
             print(f"[WARN] mjpeg_avi failed ({type(e).__name__}: {e})")
             if os.path.exists(out):
                 os.remove(out)
             out = None
     if out is None:                                    # no encoder at all: keep the data, say so
-        out = os.path.join(path, f"output{post_fix}.npy")
+        out = os.path.join(path, f"{stem}{post_fix}.npy")
         np.save(out, proc.numpy())
-        save_frames(frames, os.path.join(path, f"frames{post_fix}"), frame_ids=ids)
-        print(f"[INFO] no working video encoder (torchvision / cv2 / imageio / PIL): wrote {out} and PNG frames instead of output{post_fix}.mp4")
+        save_frames(frames, os.path.join(path, fdir), frame_ids=ids)
+        print(f"[INFO] no working video encoder (torchvision / cv2 / imageio / PIL): wrote {out} and PNG frames instead of {stem}{post_fix}.mp4")
     else:
         print(f"[INFO] save video to {out}")
     if save_frame:
-        save_frames(frames, os.path.join(path, f"frames{post_fix}"), frame_ids=ids)
+        save_frames(frames, os.path.join(path, fdir), frame_ids=ids)
     return out
 
 

@@ -7,6 +7,8 @@ start by an img2img one and ddim_sample enters a longer schedule part-way; the l
 generation.highres_scale > 1 (the second half of the same function, :301-334): highres_pass sits between ddim_sample and the decode -- decode ->
 u8 -> PIL-exact LANCZOS resize (csrc/resize.hip) -> encode -> img2img start -> the same ddim_sample at the larger size; decode and stages 1 / 2 then
 run on the frames the user gets.
+generation.normal (fbc only; the background demo's process_normal): Generator.normals runs the matte and the foreground encode once, ddim_sample and the
+decode once per ramp (left, right, bottom, top) from the same start, and one tcl_fbc_normal launch over the four results; no stage 1 / 2.
 
 Python sequences kernel launches and collectives; tensors never leave the device inside the timed region and there is no
 per-iteration host sync (the reference syncs on loss.item() and moves the token bank through the CPU).
@@ -63,6 +65,10 @@ DEFAULTS = dict(  # configs/tclight_default.yaml (generation / post_opt sections
     #   in as `background`, as they are or mirrored) | left | right | top | bottom | grey (a ramp or a flat grey built on the device, HL.BG_RAMPS).
     #   fbc_matting: the foreground is matted onto 127-grey with BriaRMBG's alpha before it is encoded (the background demo's run_rmbg); false feeds
     #   the frames as they are and needs no RMBGEngine.  "fc" (default): none of this is consulted and every path is bit for bit what it was.
+    normal=False,
+    # ^ IC-Light's "Compute Normal" (the background demo's process_normal), fbc only: Generator.normals relights the frames under the left / right /
+    #   bottom / top ramps from one seed and turns the four results into per-frame surface normals and the ambient image (tcl_fbc_normal).
+    #   bg_source is not consulted, stage 1 / 2 do not run.  false (default): nothing of it is consulted and every path is what it was.
     max_tokens_per_pass=None)
     # ^ None: TCL_MAX_TOKENS_PER_PASS (read when the Generator is built), else min(16 M, 80 % of the device's free memory / 10.5 KB) -- a block-major pass
     #   peaks at ~10.4 KB of activations per level-0 token (90 GB for the 8.64 M tokens of 300 frames at 1280x720): a 288 GB MI355X gets the 16 M
@@ -111,6 +117,7 @@ class Generator:
         self.schedule_highres = HL.img2img_schedule(c.n_timesteps, c.highres_denoise) if self.highres else None      # the second pass's schedule
         c.iclight_model, c.bg_source = HL.check_fbc(c.iclight_model, c.bg_source, c.init_latent, c.highres_scale, bool(cfg.get("background_cond")))
         self.fbc = c.iclight_model == "fbc"
+        self.normal_sides = HL.check_normal(c.normal, c.iclight_model, c.fbc_matting, c.apply_opt)      # () unless generation.normal
         self.bg_per_frame = None           # __call__'s background_per_frame: whether the fbc background is one frame per frame (None: by its length)
         cin = getattr(self.unet, "w", {}).get("conv_in", (None, None, None))[2]      # a stand-in engine may carry no weights
         if cin is not None and cin != 4 + HL.cond_channels(c.iclight_model):
@@ -136,7 +143,12 @@ class Generator:
             alpha = self.rmbg.estimate_alpha(frames, self.batch_size)
             frames = alpha * frames + (1 - alpha) * background.to(frames)
         self.frames = frames.contiguous()
-        n, _, H, W = frames.shape
+        self.prepare_start(frames.shape[0], *frames.shape[-2:])
+
+    def prepare_start(self, n, H, W):
+        """The start of one denoise of n local frames at (H, W): the device generator seeded afresh, then init_noise (or start_noise for an
+        img2img start, or the saved latents of latents_path).  Generator.normals calls it once per direction, so all four start alike."""
+        c = self.cfg
         self.h, self.w = H // 8, W // 8
         self.n_total = getattr(self, "n_total", None) or n * self.dist.world
         self.rng_dev = torch.Generator(device=self.dev).manual_seed(int(c.seed))
@@ -169,11 +181,15 @@ class Generator:
         self.L.tcl_bg_ramp_f32(img, H, W, side, start, stop, stream())
         return img
 
-    def matte_grey(self, frames, alpha):
-        """The background demo's run_rmbg composite: frames [n,3,H,W] f32, alpha [n,1,H,W] f32 -> trunc(clamp(127 + (255 f - 127) a))/254."""
+    def matte_grey(self, frames, alpha, sigma=None):
+        """The background demo's run_rmbg composite: frames [n,3,H,W] f32, alpha [n,1,H,W] f32 -> trunc(clamp(127 + (255 f - 127) a))/254.
+        sigma (process_normal's run_rmbg(img, sigma=16)): 127 + ((255 f - 127) + sigma) a."""
         n, _, H, W = frames.shape
         out = torch.empty(n, 3, H, W, dtype=torch.float32, device=self.dev)
-        self.L.tcl_matte_grey_f32(frames.float().contiguous(), alpha.float().contiguous(), out, n, H, W, stream())
+        if sigma is None:
+            self.L.tcl_matte_grey_f32(frames.float().contiguous(), alpha.float().contiguous(), out, n, H, W, stream())
+        else:
+            self.L.tcl_matte_grey_sigma_f32(frames.float().contiguous(), alpha.float().contiguous(), out, n, H, W, float(sigma), stream())
         return out
 
     def prepare_fbc(self, frames, background):
@@ -195,6 +211,77 @@ class Generator:
                                  f"expected {(1, 3, H, W)} or {(n, 3, H, W)}")
             bg = background.to(frames).float()
             self.bg_frames = (torch.flip(bg, dims=[-1]) if c.bg_source == "upload_flip" else bg).contiguous()
+
+    # ------------------------------------------------------------------ normals (gradio_demo_bg_iclight.py: process_normal)
+    def fbc_normal(self, left, right, bottom, top, alpha=None):
+        """Four decoded relights [n,3,H,W] f32 and the matting alpha [n,1,H,W] f32 (None: 1 everywhere) -> (normal_u8 [n,H,W,3] u8 with
+        RGB = (u, v, h), ambient [n,3,H,W] f32): one tcl_fbc_normal launch."""
+        n, _, H, W = left.shape
+        srcs = [t.float().contiguous() for t in (left, right, bottom, top)]
+        if any(tuple(t.shape) != (n, 3, H, W) for t in srcs) or (alpha is not None and tuple(alpha.shape) != (n, 1, H, W)):
+            raise ValueError(f"fbc_normal: relights {[tuple(t.shape) for t in srcs]}, alpha {None if alpha is None else tuple(alpha.shape)}; "
+                             f"expected four of {(n, 3, H, W)} and {(n, 1, H, W)}")
+        a = 0 if alpha is None else alpha.float().contiguous()
+        normal = torch.empty(n, H, W, 3, dtype=torch.uint8, device=self.dev)
+        ambient = torch.empty(n, 3, H, W, dtype=torch.float32, device=self.dev)
+        self.L.tcl_fbc_normal(*srcs, a, normal, 0, ambient, n, H, W, stream())
+        return normal, ambient
+
+    @torch.no_grad()
+    def normals(self, frames, conds, conds_t, n_total=None):
+        """generation.normal: frames = this rank's block [n_local,3,H,W] f32 in [0,1]; conds / conds_t as in __call__.
+        The matte (sigma = 16; fbc_matting false: the frames as they are, alpha = 1) and the foreground latents are made once.  Per direction of
+        HL.NORMAL_SIDES: the ramp's single frame is encoded, the start is made again exactly as prepare_data makes it and VidToMe's generator is put
+        back to where it stood at entry (the demo seeds a generator per process() call), then ddim_sample and the decode -- so each direction is, bit
+        for bit, the plain run with that bg_source.  One tcl_fbc_normal launch over the block; multi-rank results are all-gathered.
+        bg_source, stage 1 / 2 and the highres pass play no part.
+        Returns (normal_u8 [N,H,W,3] u8, ambient [N,3,H,W] f32, {side: relit frames [N,3,H,W] f32}, info)."""
+        c, d = self.cfg, self.dist
+        if not self.normal_sides:
+            raise ValueError("Generator.normals needs generation.normal: true (and generation.iclight_model fbc)")
+        self.bg_per_frame = False
+        self.n_total = n_total or frames.shape[0] * d.world
+        n, _, H, W = frames.shape
+        ev = lambda: (torch.cuda.synchronize(self.dev), time.perf_counter())[1]
+        t0 = ev()
+        alpha = None
+        if c.fbc_matting:
+            if self.rmbg is None:
+                raise RuntimeError("generation.fbc_matting needs an RMBGEngine (Generator(..., rmbg=...)); fbc_matting: false feeds the frames as they are")
+            alpha = self.rmbg.estimate_alpha(frames, self.batch_size).float().contiguous()
+            self.fg_frames = self.matte_grey(frames, alpha, sigma=HL.NORMAL_MATTE_SIGMA)
+        else:
+            self.fg_frames = frames.float().contiguous()
+        self.frames = frames.contiguous()
+        fg = self.vae.encode_imgs_batch(self.fg_frames, self.batch_size)
+        tome_rng = getattr(self.unet.tome, "rng", None)
+        tome_state = None if tome_rng is None else tome_rng.bit_generator.state
+        t1 = ev()
+        relit, denoise, encode, decode = {}, {}, t1 - t0, 0.0
+        for side in self.normal_sides:
+            ta = ev()
+            if tome_state is not None:
+                tome_rng.bit_generator.state = tome_state
+            self.bg_frames = self.bg_ramp(side, H, W)
+            bg = self.vae.encode_imgs_batch(self.bg_frames, self.batch_size)
+            self.prepare_start(n, H, W)
+            tb = ev()
+            x = self.ddim_sample(self.init_noise.clone(), conds, conds_t, (fg, bg))
+            tc = ev()
+            relit[side] = self.vae.decode_latents_batch(x, self.batch_size)
+            denoise[side], encode, decode = tc - tb, encode + (tb - ta), decode + (ev() - tc)
+        t2 = ev()
+        normal, ambient = self.fbc_normal(*(relit[s] for s in HL.NORMAL_SIDES), alpha)
+        if d.multi:
+            normal, ambient = d.gather_frames(normal, self.n_total), d.gather_frames(ambient, self.n_total)
+            relit = {s: d.gather_frames(r.contiguous(), self.n_total) for s, r in relit.items()}
+        t3 = ev()
+        self.timing = dict(encode=encode, denoise=sum(denoise.values()), decode=decode, normal=t3 - t2, total=t3 - t0)
+        info = dict(timing=self.timing, denoise_per_direction=denoise, total_time=t3 - t0, sec_per_frame=(t3 - t0) / self.n_total,
+                    total_number_of_frames=self.n_total, iclight_model=c.iclight_model, normal=True, apply_opt=False,
+                    scheduler_steps=self.schedule[0], steps_executed=self.schedule[2],
+                    max_memory_allocated=torch.cuda.max_memory_allocated(self.dev) / 1024.0 ** 2)
+        return normal, ambient, relit, info
 
     def light_gradient(self, side, H, W):
         """The demo's bg_source image (gradio_demo_iclight.py:241-256) in VAEEngine.encode's [0,1] convention: [1,3,H,W] f32 = uint8(linspace)/254."""

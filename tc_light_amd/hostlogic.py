@@ -175,6 +175,32 @@ def fbc_background_per_frame(n_background, n_frames, bg_source="upload"):
     return n_background == n_frames and n_frames > 1
 
 
+NORMAL_SIDES = ("left", "right", "bottom", "top")        # generation.normal: the four relights, in the order process_normal runs them
+NORMAL_MATTE_SIGMA = 16.0                                # process_normal's run_rmbg(input_fg, sigma=16)
+
+
+def check_normal(normal, iclight_model="fc", fbc_matting=True, apply_opt=True):
+    """generation.normal (IC-Light's "Compute Normal", the background demo's process_normal): false -> (), nothing else is looked at.  true -> the
+    bg_source ramps of the four relights in the demo's order.  It needs the background-conditioned model, so normal under iclight_model fc is a
+    ValueError naming both keys; normal and fbc_matting must be booleans.  apply_opt may be either: Generator.normals never runs stage 1 / 2
+    (exposure alignment per direction would bias the ratios), run.py says so and records apply_opt: false."""
+    if normal is None:
+        normal = False
+    if not isinstance(normal, bool):
+        raise ValueError(f"generation.normal {normal!r}: expected true or false")
+    if not normal:
+        return ()
+    model = "fc" if iclight_model is None else str(iclight_model).lower()
+    if model != "fbc":
+        raise ValueError(f"generation.normal needs generation.iclight_model fbc (got {iclight_model!r}): the normal is computed from four relights "
+                         "of the background-conditioned model")
+    if not isinstance(fbc_matting, bool):
+        raise ValueError(f"generation.normal: generation.fbc_matting {fbc_matting!r}: expected true or false")
+    if not isinstance(apply_opt, bool):
+        raise ValueError(f"generation.normal: post_opt.apply_opt {apply_opt!r}: expected true or false")
+    return NORMAL_SIDES
+
+
 TOME_MAX_SRC_TOKENS = 64 * 1024          # tcl_tome_match_f16 / _affine_f16: source tokens of one match (csrc/merge.hip)
 
 
