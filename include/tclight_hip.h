@@ -274,6 +274,22 @@ int tcl_matte_grey_f32(const float* frames, const float* alpha, float* out, int 
 int tcl_matte_grey_sigma_f32(const float* frames, const float* alpha, float* out, int n, int H, int W, float sigma, hipStream_t st);
 int tcl_fbc_normal(const float* left, const float* right, const float* bottom, const float* top, const float* alpha, void* normal_u8,
                    float* normal_f32, float* ambient, int n, int H, int W, hipStream_t st);
+/* generation.light_path: a light whose direction moves over the clip -- one ramp per frame at an arbitrary angle (csrc/light.hip).
+ * tcl_light_ramp_angle_f32: dir is a DEVICE array [N,2] f64 of (c, s) per frame, the unit vector of the frame's angle (hostlogic.light_dirs; the
+ *   angle names the side the light comes FROM: 0 left, 90 top, 180 right, 270 bottom); out [N,3,H,W] f32 = u/254 (one f32 division), the same plane
+ *   three times -- the [0,1] convention of tcl_light_gradient_f32.  Per pixel (x, y), every operation in f64 rounded on its own (no fma contraction),
+ *   IEEE division:  px = x - (W-1)/2;  py = y - (H-1)/2;  d = px*c + py*s;  R = (|c|*(W-1) + |s|*(H-1))/2;  t = (R - d)/(2R);  when R == 0 (a
+ *   single sample along the light's axis) t = ((|c| + |s|) + (c + s)) / (2(|c| + |s|)), the origin corner of a square image: np.linspace(start,
+ *   stop, 1) keeps the FIRST sample, and this is exactly 1 at 0 / 90 and 0 at 180 / 270, the level the two entries above give at n == 1;
+ *   v = lo + (hi - lo)*t;  u = trunc(clamp(v, 0, 255)).  hi is met at the corner nearest the light, lo at the opposite one.  fc passes the levels of
+ *   tcl_light_gradient_f32 (255, 0), fbc those of the bg_source ramps (224, 32).
+ *   In real arithmetic the formula at 0 / 90 / 180 / 270 is the linspace rule of the two entries above; the roundings differ (isolated pixels, at
+ *   most one level) -- so the caller (Generator.light_ramps) takes the existing entries for frames whose reduced angle is an exact multiple of 90,
+ *   and a constant path reproduces left / top / right / bottom bit for bit.
+ *   One launch for all N frames; a pixel's value is computed once and stored to the three planes, as 16 B stores when H*W % 4 == 0 and out is 16 B
+ *   aligned, element by element otherwise.  Null pointers, N, H, W <= 0, 3*N*H*W >= 2^31, a level outside [0, 255] or hi < lo return TCL_EINVAL;
+ *   non-finite dir entries are the caller's to refuse (hostlogic.check_light_path). */
+int tcl_light_ramp_angle_f32(float* out, const double* dir, int N, int H, int W, int hi, int lo, hipStream_t st);
 /* The highres pass (gradio_demo_iclight.py:301-334: highres_scale, highres_denoise; csrc/resize.hip): decoded frames -> u8 -> PIL's LANCZOS resize
  * -> the [0,1]-convention image the VAE encoder takes.
  * tcl_frames_to_u8: frames [N,3,H,W] f32 (what VAEEngine.decode returns) -> out [N,H,W,3] u8, u = trunc(clamp(fl32(255*p), 0, 255)): one f32 product

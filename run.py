@@ -4,6 +4,8 @@ plus [--light left|right|top|bottom|source] [--strength F]: IC-Light's "Lighting
 (generation.iclight_model / bg_source / fbc_matting; models.iclight_offset is then the fbc file) -- the UNet sees the foreground and a background latent,
 and [--highres_scale F] [--highres_denoise F]: IC-Light's highres pass (generation.highres_scale / highres_denoise) -- the relit frames are resized
 with PIL's LANCZOS filter to multiples of 64 and refined by a second img2img denoise; flows, masks, ids, output_gt and the result live at that size.
+[--light_sweep A0 A1] (generation.light_path: keyframes [[pos, angle_deg], ...]): an animated light -- every frame gets a ramp at its own angle (the
+side the light comes FROM: 0 left, 90 top, 180 right, 270 bottom), the img2img start under fc (with --strength), the background under fbc.
 [--normal]: IC-Light's "Compute Normal" on the fbc model (generation.normal) -- four relights under the left / right / bottom / top ramps with one seed
 become normal.npy / normal.mp4 (per-frame surface normals), relit_<side>.npy and the ambient video as output.*; no stage 1 / 2.
 data.scene_type picks the parser (generate.py:84-95): video (VideoDataParser) or sceneflow (SceneFlowDataParser: ground-truth depth, poses and
@@ -26,8 +28,8 @@ import torch
 from tc_light_amd.config_utils import Config, load_config, save_config
 from tc_light_amd.dataparser import VideoDataParser, get_frame_ids, save_loss_curve, save_video
 from tc_light_amd.generate import DEFAULTS, Generator
-from tc_light_amd.hostlogic import (check_fbc, check_highres, check_highres_tokens, check_init, check_normal, cond_channels,
-                                    fbc_background_per_frame, highres_size)
+from tc_light_amd.hostlogic import (check_fbc, check_highres, check_highres_tokens, check_init, check_light_path, check_normal, cond_channels,
+                                    fbc_background_per_frame, highres_size, light_angles)
 from tc_light_amd.model_utils import allow_random, init_iclight
 from tc_light_amd.parallel import Dist
 from tc_light_amd.text import encode_prompt_pair
@@ -91,6 +93,13 @@ def main(argv=None):
         config.generation.init_latent, config.generation.highres_scale, bool(config.generation.get("background_cond")))
     config.generation.fbc_matting = bool(config.generation.get("fbc_matting", DEFAULTS["fbc_matting"]))
     fbc = config.generation.iclight_model == "fbc"
+    # an animated light (generation.light_path; --light_sweep A0 A1): one ramp per frame, the start under fc and the background under fbc; what it
+    # does not combine with (init_latent, normal, another bg_source) is refused here by both key names
+    config.generation.light_path = check_light_path(
+        config.generation.get("light_path", DEFAULTS["light_path"]), config.generation.init_latent, config.generation.get("normal", DEFAULTS["normal"]),
+        config.generation.iclight_model, config.generation.bg_source, config.generation.init_strength,
+        config.generation.get("n_timesteps", DEFAULTS["n_timesteps"]))
+    light = config.generation.light_path is not None
     # IC-Light's "Compute Normal" (generation.normal; --normal): needs the fbc model, refused here otherwise
     config.generation.normal = config.generation.get("normal", DEFAULTS["normal"])
     normal = bool(check_normal(config.generation.normal, config.generation.iclight_model, config.generation.fbc_matting,
@@ -102,7 +111,9 @@ def main(argv=None):
             print("[INFO] generation.normal: stage 1 / 2 do not run on the four relights and no flows are estimated (exposure alignment per direction "
                   "would bias their ratios); post_opt.apply_opt is recorded as false.")
         config.post_opt.apply_opt = False
-    if fbc and not normal and config.generation.bg_source in ("upload", "upload_flip") and not config.generation.get("background_image_path"):
+    if light and fbc:
+        print("[INFO] generation.light_path: the per-frame ramps are the backgrounds; generation.background_image_path is not consulted.")
+    if fbc and not normal and not light and config.generation.bg_source in ("upload", "upload_flip") and not config.generation.get("background_image_path"):
         raise ValueError(f"generation.bg_source {config.generation.bg_source} needs generation.background_image_path")
     highres = config.generation.highres_scale != 1.0
     data_hr = None
@@ -181,7 +192,7 @@ def main(argv=None):
         background = parser.load_video(path=g.background_image_path)
         if background.shape[0] == len(frame_ids) and world > 1:     # a per-frame background video: this rank's block of it
             background = background[lo:hi]
-    elif fbc and not normal and g.bg_source in ("upload", "upload_flip"):     # the background the fbc model is conditioned on: one frame for all, or one per frame
+    elif fbc and not normal and not light and g.bg_source in ("upload", "upload_flip"):     # the background the fbc model is conditioned on: one frame for all, or one per frame
         background = parser.load_video(path=g.background_image_path)
         bg_per_frame = fbc_background_per_frame(background.shape[0], len(frame_ids), g.bg_source)      # the same answer on every rank
         if bg_per_frame and world > 1:
@@ -209,6 +220,8 @@ def main(argv=None):
             config.sec_per_frame = config.total_time / len(frame_ids)
             config.max_memory_allocated = max(config.max_memory_allocated, info["max_memory_allocated"])
             g.scheduler_steps, g.steps_executed = info["scheduler_steps"], info["steps_executed"]      # init_latent / init_strength are in g already
+            if light:                             # light_path is in g already; the angles of the first and the last frame of the run
+                g.light_angle_first, g.light_angle_last = (float(a) for a in light_angles(g.light_path, [0.0, 1.0 if len(frame_ids) > 1 else 0.0]))
             if highres:                           # total_time / sec_per_frame cover both passes
                 g.highres_size = list(info["highres_size"])
                 g.highres_scheduler_steps, g.highres_steps_executed = info["highres_scheduler_steps"], info["highres_steps_executed"]

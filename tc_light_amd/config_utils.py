@@ -95,8 +95,14 @@ def load_config(argv=None, print_config=True):
     # IC-Light's "Compute Normal" on the fbc model (generation.normal, generate.py DEFAULTS)
     ap.add_argument("--normal", action="store_true", help="fbc only: relight under the left / right / bottom / top ramps with one seed and write "
                     "per-frame normal maps and the ambient video instead of one relight, for a fast usage")
+    # an animated light (generation.light_path, generate.py DEFAULTS)
+    ap.add_argument("--light_sweep", type=float, nargs=2, metavar=("A0", "A1"), default=None,
+                    help="turn the light from angle A0 at the first frame to A1 at the last (degrees, the side it comes FROM: 0 left, 90 top, "
+                    "180 right, 270 bottom): generation.light_path [[0, A0], [1, A1]], for a fast usage")
     a = ap.parse_args(argv)
     cfg = load_yaml_chain(a.config, a.base_config)
+    if a.light_sweep is not None:
+        cfg.generation.light_path = [[0.0, float(a.light_sweep[0])], [1.0, float(a.light_sweep[1])]]
     if a.normal:
         cfg.generation.normal = True
     if a.iclight_model is not None:

@@ -3,7 +3,8 @@
 //   * the img2img start latents  x_start = alpha*x0 + sigma_t*z  of the first executed sigma (diffusers' add_noise);
 //   * for the background-conditioned model (generation.iclight_model: fbc): the background ramps of bg_source and the foreground's grey matte;
 //   * for generation.normal (the background demo's "Compute Normal", process_normal): the matte with its sigma offset and the kernel that turns the
-//     four directional relights into a surface normal and the ambient image.
+//     four directional relights into a surface normal and the ambient image;
+//   * for generation.light_path (an animated light): one ramp per frame at an arbitrary angle.
 // Both run once per relight, in front of the denoise loop; every rounding is spelled out because the tests ask for the bits numpy gives.
 #include "common.h"
 #include "../../include/tclight_hip.h"
@@ -45,6 +46,67 @@ __global__ __launch_bounds__(256) void k_light_gradient(float* __restrict__ out,
             *(float4*)(out + e0) = make_float4(v[0], v[1], v[2], v[3]);
         } else {
             for (int j = 0; j < 4 && e0 + j < total; ++j) out[e0 + j] = v[j];
+        }
+    }
+}
+
+// generation.light_path: the ramp of one frame at an arbitrary angle.  (c, s) is the frame's unit vector, R the half extent of the image along it;
+// every operation in f64 and rounded on its own, the division IEEE: d = px*c + py*s; t = (R - d)/(2R), t0 when R == 0; v = lo + (hi - lo)*t;
+// u = trunc(clamp(v, 0, 255)); out = u/254 as light_sample stores it.
+// R == 0: the image has a single sample along the light's axis.  np.linspace(start, stop, 1) keeps the FIRST sample, so the pixel counts as the
+// origin corner of a square image, whose t is t0 = ((|c| + |s|) + (c + s)) / (2(|c| + |s|)): exactly 1 at 0 / 90, 0 at 180 / 270 -- the level
+// tcl_light_gradient_f32 / tcl_bg_ramp_f32 give at n == 1 -- and continuous in the angle between them.
+__device__ __forceinline__ float ramp_angle_sample(double px, double py, double c, double s, double R, double t0, double hi, double lo) {
+#pragma clang fp contract(off)
+    const double a = px * c, b = py * s;
+    const double d = a + b;
+    double t = t0;
+    if (R != 0.0) {
+        const double num = R - d, den = 2.0 * R;
+        t = num / den;
+    }
+    const double w = (hi - lo) * t;
+    const double v = lo + w;
+    const int u = (int)trunc(fmin(fmax(v, 0.0), 255.0));       // NaN -> 0
+    return (float)u / 254.f;
+}
+
+// out [N,3,hw] f32, dir [N,2] f64.  HBM-write-bound (12 B per pixel out, nothing in but the frame's pair).  VEC: hw % 4 == 0 and out 16 B aligned -> a
+// lane owns 4 consecutive pixels of one frame, computes each once and stores one float4 to each of the three planes.  Otherwise one pixel per lane.
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_light_ramp_angle(float* __restrict__ out, const double* __restrict__ dir, long N, int H, int W, double hi,
+                                                          double lo) {
+#pragma clang fp contract(off)
+    constexpr int V = VEC ? 4 : 1;
+    const long hw = (long)H * W, per = hw / V, total = N * per;
+    const double cx = (double)(W - 1) / 2.0, cy = (double)(H - 1) / 2.0;
+    for (long g = (long)blockIdx.x * blockDim.x + threadIdx.x; g < total; g += (long)gridDim.x * blockDim.x) {
+        const long f = g / per;
+        const int p = (int)(g - f * per) * V;
+        const double c = dir[2 * f], s = dir[2 * f + 1];
+        const double ex = fabs(c) * (double)(W - 1), ey = fabs(s) * (double)(H - 1);
+        const double R = (ex + ey) / 2.0;
+        double t0 = 0.5;
+        if (R == 0.0) {
+            const double A = fabs(c) + fabs(s), cs = c + s;
+            const double num = A + cs, den = 2.0 * A;
+            t0 = num / den;
+        }
+        int y = p / W, x = p - y * W;
+        float v[V];
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            v[j] = ramp_angle_sample((double)x - cx, (double)y - cy, c, s, R, t0, hi, lo);
+            if (++x == W) { x = 0; ++y; }
+        }
+        float* po = out + f * 3 * hw + p;
+        if constexpr (VEC) {
+            const float4 q = make_float4(v[0], v[1], v[2], v[3]);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) *(float4*)(po + k * hw) = q;
+        } else {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) po[k * hw] = v[0];
         }
     }
 }
@@ -266,6 +328,20 @@ int tcl_bg_ramp_f32(float* out, int H, int W, int side, int start, int stop, hip
     TCL_CHECK_ARG(start >= 0 && start <= 255 && stop >= 0 && stop <= 255 && 3L * H * W + 3 < (1L << 31));
     const long groups = (3L * H * W + 3) / 4;
     hipLaunchKernelGGL(k_light_gradient, dim3(stream_grid(groups, 256, 1)), dim3(256), 0, st, out, H, W, side, (double)start, (double)stop);
+    TCL_LAUNCH_RET();
+}
+
+int tcl_light_ramp_angle_f32(float* out, const double* dir, int N, int H, int W, int hi, int lo, hipStream_t st) {
+    TCL_CHECK_ARG(out && dir && N > 0 && H > 0 && W > 0);
+    TCL_CHECK_ARG(3L * N * H * W < (1L << 31));
+    TCL_CHECK_ARG(hi >= 0 && hi <= 255 && lo >= 0 && lo <= 255 && hi >= lo);
+    const long hw = (long)H * W;
+    if (hw % 4 == 0 && ((uintptr_t)out & 15) == 0)
+        hipLaunchKernelGGL(k_light_ramp_angle<true>, dim3(stream_grid(N * (hw / 4), 256, 1)), dim3(256), 0, st, out, dir, (long)N, H, W, (double)hi,
+                           (double)lo);
+    else
+        hipLaunchKernelGGL(k_light_ramp_angle<false>, dim3(stream_grid(N * hw, 256, 1)), dim3(256), 0, st, out, dir, (long)N, H, W, (double)hi,
+                           (double)lo);
     TCL_LAUNCH_RET();
 }
 

@@ -10,6 +10,9 @@ run on the frames the user gets.
 generation.normal (fbc only; the background demo's process_normal): Generator.normals runs the matte and the foreground encode once, ddim_sample and the
 decode once per ramp (left, right, bottom, top) from the same start, and one tcl_fbc_normal launch over the four results; no stage 1 / 2.
 
+generation.light_path (an animated light; in neither the reference nor the demos): light_ramps renders one ramp per distinct angle of the rank's frames;
+build_start (fc) makes them the per-frame img2img start, prepare_fbc (fbc) the per-frame backgrounds; distinct ramps are encoded once and gathered.
+
 Python sequences kernel launches and collectives; tensors never leave the device inside the timed region and there is no
 per-iteration host sync (the reference syncs on loss.item() and moves the token bank through the CPU).
 """
@@ -65,6 +68,11 @@ DEFAULTS = dict(  # configs/tclight_default.yaml (generation / post_opt sections
     #   in as `background`, as they are or mirrored) | left | right | top | bottom | grey (a ramp or a flat grey built on the device, HL.BG_RAMPS).
     #   fbc_matting: the foreground is matted onto 127-grey with BriaRMBG's alpha before it is encoded (the background demo's run_rmbg); false feeds
     #   the frames as they are and needs no RMBGEngine.  "fc" (default): none of this is consulted and every path is bit for bit what it was.
+    light_path=None,
+    # ^ an animated light: keyframes [[pos, angle_deg], ...] over the clip (pos 0 .. 1, frame i of N at i/(N - 1); the angle is the side the light comes
+    #   FROM: 0 left, 90 top, 180 right, 270 bottom; linear in the angle, several turns allowed).  Every frame gets its own ramp (light_ramps): under fc
+    #   it is the img2img start of that frame, with init_strength exactly as init_latent uses it (init_latent itself stays none); under fbc it is that
+    #   frame's background (bg_source stays at its default).  None (default): nothing of it is consulted and every path is what it was.
     normal=False,
     # ^ IC-Light's "Compute Normal" (the background demo's process_normal), fbc only: Generator.normals relights the frames under the left / right /
     #   bottom / top ramps from one seed and turns the four results into per-frame surface normals and the ambient image (tcl_fbc_normal).
@@ -109,7 +117,9 @@ class Generator:
         t.args.update(local_merge_ratio=c.local_merge_ratio, merge_global=c.merge_global, global_merge_ratio=c.global_merge_ratio,
                       global_rand=c.global_rand, align_batch=bool(c.align_batch))
         c.init_latent, c.init_strength = HL.check_init(c.init_latent, c.init_strength, c.n_timesteps)
-        self.img2img = c.init_latent != "none"
+        c.light_path = HL.check_light_path(c.light_path, c.init_latent, c.normal, c.iclight_model, c.bg_source, c.init_strength, c.n_timesteps)
+        self.light = c.light_path is not None
+        self.img2img = c.init_latent != "none" or (self.light and str(c.iclight_model).lower() != "fbc")      # fc: the path's ramps are the start
         # (scheduler steps, begin index, steps executed): the whole n_timesteps schedule unless the start is an img2img one
         self.schedule = HL.img2img_schedule(c.n_timesteps, c.init_strength) if self.img2img else (c.n_timesteps, 0, c.n_timesteps)
         c.highres_scale, c.highres_denoise = HL.check_highres(c.highres_scale, c.highres_denoise, c.n_timesteps)
@@ -155,7 +165,8 @@ class Generator:
         self.start_noise = None
         if self.img2img:
             if c.latents_path is not None:
-                print(f"[INFO] init_latent '{c.init_latent}': the start is built from it, generation.latents_path is not consulted.")
+                what = f"light_path {c.light_path}" if self.light else f"init_latent '{c.init_latent}'"
+                print(f"[INFO] {what}: the start is built from it, generation.latents_path is not consulted.")
         elif c.latents_path is not None and self._load_start_latents(n):
             return
         if c.noise_mode.lower() == "same":        # prepare_latents(1, 4, H, W) repeated (generate.py:183-188)
@@ -203,7 +214,12 @@ class Generator:
             self.fg_frames = self.matte_grey(frames, self.rmbg.estimate_alpha(frames, self.batch_size))
         else:
             self.fg_frames = frames.float().contiguous()
-        if c.bg_source in HL.BG_RAMPS:
+        self.bg_index = None               # light_path only: the image of bg_frames that is each frame's background (None: bg_frames as they are)
+        if self.light:                     # bg_frames = the DISTINCT ramps of this rank's frames; __call__ encodes those and gathers the latents
+            self.bg_frames, index, self.bg_per_frame = self.light_images(n, H, W)
+            if self.bg_per_frame:
+                self.bg_index = torch.tensor(index, dtype=torch.long, device=self.dev)
+        elif c.bg_source in HL.BG_RAMPS:
             self.bg_frames = self.bg_ramp(c.bg_source, H, W)
         else:
             if background is None or background.dim() != 4 or background.shape[0] not in (1, n) or tuple(background.shape[1:]) != (3, H, W):
@@ -289,10 +305,58 @@ class Generator:
         self.L.tcl_light_gradient_f32(img, H, W, HL.INIT_LATENTS.index(side) - 1, stream())
         return img
 
+    def light_ramps(self, angles, H, W, hi, lo):
+        """generation.light_path: the ramps of frames at `angles` (degrees).  Frames are grouped by bitwise-equal reduced angle and every distinct
+        angle is rendered once, in [0,1] convention [1,3,H,W] f32 = u/254: an exact multiple of 90 takes the image of the existing kernels
+        (tcl_light_gradient_f32 at the levels (255, 0), tcl_bg_ramp_f32 otherwise), so a constant path at 0 / 90 / 180 / 270 is the left / top / right /
+        bottom run bit for bit; all the others leave in one tcl_light_ramp_angle_f32 launch.
+        Returns (images [D,3,H,W] f32 in order of first appearance, [index into them per frame])."""
+        reduced = [HL.light_reduce(a) for a in angles]
+        distinct, index = [], []
+        for r in reduced:                  # floats of [0, 360) without -0.0: equal values are equal bits
+            if r not in distinct:
+                distinct.append(r)
+            index.append(distinct.index(r))
+        general = [r for r in distinct if HL.light_axis_side(r) is None]
+        swept = None
+        if general:
+            swept = torch.empty(len(general), 3, H, W, dtype=torch.float32, device=self.dev)
+            dirs = torch.tensor(HL.light_dirs(general), dtype=torch.float64).to(self.dev)
+            self.L.tcl_light_ramp_angle_f32(swept, dirs, len(general), H, W, int(hi), int(lo), stream())
+            if len(general) == len(distinct):
+                return swept, index
+        images = []
+        for r in distinct:
+            side = HL.light_axis_side(r)
+            if side is None:
+                images.append(swept[general.index(r)][None])
+            elif (hi, lo) == HL.LIGHT_LEVELS["fc"]:
+                images.append(self.light_gradient(side, H, W))
+            else:
+                img = torch.empty(1, 3, H, W, dtype=torch.float32, device=self.dev)
+                start, stop = (hi, lo) if side in ("left", "top") else (lo, hi)
+                self.L.tcl_bg_ramp_f32(img, H, W, HL.INIT_LATENTS.index(side) - 1, int(start), int(stop), stream())
+                images.append(img)
+        return (images[0] if len(images) == 1 else torch.cat(images)), index
+
+    def light_images(self, n, H, W):
+        """The ramps of this rank's n frames under generation.light_path, from the frames' GLOBAL positions (a rank of a sharded run builds what one
+        rank would): (distinct images [D,3,H,W], [index per local frame], whether the run as a whole has more than one distinct ramp -- the same
+        answer on every rank, as the per-frame background of fbc needs it)."""
+        c = self.cfg
+        n_total = getattr(self, "n_total", None) or n * self.dist.world
+        lo, hi = self.dist.range(n_total)
+        assert hi - lo == n
+        angles = HL.light_angles(c.light_path, HL.light_positions(n_total))
+        self.light_angles = angles[lo:hi]
+        several = len({HL.light_reduce(a) for a in angles}) > 1
+        images, index = self.light_ramps(self.light_angles, H, W, *HL.LIGHT_LEVELS[c.iclight_model])
+        return images, index, several
+
     def build_start(self, concat_conds):
         """img2img start (gradio_demo_iclight.py:283-299 -> the img2img pipeline's add_noise): init_noise = alpha*x0 + sigma_t*z at the first executed
         sigma, with z the f32 draw of prepare_data and x0 the light gradient's latent (encoded once, shared by all frames) or, for `source`,
-        the frames' own clean latents `concat_conds` [n_local,4,h,w] f16."""
+        the frames' own clean latents `concat_conds` [n_local,4,h,w] f16, or, under light_path, the latent of each frame's own ramp."""
         c, sch = self.cfg, self.scheduler
         n_sched, begin, _ = self.schedule
         sch.set_timesteps(n_sched, begin)
@@ -302,6 +366,11 @@ class Generator:
             x0, x0_stride = concat_conds.contiguous(), chw
             if tuple(x0.shape) != (n, 4, self.h, self.w) or x0.dtype != H16:
                 raise ValueError(f"init_latent 'source': clean latents {tuple(x0.shape)} {x0.dtype}, expected {(n, 4, self.h, self.w)} f16")
+        elif self.light:                   # the distinct ramps are encoded, in batches of batch_size, and gathered to the frames; one ramp serves all
+            images, index, _ = self.light_images(n, *self.frames.shape[-2:])
+            x0, x0_stride = self.vae.encode_imgs_batch(images, self.batch_size).contiguous(), 0
+            if x0.shape[0] > 1:
+                x0, x0_stride = x0[torch.tensor(index, dtype=torch.long, device=self.dev)].contiguous(), chw
         else:
             x0, x0_stride = self.vae.encode(self.light_gradient(c.init_latent, *self.frames.shape[-2:])).contiguous(), 0
         same = c.noise_mode.lower() == "same"
@@ -573,6 +642,8 @@ class Generator:
         self.prepare_data(frames, background)
         if self.fbc:                       # (foreground, background) latents: model_utils.py:97-179 concat_conds, kept apart (one background frame stays one)
             concat_conds = (self.vae.encode_imgs_batch(self.fg_frames, self.batch_size), self.vae.encode_imgs_batch(self.bg_frames, self.batch_size))
+            if self.bg_index is not None:      # light_path: bg_frames are the distinct ramps; their latents are gathered to one per frame
+                concat_conds = (concat_conds[0], concat_conds[1][self.bg_index].contiguous())
         else:
             concat_conds = self.vae.encode_imgs_batch(self.frames, self.batch_size)
         if self.img2img:

@@ -201,7 +201,97 @@ def check_normal(normal, iclight_model="fc", fbc_matting=True, apply_opt=True):
     return NORMAL_SIDES
 
 
-TOME_MAX_SRC_TOKENS = 64 * 1024          # tcl_tome_match_f16 / _affine_f16: source tokens of one match (csrc/merge.hip)
+LIGHT_AXIS_SIDES = ("left", "top", "right", "bottom")     # reduced angle 0 / 90 / 180 / 270: the side the light comes FROM
+LIGHT_AXIS_DIRS = ((1.0, 0.0), (0.0, 1.0), (-1.0, 0.0), (0.0, -1.0))
+# iclight_model -> (hi, lo) levels of the animated ramps: those of tcl_light_gradient_f32 (fc) and of the bg_source ramps (fbc, BG_RAMPS)
+LIGHT_LEVELS = {"fc": (255, 0), "fbc": (224, 32)}
+
+
+def _is_number(v):
+    return not isinstance(v, bool) and isinstance(v, (int, float))
+
+
+def check_light_path(path, init_latent="none", normal=False, iclight_model="fc", bg_source=None, init_strength=None, n_timesteps=None):
+    """generation.light_path: None (off: nothing else is looked at) or keyframes [[pos, angle_deg], ...] -> [[float, float], ...]; anything else is a
+    ValueError (run.py and Generator raise it before a model is loaded).  pos in [0, 1], non-decreasing, the first 0 and the last 1 -- a single
+    keyframe [[0, a]] is a constant direction; angle_deg any finite number, the side the light comes FROM (0 left, 90 top, 180 right, 270 bottom),
+    beyond 360 allowed (several turns).  Refused by both key names: init_latent other than none (the path is the start), normal (the four ramps are
+    the lights), and under fbc a bg_source other than the default upload (the per-frame ramps are the backgrounds).  Under fc the start is an img2img
+    one, so with init_strength and n_timesteps a schedule that would execute no step is refused as check_init refuses it."""
+    if path is None:
+        return None
+    if not isinstance(path, (list, tuple)) or len(path) == 0:
+        raise ValueError(f"generation.light_path {path!r}: expected null or a list of keyframes [[pos, angle_deg], ...] with at least one")
+    keys = []
+    for kf in path:
+        if not isinstance(kf, (list, tuple)) or len(kf) != 2 or not all(_is_number(v) and math.isfinite(v) for v in kf):
+            raise ValueError(f"generation.light_path keyframe {kf!r}: expected [pos, angle_deg], two finite numbers")
+        keys.append([float(kf[0]), float(kf[1])])
+    pos = [k[0] for k in keys]
+    if pos[0] != 0.0 or (len(keys) > 1 and pos[-1] != 1.0) or any(b < a for a, b in zip(pos, pos[1:])) or not all(0.0 <= p <= 1.0 for p in pos):
+        raise ValueError(f"generation.light_path positions {pos}: expected non-decreasing values in [0, 1], the first 0 and (with more than one "
+                         "keyframe) the last 1")
+    if init_latent is not None and str(init_latent).lower() != "none":
+        raise ValueError(f"generation.light_path together with generation.init_latent {init_latent!r} is not supported: the path is the start")
+    if normal:
+        raise ValueError("generation.light_path together with generation.normal is not supported: the normal is computed from the four fixed ramps")
+    model = "fc" if iclight_model is None else str(iclight_model).lower()
+    if model == "fbc" and bg_source is not None and str(bg_source).lower() != "upload":
+        raise ValueError(f"generation.light_path together with generation.bg_source {bg_source!r} is not supported under iclight_model fbc: the "
+                         "per-frame ramps are the backgrounds, leave bg_source at its default")
+    if model != "fbc" and init_strength is not None and n_timesteps is not None and img2img_schedule(n_timesteps, init_strength)[2] < 1:
+        raise ValueError(f"generation.light_path: generation.init_strength {init_strength} with n_timesteps {n_timesteps} leaves no step to execute")
+    return keys
+
+
+def light_positions(n_total, lo=0, hi=None):
+    """pos = i/(N - 1) of the run's frames lo <= i < hi (GLOBAL indices: a rank of a sharded run builds what one rank would); N == 1 -> 0."""
+    hi = n_total if hi is None else hi
+    return [i / (n_total - 1) if n_total > 1 else 0.0 for i in range(lo, hi)]
+
+
+def light_angles(path, positions):
+    """The angle (degrees, f64) at every position: linear between the two keyframes around it, no shortest-arc logic; of keyframes that share a
+    position the later one holds from there on.  A single keyframe is a constant."""
+    out = []
+    for p in positions:
+        k = 0
+        while k + 1 < len(path) and path[k + 1][0] <= p:
+            k += 1
+        if k + 1 == len(path):
+            out.append(path[k][1])
+            continue
+        (p0, a0), (p1, a1) = path[k], path[k + 1]
+        out.append(a0 + (a1 - a0) * ((p - p0) / (p1 - p0)))
+    return out
+
+
+def light_reduce(angle):
+    """math.fmod(angle, 360), plus 360 when that is negative -> [0, 360).  (A negative angle so small that the sum rounds to 360, and -0.0, are 0.)"""
+    r = math.fmod(angle, 360.0)
+    if r < 0.0:
+        r += 360.0
+    return 0.0 if r >= 360.0 or r == 0.0 else r
+
+
+def light_axis_side(reduced):
+    """left | top | right | bottom when the reduced angle is exactly 0 / 90 / 180 / 270 (those frames take the existing ramp kernels), else None."""
+    q = reduced / 90.0
+    return LIGHT_AXIS_SIDES[int(q)] if q == int(q) and q * 90.0 == reduced else None
+
+
+def light_dirs(angles):
+    """(c, s) f64 per angle, the unit vector pointing AWAY from the light's side: exact multiples of 90 give exactly (1,0) (0,1) (-1,0) (0,-1),
+    anything else (cos, sin) of math.radians of the reduced angle."""
+    out = []
+    for a in angles:
+        r = light_reduce(a)
+        side = light_axis_side(r)
+        out.append(LIGHT_AXIS_DIRS[LIGHT_AXIS_SIDES.index(side)] if side is not None else (math.cos(math.radians(r)), math.sin(math.radians(r))))
+    return out
+
+
+TOME_MAX_SRC_TOKENS = 64 * 1024         # tcl_tome_match_f16 / _affine_f16: source tokens of one match (csrc/merge.hip)
 
 
 def check_highres_tokens(H2, W2, chunk_size):
