@@ -344,6 +344,24 @@ int tcl_attention_plan(int B, int H, int Tq, int Tk, int d, int kv_div, int flag
 /* The packing half of tcl_attention_f16 alone: Q panel (scaled) into ws_q and, with TCL_ATTN_PACK_KV, the K / V^T panels into ws_kv. */
 int tcl_attention_pack_f16(const void* q, int ldq, long qbs, const void* k, int ldk, long kbs, const void* v, int ldv, long vbs, int B, int H, int Tq,
                            int Tk, int d, float scale, int kv_div, int pack_kv, void* ws_q, void* ws_kv, hipStream_t st);
+/* tcl_attention_f16 with a K / V entry PER SAMPLE (generation.prompt_path: the text cross-attention where every frame has its own text, and the chunks
+ * of a pass draw frames in no order a `b / kv_div` could express).  kv_index: DEVICE int32 [B], sample b attends to entry kv_index[b] of the kv_rows
+ * entries in ws_kv (tcl_attention_kv_bytes(kv_rows, H, Tk, d); with TCL_ATTN_PACK_KV they are packed from k / v [kv_rows, Tk, ...] by this call);
+ * h_kv_index: a HOST copy of the same table, checked here -- an entry outside [0, kv_rows) returns TCL_EINVAL and nothing is launched (the device
+ * never checks).  kv_div is not consulted then; d in {40, 80, 160}.  The kernels are those of tcl_attention_f16, chosen by the same rule, with the
+ * entry read by a per-block scalar load: a sample's arithmetic is what it is when its entry is handed over through kv_div, bit for bit.
+ * kv_index == NULL: the call IS tcl_attention_f16 (same kernels, `b / kv_div`), h_kv_index and kv_rows are not looked at. */
+int tcl_attention_kvindex_f16(const void* q, int ldq, long qbs, const void* k, int ldk, long kbs, const void* v, int ldv, long vbs, void* o, int ldo,
+                              long obs, int B, int H, int Tq, int Tk, int d, float scale, int kv_div, int pack_kv, void* ws_q, void* ws_kv,
+                              const int* kv_index, const int* h_kv_index, int kv_rows, hipStream_t st);
+/* generation.prompt_path: the text conditioning of F frames between keyframe prompts, one launch (csrc/text_lerp.hip).  keys [n_keys, LD] f16: the
+ * keyframes' CLIP last_hidden_state (LD = L * D elements each); out [F, LD] f16.  tab: DEVICE int32 [F, 3] = (k0, k1, the bits of t as f32) per frame,
+ * h_tab a HOST copy of it, checked here: k0, k1 outside [0, n_keys) or t outside [0, 1] (NaN included) return TCL_EINVAL and nothing is launched.
+ * Per element, with a = keys[k0][i], b = keys[k1][i], every operation rounded to f32 on its own (no fma contraction), one rounding to f16:
+ *   a32 = f32(a);  b32 = f32(b);  e = b32 - a32;  m = t * e;  s = a32 + m;  out[f][i] = f16(s).
+ * t == 0 copies the f16 bits of keys[k0], t == 1 those of keys[k1] (the formula would turn -0 into +0, and a + 1 (b - a) need not be b).
+ * t is computed by the caller in f64 and rounded to f32 once.  16 B accesses when LD % 8 == 0 and out / keys are 16 B aligned.  F <= 65535. */
+int tcl_text_lerp_f16(void* out, const void* keys, int n_keys, const int* tab, const int* h_tab, int F, long LD, hipStream_t st);
 
 /* ---- VidToMe token merging (utils/VidToMe/vidtome/merge.py, patch.py:14-91); int32 maps live on the device ---- */
 /* metric / metric.norm(dim=-1) with f16 rounding of the norm and the quotient (merge.py:84, :386). */

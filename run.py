@@ -8,6 +8,8 @@ with PIL's LANCZOS filter to multiples of 64 and refined by a second img2img den
 side the light comes FROM: 0 left, 90 top, 180 right, 270 bottom), the img2img start under fc (with --strength), the background under fbc.
 [--normal]: IC-Light's "Compute Normal" on the fbc model (generation.normal) -- four relights under the left / right / bottom / top ramps with one seed
 become normal.npy / normal.mp4 (per-frame surface normals), relit_<side>.npy and the ambient video as output.*; no stage 1 / 2.
+[--prompt_sweep PROMPT_A PROMPT_B] (generation.prompt_path: keyframes [[pos, "prompt"], ...]): a prompt that changes over the clip -- every frame's text
+conditioning of the xy passes is the blend of its two neighbouring keyframes' embeddings; -p / generation.prompt still names the run.
 data.scene_type picks the parser (generate.py:84-95): video (VideoDataParser) or sceneflow (SceneFlowDataParser: ground-truth depth, poses and
 flows -> voxelised Unique Video Tensor ids); carla and interiornet are not built.
 
@@ -28,11 +30,11 @@ import torch
 from tc_light_amd.config_utils import Config, load_config, save_config
 from tc_light_amd.dataparser import VideoDataParser, get_frame_ids, save_loss_curve, save_video
 from tc_light_amd.generate import DEFAULTS, Generator
-from tc_light_amd.hostlogic import (check_fbc, check_highres, check_highres_tokens, check_init, check_light_path, check_normal, cond_channels,
-                                    fbc_background_per_frame, highres_size, light_angles)
+from tc_light_amd.hostlogic import (check_fbc, check_highres, check_highres_tokens, check_init, check_light_path, check_normal, check_prompt_path,
+                                    cond_channels, fbc_background_per_frame, highres_size, light_angles, prompt_table)
 from tc_light_amd.model_utils import allow_random, init_iclight
 from tc_light_amd.parallel import Dist
-from tc_light_amd.text import encode_prompt_pair
+from tc_light_amd.text import encode_prompt_pair, encode_prompt_set
 
 
 def seed_everything(seed):
@@ -111,6 +113,13 @@ def main(argv=None):
             print("[INFO] generation.normal: stage 1 / 2 do not run on the four relights and no flows are estimated (exposure alignment per direction "
                   "would bias their ratios); post_opt.apply_opt is recorded as false.")
         config.post_opt.apply_opt = False
+    # a prompt that changes over the clip (generation.prompt_path; --prompt_sweep A B): malformed lists and what it does not combine with (normal, the
+    # highres pass) are refused here by both key names
+    config.generation.prompt_path = check_prompt_path(config.generation.get("prompt_path", DEFAULTS["prompt_path"]), config.generation.normal,
+                                                      config.generation.highres_scale)
+    if config.generation.prompt_path is not None:
+        print("[INFO] generation.prompt_path: the xy passes are conditioned on the keyframe prompts, blended per frame; generation.prompt names the "
+              "run and is recorded in config.yaml, it conditions nothing.  negative_prompt, prompt_t and negative_prompt_t are used as they are.")
     if light and fbc:
         print("[INFO] generation.light_path: the per-frame ramps are the backgrounds; generation.background_image_path is not consulted.")
     if fbc and not normal and not light and config.generation.bg_source in ("upload", "upload_flip") and not config.generation.get("background_image_path"):
@@ -199,7 +208,12 @@ def main(argv=None):
             background = background[lo:hi]
     gen = Generator(pipe.unet, pipe.vae, cfg, dist=d, scheduler=scheduler, rmbg=rmbg)
     for name, prompt in g.prompt.items():
-        conds = encode_prompt_pair(prompt, g.negative_prompt, dev, models.get("text_encoder"), allow_random=ok_random, lora=lora)
+        if g.prompt_path is not None:      # every distinct keyframe prompt is encoded once; the rows of this rank's frames are blended from them
+            uncond, keys = encode_prompt_set(prompt_table(g.prompt_path, len(frame_ids))[0], g.negative_prompt, dev, models.get("text_encoder"),
+                                             allow_random=ok_random, lora=lora)
+            conds = gen.frame_text(uncond, keys, hi - lo, n_total=len(frame_ids))
+        else:
+            conds = encode_prompt_pair(prompt, g.negative_prompt, dev, models.get("text_encoder"), allow_random=ok_random, lora=lora)
         conds_t = encode_prompt_pair(g.prompt_t, g.negative_prompt_t, dev, models.get("text_encoder"), allow_random=ok_random, lora=lora)
         if normal:
             nrm, ambient, relit, info = gen.normals(frames_all[lo:hi], conds, conds_t, n_total=len(frame_ids))

@@ -99,8 +99,14 @@ def load_config(argv=None, print_config=True):
     ap.add_argument("--light_sweep", type=float, nargs=2, metavar=("A0", "A1"), default=None,
                     help="turn the light from angle A0 at the first frame to A1 at the last (degrees, the side it comes FROM: 0 left, 90 top, "
                     "180 right, 270 bottom): generation.light_path [[0, A0], [1, A1]], for a fast usage")
+    # a prompt that changes over the clip (generation.prompt_path, generate.py DEFAULTS)
+    ap.add_argument("--prompt_sweep", type=str, nargs=2, metavar=("PROMPT_A", "PROMPT_B"), default=None,
+                    help="blend the text conditioning from PROMPT_A at the first frame to PROMPT_B at the last: generation.prompt_path "
+                    "[[0, PROMPT_A], [1, PROMPT_B]]; -p / generation.prompt still names the run, for a fast usage")
     a = ap.parse_args(argv)
     cfg = load_yaml_chain(a.config, a.base_config)
+    if a.prompt_sweep is not None:
+        cfg.generation.prompt_path = [[0.0, a.prompt_sweep[0]], [1.0, a.prompt_sweep[1]]]
     if a.light_sweep is not None:
         cfg.generation.light_path = [[0.0, float(a.light_sweep[0])], [1.0, float(a.light_sweep[1])]]
     if a.normal:

@@ -121,10 +121,13 @@ __device__ __forceinline__ float xhalf_max(float v) {
 
 // (the body of k_flash for ONE block index: the kernel below calls it once, or -- the flag-gated exact pass behind the speculative kernel -- once per
 // flagged index of its stride class)
-template <int D, int DP, int DPV, int QB, int NSTG, int TPB, int MINB, int SPEC, bool SPLIT = false>
+// KVI: the K / V panel of sample b is kv_index[b] (a per-block scalar load: b is uniform over the block) instead of b / kv_div -- the per-frame text of
+// generation.prompt_path.  Instantiated beside the kernels without it, whose code is what it was.
+template <int D, int DP, int DPV, int QB, int NSTG, int TPB, int MINB, int SPEC, bool SPLIT = false, bool KVI = false>
 __device__ __forceinline__ void flash_block(const int bid, const _Float16* __restrict__ Qp, const _Float16* __restrict__ Kp, const _Float16* __restrict__ Vt,
                                             _Float16* __restrict__ O, int H, int Tq, int Tk, int Tqp, int Tkp, int d, int ldo, long obstride,
-                                            int kv_div, int nqb, int* __restrict__ flags, float* __restrict__ lse = nullptr) {
+                                            int kv_div, int nqb, int* __restrict__ flags, float* __restrict__ lse = nullptr,
+                                            const int* __restrict__ kv_index = nullptr) {
     constexpr int KS = DP + 8;                    // K row stride (halves); KS/8 odd -> conflict-free b128 reads
     constexpr int NQK = DP / 16, NDT = DPV / 32;
     constexpr int KBYTES = KV_TILE * KS * 2, VBYTES = vt_tile_halves(DPV) * 2, SBYTES = KBYTES + VBYTES;
@@ -147,7 +150,7 @@ __device__ __forceinline__ void flash_block(const int bid, const _Float16* __res
     const int head = bid % H, qb_ = (bid / H) % nqb, b = bid / (H * nqb);
     const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6), hl = lane >> 5, ql = lane & 31;
     const int q0 = qb_ * (128 * QB) + wid * (32 * QB);
-    const long bh = (long)b * H + head, kbh = (long)(b / kv_div) * H + head;
+    const long bh = (long)b * H + head, kbh = (long)(KVI ? kv_index[b] : b / kv_div) * H + head;
     const int nt = Tkp / KV_TILE, nfull = Tk / KV_TILE;      // tiles / tiles without padded keys
     const char* kbase = (const char*)(Kp + kbh * Tkp * KS);
     const char* vbase = (const char*)(Vt + kbh * nt * vt_tile_halves(DPV));
@@ -614,6 +617,29 @@ __global__ __launch_bounds__(256, MINB ? MINB : (QB == 1 && DP <= 80 && TPB == 1
     }
     flash_block<D, DP, DPV, QB, NSTG, TPB, MINB, SPEC>(blockIdx.x, Qp, Kp, Vt, O, H, Tq, Tk, Tqp, Tkp, d, ldo, obstride, kv_div, nqb, flags);
 }
+// k_flash with a K / V panel index per sample (tcl_attention_kvindex_f16): kv_index[b] in [0, Bkv), checked on the host before the launch.  A kernel of
+// its own, so that k_flash above compiles to what it was; the gated pass walks the flags exactly as there.
+template <int D, int DP, int DPV, int QB, int NSTG, int TPB, int MINB, int SPEC>
+__global__ __launch_bounds__(256, MINB ? MINB : (QB == 1 && DP <= 80 && TPB == 1 ? 3 : 2)) void k_flash_kvi(const _Float16* __restrict__ Qp, const _Float16* __restrict__ Kp, const _Float16* __restrict__ Vt,
+                                                  _Float16* __restrict__ O, int H, int Tq, int Tk, int Tqp, int Tkp, int d, int ldo, long obstride,
+                                                  const int* __restrict__ kv_index, int nqb, int* __restrict__ flags, int nblk) {
+    if constexpr (D == 40 && QB == 2 && !SPEC) {
+        if (flags) {
+            const int per = (nblk + (int)gridDim.x - 1) / (int)gridDim.x, lo = (int)blockIdx.x * per, hi = min(lo + per, nblk);
+            for (int base = lo; base < hi; base += 256) {
+                const int mine = base + (int)threadIdx.x < hi ? flags[base + threadIdx.x] : 0;
+                if (!__syncthreads_or(mine)) continue;
+                for (int bid = base; bid < min(base + 256, hi); ++bid) {
+                    if (!flags[bid]) continue;
+                    flash_block<D, DP, DPV, QB, NSTG, TPB, MINB, SPEC, false, true>(bid, Qp, Kp, Vt, O, H, Tq, Tk, Tqp, Tkp, d, ldo, obstride, 1, nqb, flags, nullptr, kv_index);
+                    __syncthreads();
+                }
+            }
+            return;
+        }
+    }
+    flash_block<D, DP, DPV, QB, NSTG, TPB, MINB, SPEC, false, true>(blockIdx.x, Qp, Kp, Vt, O, H, Tq, Tk, Tqp, Tkp, d, ldo, obstride, 1, nqb, flags, nullptr, kv_index);
+}
 
 // ---- optional in-library timing of the flash kernel (bench.py roofline leg): HIP events recorded on the launch stream
 #include <vector>
@@ -645,16 +671,20 @@ struct AttnCall {
     AttnPanels p;
     _Float16 *Qp, *Kp, *Vt; int* flags;
     hipStream_t st;
+    int Bkv;                                           // entries of the K / V panels: B / kv_div, or kv_rows under a per-sample index
+    const int* kv_index;                               // device int32 [B] (NULL: b / kv_div): the K / V entry of every sample, each in [0, Bkv)
 };
 static bool attn_shape_ok(int B, int H, int Tq, int Tk, int d, int kv_div) {
     return B > 0 && H > 0 && Tq > 0 && Tk > 0 && kv_div > 0 && B % kv_div == 0 && (d == 40 || d == 80 || d == 128 || d == 160);
 }
 // (shape already checked: kv_div > 0)
 static AttnCall attn_call(const void* q, int ldq, long qbs, const void* k, int ldk, long kbs, const void* v, int ldv, long vbs, void* o, int ldo, long obs,
-                          int B, int H, int Tq, int Tk, int d, float scale, int kv_div, int flags, void* ws_q, void* ws_kv, hipStream_t st) {
+                          int B, int H, int Tq, int Tk, int d, float scale, int kv_div, int flags, void* ws_q, void* ws_kv, hipStream_t st,
+                          const int* kv_index = nullptr, int kv_rows = 0) {
+    const int Bkv = kv_index ? kv_rows : B / kv_div;
     AttnCall c = {(const _Float16*)q, (const _Float16*)k, (const _Float16*)v, ldq, ldk, ldv, qbs, kbs, vbs, (_Float16*)o, ldo, obs, B, H, Tq, Tk, d, scale, kv_div,
-                  !(flags & TCL_ATTN_PREPACKED), (flags & TCL_ATTN_PACK_KV) != 0, (flags & TCL_ATTN_PAIR) != 0, attn_panels(B, B / kv_div, H, Tq, Tk, d)};
-    c.Qp = (_Float16*)ws_q; c.flags = (int*)((char*)ws_q + c.p.flags_off); c.Kp = (_Float16*)ws_kv; c.Vt = c.Kp + c.p.vt_off; c.st = st;
+                  !(flags & TCL_ATTN_PREPACKED), (flags & TCL_ATTN_PACK_KV) != 0, (flags & TCL_ATTN_PAIR) != 0, attn_panels(B, Bkv, H, Tq, Tk, d)};
+    c.Qp = (_Float16*)ws_q; c.flags = (int*)((char*)ws_q + c.p.flags_off); c.Kp = (_Float16*)ws_kv; c.Vt = c.Kp + c.p.vt_off; c.st = st; c.Bkv = Bkv; c.kv_index = kv_index;
     return c;
 }
 constexpr size_t flash_lds(int DP, int DPV, int NSTG) {      // NSTG ring slots of one K + V^T image in whole 1-KiB DMA pieces, + the 1-KiB dump
@@ -678,8 +708,17 @@ static int launch_flash(const AttnCall& c, int grid, bool gated) {      // gated
         if (g_prof.ev.size() > 8192) flash_prof_drain(false);       // a 300-frame pass has ~1e5 launches: keep the live event count bounded
         (void)hipEventCreate(&e0); (void)hipEventCreate(&e1); (void)hipEventRecord(e0, c.st);
     }
-    hipLaunchKernelGGL((k_flash<D, DP, DPV, QB, NSTG, TPB, MINB, SPEC>), dim3(grid), dim3(256), lds, c.st, c.Qp, c.Kp, c.Vt, c.o, c.H, c.Tq, c.Tk,
-                       c.p.Tqp, c.p.Tkp, c.d, c.ldo, c.obs, c.kv_div, nqb, SPEC || gated ? c.flags : nullptr, c.B * c.H * nqb);
+    if (c.kv_index) {
+        if constexpr (D != 128) {      // (the text cross-attention's head dims; attention_kvindex refuses 128)
+            static bool set_kvi = false;
+            if (!set_kvi) { (void)hipFuncSetAttribute((const void*)k_flash_kvi<D, DP, DPV, QB, NSTG, TPB, MINB, SPEC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); set_kvi = true; }
+            hipLaunchKernelGGL((k_flash_kvi<D, DP, DPV, QB, NSTG, TPB, MINB, SPEC>), dim3(grid), dim3(256), lds, c.st, c.Qp, c.Kp, c.Vt, c.o, c.H, c.Tq, c.Tk,
+                               c.p.Tqp, c.p.Tkp, c.d, c.ldo, c.obs, c.kv_index, nqb, SPEC || gated ? c.flags : nullptr, c.B * c.H * nqb);
+        } else return TCL_EINVAL;
+    } else {
+        hipLaunchKernelGGL((k_flash<D, DP, DPV, QB, NSTG, TPB, MINB, SPEC>), dim3(grid), dim3(256), lds, c.st, c.Qp, c.Kp, c.Vt, c.o, c.H, c.Tq, c.Tk,
+                           c.p.Tqp, c.p.Tkp, c.d, c.ldo, c.obs, c.kv_div, nqb, SPEC || gated ? c.flags : nullptr, c.B * c.H * nqb);
+    }
     // (the statistics count a call once: the gated pass is timed with the speculative launch it follows)
     if (prof) { (void)hipEventRecord(e1, c.st); g_prof.ev.push_back(e0); g_prof.ev.push_back(e1); if (!gated) { const double fl = 4.0 * c.B * c.H * (double)c.Tq * c.Tk * c.d; g_prof.flops += fl; g_prof.launches++; if (fl > g_prof.bigfl) { g_prof.bigfl = fl; g_prof.big[0] = c.B; g_prof.big[1] = c.H; g_prof.big[2] = c.Tq; g_prof.big[3] = c.Tk; } } }
     return hipPeekAtLastError() == hipSuccess ? TCL_OK : TCL_ELAUNCH;
@@ -768,7 +807,7 @@ static SplitKvWs splitkv_ws(int nsplit, int H, int Tq, int Tk, int d) {
 // The Q (scaled), K and V^T panels of a call, as its pack_q / pack_kv ask: one launch when both are packed.
 static int attention_pack(const AttnCall& c) {
     const AttnPanels& p = c.p;
-    const int Bkv = c.B / c.kv_div, nt = p.Tkp / KV_TILE;
+    const int Bkv = c.Bkv, nt = p.Tkp / KV_TILE;
     const long qc = (long)c.B * c.H * p.Tqp * (p.DP / 8), kc = (long)Bkv * c.H * p.Tkp * (p.KS / 8);
     const int gq = stream_grid(qc, 256, 2), gk = stream_grid(kc, 256, 2);
     const size_t vt_lds = (size_t)64 * (p.DPV + 2) * 2;
@@ -785,6 +824,15 @@ static int attention_pack(const AttnCall& c) {
         if (c.pack_kv) hipLaunchKernelGGL(k_pack_vt, dim3(nt, Bkv * c.H), dim3(256), vt_lds, c.st, c.v, c.vbs, c.ldv, c.Tk, c.H, c.d, c.Vt, nt, p.DPV, p.skew);
     }
     return hipPeekAtLastError() == hipSuccess ? TCL_OK : TCL_ELAUNCH;
+}
+
+// pack (as the call's flags ask), choose, run
+static int attention_run(const AttnCall& c) {
+    if (attention_pack(c) != TCL_OK) return TCL_ELAUNCH;
+    const FlashPlan pl = choose(c, flash40_mode());
+    int rc = pl.v->run(c, pl.grid, false);
+    if (rc == TCL_OK && pl.second) rc = pl.second->run(c, pl.grid2, true);
+    return rc;
 }
 
 extern "C" {
@@ -836,12 +884,17 @@ int tcl_attention_f16(const void* q, int ldq, long qbs, const void* k, int ldk, 
                       hipStream_t st) {
     TCL_CHECK_ARG(q && o && ws_q && ws_kv && attn_shape_ok(B, H, Tq, Tk, d, kv_div));
     TCL_CHECK_ARG(!(pack_kv & TCL_ATTN_PACK_KV) || ((k && v) && !(pack_kv & TCL_ATTN_PREPACKED)));
-    const AttnCall c = attn_call(q, ldq, qbs, k, ldk, kbs, v, ldv, vbs, o, ldo, obs, B, H, Tq, Tk, d, scale, kv_div, pack_kv, ws_q, ws_kv, st);
-    if (attention_pack(c) != TCL_OK) return TCL_ELAUNCH;
-    const FlashPlan pl = choose(c, flash40_mode());
-    int rc = pl.v->run(c, pl.grid, false);
-    if (rc == TCL_OK && pl.second) rc = pl.second->run(c, pl.grid2, true);
-    return rc;
+    return attention_run(attn_call(q, ldq, qbs, k, ldk, kbs, v, ldv, vbs, o, ldo, obs, B, H, Tq, Tk, d, scale, kv_div, pack_kv, ws_q, ws_kv, st));
+}
+// tcl_attention_f16 with the K / V entry of every sample read from a table (generation.prompt_path: every frame its own text).  kv_index NULL: that call.
+int tcl_attention_kvindex_f16(const void* q, int ldq, long qbs, const void* k, int ldk, long kbs, const void* v, int ldv, long vbs, void* o, int ldo,
+                              long obs, int B, int H, int Tq, int Tk, int d, float scale, int kv_div, int pack_kv, void* ws_q, void* ws_kv,
+                              const int* kv_index, const int* h_kv_index, int kv_rows, hipStream_t st) {
+    if (!kv_index) return tcl_attention_f16(q, ldq, qbs, k, ldk, kbs, v, ldv, vbs, o, ldo, obs, B, H, Tq, Tk, d, scale, kv_div, pack_kv, ws_q, ws_kv, st);
+    TCL_CHECK_ARG(q && o && ws_q && ws_kv && attn_shape_ok(B, H, Tq, Tk, d, 1) && d != 128 && h_kv_index && kv_rows > 0);
+    TCL_CHECK_ARG(!(pack_kv & TCL_ATTN_PACK_KV) || ((k && v) && !(pack_kv & TCL_ATTN_PREPACKED)));
+    for (int b = 0; b < B; ++b) TCL_CHECK_ARG(h_kv_index[b] >= 0 && h_kv_index[b] < kv_rows);      // the host copy of the table: nothing is launched on a bad one
+    return attention_run(attn_call(q, ldq, qbs, k, ldk, kbs, v, ldv, vbs, o, ldo, obs, B, H, Tq, Tk, d, scale, 1, pack_kv, ws_q, ws_kv, st, kv_index, kv_rows));
 }
 // What choose() decides for tcl_attention_f16(..., flags, ...): out4 = (variant id, blocks of its launch, blocks of the gated exact launch behind the
 // speculative kernel or 0, dynamic LDS bytes).  Pure host code.

@@ -13,11 +13,16 @@ decode once per ramp (left, right, bottom, top) from the same start, and one tcl
 generation.light_path (an animated light; in neither the reference nor the demos): light_ramps renders one ramp per distinct angle of the rank's frames;
 build_start (fc) makes them the per-frame img2img start, prepare_fbc (fbc) the per-frame backgrounds; distinct ramps are encoded once and gathered.
 
+generation.prompt_path (a text conditioning that changes over the clip; in neither the reference nor the demos): frame_text blends the keyframe prompts'
+embeddings into one row per distinct (k0, k1, t) of the rank's frames (tcl_text_lerp_f16); the xy passes hand the frame ids of their samples to the UNet,
+whose text cross-attention then reads every sample's own K / V (unet.FrameText).  The yt passes keep prompt_t.
+
 Python sequences kernel launches and collectives; tensors never leave the device inside the timed region and there is no
 per-iteration host sync (the reference syncs on loss.item() and moves the token bank through the CPU).
 """
 import math
 import os
+import struct
 import time
 from types import SimpleNamespace
 
@@ -30,6 +35,7 @@ from . import post_opt
 from .dataparser import check_latent_exists, get_latents_dir, load_latent
 from .parallel import Dist, sharded_temporal_pass
 from .scheduler import DPMSolverSDEScheduler
+from .unet import FrameText
 
 H16 = torch.float16
 I32 = torch.int32
@@ -77,6 +83,12 @@ DEFAULTS = dict(  # configs/tclight_default.yaml (generation / post_opt sections
     # ^ IC-Light's "Compute Normal" (the background demo's process_normal), fbc only: Generator.normals relights the frames under the left / right /
     #   bottom / top ramps from one seed and turns the four results into per-frame surface normals and the ambient image (tcl_fbc_normal).
     #   bg_source is not consulted, stage 1 / 2 do not run.  false (default): nothing of it is consulted and every path is what it was.
+    prompt_path=None,
+    # ^ a prompt that changes over the clip: keyframes [[pos, "prompt"], ...] (pos as in light_path, strictly increasing, 0 first and 1 last).  Every
+    #   frame's text conditioning of the xy passes is the linear blend of its two neighbouring keyframes' embeddings (frame_text); the negative prompt
+    #   is one for all, the yt passes keep prompt_t.  generation.prompt is then only the run's name.  None (default): nothing of it is consulted and
+    #   every path is what it was.  With it the K / V panels of the distinct rows stay resident (UNetEngine.text_rows_bytes: 7.6 MB per row over
+    #   the 16 blocks, 2.3 GB for 300 distinct rows); the token budget below is taken from what is left.
     max_tokens_per_pass=None)
     # ^ None: TCL_MAX_TOKENS_PER_PASS (read when the Generator is built), else min(16 M, 80 % of the device's free memory / 10.5 KB) -- a block-major pass
     #   peaks at ~10.4 KB of activations per level-0 token (90 GB for the 8.64 M tokens of 300 frames at 1280x720): a 288 GB MI355X gets the 16 M
@@ -88,8 +100,9 @@ DEFAULTS = dict(  # configs/tclight_default.yaml (generation / post_opt sections
     #   the in-call tuner -- the 4.5 M line of that file).  tests/test_gpu_fullsize.py pins pass-size invariance (same bits) beyond 2^31 elements.
 
 
-def default_max_tokens_per_pass(unet, dev):
-    """max_tokens_per_pass when the configuration leaves it open (see DEFAULTS): TCL_MAX_TOKENS_PER_PASS, else what the device's free memory carries."""
+def default_max_tokens_per_pass(unet, dev, reserve=0):
+    """max_tokens_per_pass when the configuration leaves it open (see DEFAULTS): TCL_MAX_TOKENS_PER_PASS, else what the device's free memory carries.
+    reserve: bytes that will be held beside the pass and are not allocated yet (the per-frame text K / V panels of generation.prompt_path)."""
     env = os.environ.get("TCL_MAX_TOKENS_PER_PASS")
     if env:
         return int(env)
@@ -98,6 +111,7 @@ def default_max_tokens_per_pass(unet, dev):
         free = torch.cuda.mem_get_info(dev)[0] + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
     if hasattr(unet, "panel_cache_cap"):      # persistent attention panels live beside the pass (a stand-in engine keeps none)
         free -= max(0, unet.panel_cache_cap() - unet.panel_cache_bytes())
+    free -= int(reserve)
     return int(min(16_000_000, max(1_000_000, 0.8 * free / 10_500)))
 
 
@@ -128,6 +142,7 @@ class Generator:
         c.iclight_model, c.bg_source = HL.check_fbc(c.iclight_model, c.bg_source, c.init_latent, c.highres_scale, bool(cfg.get("background_cond")))
         self.fbc = c.iclight_model == "fbc"
         self.normal_sides = HL.check_normal(c.normal, c.iclight_model, c.fbc_matting, c.apply_opt)      # () unless generation.normal
+        c.prompt_path = HL.check_prompt_path(c.prompt_path, c.normal, c.highres_scale)
         self.bg_per_frame = None           # __call__'s background_per_frame: whether the fbc background is one frame per frame (None: by its length)
         cin = getattr(self.unet, "w", {}).get("conv_in", (None, None, None))[2]      # a stand-in engine may carry no weights
         if cin is not None and cin != 4 + HL.cond_channels(c.iclight_model):
@@ -137,7 +152,12 @@ class Generator:
         self.batch_size = 2
         self.timing = {}
         if c.max_tokens_per_pass is None:
-            c.max_tokens_per_pass = default_max_tokens_per_pass(self.unet, self.dev)
+            reserve = 0
+            if c.prompt_path is not None and c.frame_ids is not None and hasattr(self.unet, "text_rows_bytes"):
+                # the K / V panels of the negative and of at most one row per frame of this rank (frame_ids unknown: the bound is not known here)
+                lo, hi = self.dist.range(len(c.frame_ids))
+                reserve = self.unet.text_rows_bytes(1 + hi - lo)
+            c.max_tokens_per_pass = default_max_tokens_per_pass(self.unet, self.dev, reserve)
 
     # ------------------------------------------------------------------ data
     def prepare_data(self, frames, background=None):
@@ -353,6 +373,27 @@ class Generator:
         images, index = self.light_ramps(self.light_angles, H, W, *HL.LIGHT_LEVELS[c.iclight_model])
         return images, index, several
 
+    def frame_text(self, uncond, keys, n, n_total=None):
+        """generation.prompt_path: the per-frame text of this rank's n frames, from the frames' GLOBAL positions (a rank of a sharded run builds the
+        rows of the frames it denoises).  uncond [L,768] f16: the negative prompt; keys [P,L,768] f16: the distinct keyframe prompts in the order of
+        HL.prompt_table (text.encode_prompt_set).  Frames with equal (k0, k1, t) share a row; all rows leave in one tcl_text_lerp_f16 launch, t rounded
+        from f64 to f32 once.  -> unet.FrameText, which takes the place of `conds` in __call__ / ddim_sample."""
+        c = self.cfg
+        if c.prompt_path is None:
+            raise ValueError("Generator.frame_text needs generation.prompt_path")
+        n_total = n_total or getattr(self, "n_total", None) or n * self.dist.world
+        lo, hi = self.dist.range(n_total)
+        assert hi - lo == n
+        prompts, rows, index = HL.prompt_table(c.prompt_path, n_total, lo, hi)
+        keys = keys.to(self.dev).to(H16).contiguous()
+        if keys.dim() != 3 or keys.shape[0] != len(prompts):
+            raise ValueError(f"generation.prompt_path: {len(prompts)} distinct keyframe prompts, embeddings {tuple(keys.shape)}")
+        h_tab = torch.tensor([[k0, k1, struct.unpack("<i", struct.pack("<f", t))[0]] for k0, k1, t in rows], dtype=I32)
+        out = torch.empty(len(rows), *keys.shape[1:], dtype=H16, device=self.dev)
+        self.L.tcl_text_lerp_f16(out, keys, len(prompts), h_tab.to(self.dev), h_tab, len(rows), keys.shape[1] * keys.shape[2], stream())
+        self.prompt_rows = rows
+        return FrameText(uncond.to(self.dev), out, index)
+
     def build_start(self, concat_conds):
         """img2img start (gradio_demo_iclight.py:283-299 -> the img2img pipeline's add_noise): init_noise = alpha*x0 + sigma_t*z at the first executed
         sigma, with z the f32 draw of prepare_data and x0 the light gradient's latent (encoded once, shared by all frames) or, for `source`,
@@ -505,7 +546,9 @@ class Generator:
         """One block-major UNet pass per group of chunks.  pack(grp) -> (xin, idx, n); unpack(eps, idx, n)."""
         for grp in groups:
             xin, idx, n = pack(grp)
-            eps = self.unet.forward_many(xin, [len(c) for c in grp], Hh, Ww, t, text, cfg_pair=True)     # the pack kernel wrote both halves
+            # per-frame text (prompt_path, xy passes only): the UNet needs to know which frame each sample is
+            kw = dict(frames=[f for c in grp for f in c]) if isinstance(text, FrameText) else {}
+            eps = self.unet.forward_many(xin, [len(c) for c in grp], Hh, Ww, t, text, cfg_pair=True, **kw)     # the pack kernel wrote both halves
             unpack(eps, idx, n)
 
     def _unet_xy(self, x, cc, chunks, text, t, noises):
@@ -625,7 +668,7 @@ class Generator:
     def __call__(self, frames, conds, conds_t, past_flows, mask_bwds, unq_inv, n_total=None, k=None, background=None, frames_hr=None,
                  background_per_frame=None):
         """frames: local block [n_local,3,H,W]; conds / conds_t: [2,L,768] f16 (uncond, cond) text embeddings for the xy / yt
-        passes (generate.py:553-555); past_flows / mask_bwds / unq_inv: stage-2 inputs for ALL frames (device).
+        passes (generate.py:553-555) -- under generation.prompt_path conds is the FrameText of frame_text; past_flows / mask_bwds / unq_inv: stage-2 inputs for ALL frames (device).
         Returns (relit frames [N,3,H,W] f32, info dict).
         With generation.highres_scale > 1: frames_hr is the local block at HL.highres_size [n_local,3,H2,W2], the stage-2 inputs live at that size
         and so do the returned frames.
@@ -637,6 +680,8 @@ class Generator:
         if self.highres and background is not None:
             raise ValueError("generation.background_cond together with generation.highres_scale > 1 is not supported")
         self.n_total = n_total or frames.shape[0] * d.world
+        if (c.prompt_path is not None) != isinstance(conds, FrameText) or (isinstance(conds, FrameText) and len(conds.index) != frames.shape[0]):
+            raise ValueError("generation.prompt_path: conds must be the FrameText of Generator.frame_text for this rank's frames (and only then)")
         ev = lambda: (torch.cuda.synchronize(self.dev), time.perf_counter())[1]
         t0 = ev()
         self.prepare_data(frames, background)

@@ -291,7 +291,69 @@ def light_dirs(angles):
     return out
 
 
-TOME_MAX_SRC_TOKENS = 64 * 1024         # tcl_tome_match_f16 / _affine_f16: source tokens of one match (csrc/merge.hip)
+def check_prompt_path(path, normal=False, highres_scale=1.0):
+    """generation.prompt_path: None (off: nothing else is looked at) or keyframes [[pos, "prompt"], ...] -> [[float, str], ...]; anything else is a
+    ValueError naming the key (run.py raises it before a model is loaded).  pos strictly increasing, the first 0 and (with more than one keyframe)
+    the last 1 -- a single [[0, "p"]] is a constant path; every prompt a non-empty string.  Refused by both key names, as out of scope rather than
+    impossible: generation.normal and a generation.highres_scale other than 1."""
+    if path is None:
+        return None
+    if not isinstance(path, (list, tuple)) or len(path) == 0:
+        raise ValueError(f"generation.prompt_path {path!r}: expected null or a list of keyframes [[pos, \"prompt\"], ...] with at least one")
+    keys = []
+    for kf in path:
+        if (not isinstance(kf, (list, tuple)) or len(kf) != 2 or not _is_number(kf[0]) or not math.isfinite(kf[0])
+                or not isinstance(kf[1], str) or not kf[1].strip()):
+            raise ValueError(f"generation.prompt_path keyframe {kf!r}: expected [pos, \"prompt\"], a finite number and a non-empty string")
+        keys.append([float(kf[0]), kf[1]])
+    pos = [k[0] for k in keys]
+    if pos[0] != 0.0 or (len(keys) > 1 and pos[-1] != 1.0) or any(b <= a for a, b in zip(pos, pos[1:])):
+        raise ValueError(f"generation.prompt_path positions {pos}: expected strictly increasing values, the first 0 and (with more than one "
+                         "keyframe) the last 1")
+    if normal:
+        raise ValueError("generation.prompt_path together with generation.normal is not supported: the four relights of the normal share one prompt")
+    if isinstance(highres_scale, bool) or not isinstance(highres_scale, (int, float)) or float(highres_scale) != 1.0:
+        raise ValueError(f"generation.prompt_path together with generation.highres_scale {highres_scale!r} is not supported: the second pass is "
+                         "conditioned on one prompt")
+    return keys
+
+
+def prompt_sweep(prompt_a, prompt_b):
+    """--prompt_sweep A B -> generation.prompt_path [[0, A], [1, B]]."""
+    return [[0.0, str(prompt_a)], [1.0, str(prompt_b)]]
+
+
+def prompt_table(path, n_total, lo=0, hi=None):
+    """The per-frame text of generation.prompt_path for the run's frames lo <= i < hi (GLOBAL indices, positions as light_positions: a rank of a
+    sharded run builds the rows of the frames it denoises).  -> (prompts, rows, index):
+      prompts  the distinct keyframe prompts in order of first appearance (each is encoded once);
+      rows     the distinct (k0, k1, t) of these frames in order of first appearance, k0 / k1 indices into `prompts` and t = (pos - p0)/(p1 - p0) in f64
+               -- one embedding row each (tcl_text_lerp_f16);
+      index    the row of every frame lo .. hi - 1.
+    A frame that lands on a keyframe, and a segment whose two prompts are the same text, is (k, k, 0.0): the keyframe's own bits."""
+    hi = n_total if hi is None else hi
+    prompts, key = [], []
+    for _, text in path:
+        if text not in prompts:
+            prompts.append(text)
+        key.append(prompts.index(text))
+    rows, index = [], []
+    for p in light_positions(n_total, lo, hi):
+        k = 0
+        while k + 1 < len(path) and path[k + 1][0] <= p:
+            k += 1
+        if k + 1 == len(path) or path[k][0] == p or key[k] == key[k + 1]:
+            row = (key[k], key[k], 0.0)
+        else:
+            p0, p1 = path[k][0], path[k + 1][0]
+            row = (key[k], key[k + 1], (p - p0) / (p1 - p0))
+        if row not in rows:
+            rows.append(row)
+        index.append(rows.index(row))
+    return prompts, rows, index
+
+
+TOME_MAX_SRC_TOKENS = 64 * 1024        # tcl_tome_match_f16 / _affine_f16: source tokens of one match (csrc/merge.hip)
 
 
 def check_highres_tokens(H2, W2, chunk_size):

@@ -111,15 +111,13 @@ def _stand_in(txt, dev):
     return torch.from_numpy(np.random.default_rng(seed).standard_normal((n, 77, 768)).astype(np.float32)).to(dev).half()
 
 
-def encode_prompt_pair(positive, negative, dev, enc_dir=None, allow_random=False, tokenizer=None, text_encoder=None, lora=None):
-    """-> [2, L*k, 768] f16 = cat([uncond, cond]) (generate.py:553-555).  `lora` (lora.LoRASet): its text-encoder entries are merged into
-    the checkpoint under `enc_dir`; a tokenizer / text_encoder handed in is used as it is."""
+def _encode_chunks(texts, dev, enc_dir, allow_random, tokenizer, text_encoder, lora):
+    """The chunked embedding [n_chunks, L, D] of every text, on the CLIP engine or -- no checkpoint and allow_random -- as stand-ins."""
     global _WARNED_TE_LORA
     if tokenizer is None and enc_dir and os.path.isdir(enc_dir):
         tokenizer, text_encoder = load_text_encoder(enc_dir, dev, lora)
     if tokenizer is not None:
-        c = encode_prompt_inner(positive, tokenizer, text_encoder, dev)
-        uc = encode_prompt_inner(negative, tokenizer, text_encoder, dev)
+        return [encode_prompt_inner(t, tokenizer, text_encoder, dev) for t in texts]
     else:
         if not allow_random:
             raise FileNotFoundError(f"CLIP text encoder directory {enc_dir!r} not found (models.text_encoder); set models.allow_random / "
@@ -131,6 +129,22 @@ def encode_prompt_pair(positive, negative, dev, enc_dir=None, allow_random=False
                 _WARNED_TE_LORA = True
                 warnings.warn("the LoRA carries text-encoder entries (lora_te_ / text_encoder.), but the stand-in embeddings have no text "
                               "encoder to merge them into: they are not applied")
-        c, uc = _stand_in(positive, dev), _stand_in(negative, dev)
+        return [_stand_in(t, dev) for t in texts]
+
+
+def encode_prompt_pair(positive, negative, dev, enc_dir=None, allow_random=False, tokenizer=None, text_encoder=None, lora=None):
+    """-> [2, L*k, 768] f16 = cat([uncond, cond]) (generate.py:553-555).  `lora` (lora.LoRASet): its text-encoder entries are merged into
+    the checkpoint under `enc_dir`; a tokenizer / text_encoder handed in is used as it is."""
+    c, uc = _encode_chunks([positive, negative], dev, enc_dir, allow_random, tokenizer, text_encoder, lora)
     c, uc = tile_and_concat(c, uc)
     return torch.cat([uc, c]).to(torch.float16).contiguous()
+
+
+def encode_prompt_set(positives, negative, dev, enc_dir=None, allow_random=False, tokenizer=None, text_encoder=None, lora=None):
+    """generation.prompt_path: the keyframe prompts and the one negative, each encoded once exactly as encode_prompt_pair encodes its two, and all
+    brought to the chunk count of the longest (tile_and_concat's cycling) so that they can be blended element by element.
+    -> (uncond [L*k, 768], conds [P, L*k, 768]) f16; with one prompt they are the two halves of encode_prompt_pair, bit for bit."""
+    embs = _encode_chunks(list(positives) + [negative], dev, enc_dir, allow_random, tokenizer, text_encoder, lora)
+    longest = max(embs, key=lambda e: e.shape[0])
+    seqs = [tile_and_concat(e, longest)[0] for e in embs]
+    return seqs[-1][0].to(torch.float16).contiguous(), torch.cat(seqs[:-1]).to(torch.float16).contiguous()

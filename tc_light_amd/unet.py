@@ -52,6 +52,34 @@ class Switches(NamedTuple):
         return cls(*(os.environ.get("TCL_" + f.upper(), "1") != "0" for f in cls._fields))
 
 
+class FrameText:
+    """generation.prompt_path: a text conditioning per frame instead of one per guidance half.  neg [L, 768] f16 is the negative prompt all frames
+    share, rows [R, L, 768] f16 the distinct per-frame embeddings (tcl_text_lerp_f16) and index[f] the row of LOCAL frame f.  `text` [1 + R, L, 768]
+    is what every transformer block projects to K | V once per run: entry 0 the negative, entry 1 + r row r."""
+
+    def __init__(self, neg, rows, index):
+        R, Lt, D = rows.shape
+        if tuple(neg.shape[-2:]) != (Lt, D) or neg.numel() != Lt * D:
+            raise ValueError(f"FrameText: negative embedding {tuple(neg.shape)} against rows {tuple(rows.shape)}")
+        self.index = [int(i) for i in index]
+        if not self.index or min(self.index) < 0 or max(self.index) >= R:
+            raise ValueError(f"FrameText: frame -> row table outside [0, {R})")
+        self.rows = R
+        self.text = torch.cat([neg.reshape(1, Lt, D).to(rows), rows]).to(H16).contiguous()
+
+    def kv_index(self, frames, dev):
+        """The K / V entry of every sample of a pass over `frames` (local ids, in sample order): the unconditional half takes entry 0, the conditional
+        sample of frame f entry 1 + index[f].  -> KVIndex, built on the host and uploaded once per pass."""
+        host = torch.tensor([0] * len(frames) + [1 + self.index[f] for f in frames], dtype=torch.int32)
+        return KVIndex(host.to(dev), host, 1 + self.rows)
+
+
+class KVIndex(NamedTuple):
+    dev: torch.Tensor      # int32 [B] on the device
+    host: torch.Tensor     # the same table on the host: tcl_attention_kvindex_f16 checks its range there
+    rows: int              # entries of the K / V panels
+
+
 GEMM_TABLE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "gemm_tune_gfx950.txt")
 
 
@@ -145,19 +173,29 @@ class Ops:
         self.L.tcl_ln_gemm_f16(x, gamma, beta, 1e-5, w, bias if bias is not None else 0, 0, c, M, N, K, K, K, c.shape[1], N, act, stream())
         return c
 
-    def attention(self, q, ldq, qbs, k, ldk, kbs, v, ldv, vbs, B, Hh, Tq, Tk, d, kv_div=1, ws_kv=None, pack_kv=True, pair=False):
-        """Strided operands: Q is packed into a fresh panel workspace, K / V into ws_kv (pack_kv=False: ws_kv already holds them packed)."""
+    def attention(self, q, ldq, qbs, k, ldk, kbs, v, ldv, vbs, B, Hh, Tq, Tk, d, kv_div=1, ws_kv=None, pack_kv=True, pair=False, kvi=None):
+        """Strided operands: Q is packed into a fresh panel workspace, K / V into ws_kv (pack_kv=False: ws_kv already holds them packed).
+        kvi (KVIndex): every sample's K / V entry comes from that table instead of b // kv_div; ws_kv holds kvi.rows entries."""
         o = self.empty(B * Tq, Hh * d)
         wq = torch.empty(self.L.tcl_attention_q_bytes(B, Hh, Tq, d), dtype=torch.uint8, device=self.dev)
+        if kvi is not None:
+            self.L.tcl_attention_kvindex_f16(q, ldq, qbs, k, ldk, kbs, v, ldv, vbs, o, Hh * d, Tq * Hh * d, B, Hh, Tq, Tk, d, d ** -0.5, 1,
+                                             (TCL_ATTN_PACK_KV if pack_kv else 0) | (TCL_ATTN_PAIR if pair else 0), wq, ws_kv, kvi.dev, kvi.host, kvi.rows,
+                                             stream())
+            return o
         if ws_kv is None:
             ws_kv = torch.empty(self.L.tcl_attention_kv_bytes(B // kv_div, Hh, Tk, d), dtype=torch.uint8, device=self.dev)
         self.L.tcl_attention_f16(q, ldq, qbs, k, ldk, kbs, v, ldv, vbs, o, Hh * d, Tq * Hh * d, B, Hh, Tq, Tk, d, d ** -0.5, kv_div,
                                  (TCL_ATTN_PACK_KV if pack_kv else 0) | (TCL_ATTN_PAIR if pair else 0), wq, ws_kv, stream())
         return o
 
-    def attention_prepacked(self, wq, wkv, B, Hh, Tq, Tk, d, kv_div=1, pair=False, ldq=0, qbs=0):
+    def attention_prepacked(self, wq, wkv, B, Hh, Tq, Tk, d, kv_div=1, pair=False, ldq=0, qbs=0, kvi=None):
         """Panels already filled by tcl_gemm_qkv_panels_f16 / tcl_ln_gemm_qpanel_f16; ldq / qbs: strides of the Q tensor never written (the ABI takes them)."""
         o = self.empty(B * Tq, Hh * d)
+        if kvi is not None:
+            self.L.tcl_attention_kvindex_f16(wq, ldq, qbs, 0, 0, 0, 0, 0, 0, o, Hh * d, Tq * Hh * d, B, Hh, Tq, Tk, d, d ** -0.5, 1,
+                                             TCL_ATTN_PREPACKED | (TCL_ATTN_PAIR if pair else 0), wq, wkv, kvi.dev, kvi.host, kvi.rows, stream())
+            return o
         self.L.tcl_attention_f16(wq, ldq, qbs, 0, 0, 0, 0, 0, 0, o, Hh * d, Tq * Hh * d, B, Hh, Tq, Tk, d, d ** -0.5, kv_div,
                                  TCL_ATTN_PREPACKED | (TCL_ATTN_PAIR if pair else 0), wq, wkv, stream())
         return o
@@ -314,6 +352,11 @@ class UNetEngine:
     def panel_cache_bytes(self):
         return sum(a.numel() + b.numel() for a, b in self._panel_cache.values())
 
+    def text_rows_bytes(self, rows, Lt=77):
+        """Bytes the K / V panels of `rows` text entries hold over all transformer blocks (tcl_attention_kv_bytes per block): what a FrameText of that many
+        rows keeps resident beside the pass.  Generator.__init__'s token budget subtracts it."""
+        return sum(self.L.tcl_attention_kv_bytes(int(rows), sd15.HEADS, Lt, blk["c"] // sd15.HEADS) for blk in self.tfm.values())
+
     def drop_panels(self):
         self._panel_cache.clear()
         self._qpanels.clear()
@@ -385,21 +428,26 @@ class UNetEngine:
         self.tome.unmerge_add(h, xbs, y, T, unm, FN, C, ne)
         self._fl(2.0 * T * C * C * 4 + 4.0 * T * T * C, 2, ne)
 
-    def _attn2(self, blk, h, B, N, text, fuse_ln, qpanel):
-        """Text cross-attention on the full tokens; every sample of a guidance half shares that half's text K / V (kv_div)."""
+    def _attn2(self, blk, h, B, N, text, fuse_ln, qpanel, kvi=None):
+        """Text cross-attention on the full tokens; every sample of a guidance half shares that half's text K / V (kv_div).
+        kvi (text is a FrameText): every sample attends to the K / V of its own frame's row; the rows are projected and packed once per run, after which
+        only their panels are kept."""
         o, C, Hd, d, M = self.ops, blk["c"], sd15.HEADS, blk["c"] // sd15.HEADS, B * N
-        tk = self._text_kv(blk, text)
+        tk = self._text_kv(blk, text.text if kvi is not None else text)
         Lt = tk["L"]
         if fuse_ln and qpanel and tk["packed"]:
             # norm2 -> to_q straight into the attention kernel's query panel (linstrip.hip Q-panel epilogue): no [M, C] output, no pack pass
             wq = self._q_panel(B, Hd, N, d)
             self.L.tcl_ln_gemm_qpanel_f16(h, *blk["ln"][1], 1e-5, blk["q2"], M, Hd, d, N, C, C, d ** -0.5, wq, stream())
-            a = o.attention_prepacked(wq, tk["ws"], B, Hd, N, Lt, d, kv_div=B // 2, ldq=C, qbs=N * C)
+            a = o.attention_prepacked(wq, tk["ws"], B, Hd, N, Lt, d, kv_div=B // 2, ldq=C, qbs=N * C, kvi=kvi)
         else:
             q = o.ln_gemm(h, *blk["ln"][1], blk["q2"]) if fuse_ln else o.gemm(o.layernorm(h, *blk["ln"][1], M, C), blk["q2"])
-            a = o.attention(q, C, N * C, tk["kv"], 2 * C, Lt * 2 * C, tk["kv"][:, C:], 2 * C, Lt * 2 * C, B, Hd, N, Lt, d,
-                            kv_div=B // 2, ws_kv=tk["ws"], pack_kv=not tk["packed"])
+            kv = tk["kv"]
+            a = o.attention(q, C, N * C, kv if kv is not None else 0, 2 * C, Lt * 2 * C, kv[:, C:] if kv is not None else 0, 2 * C, Lt * 2 * C, B, Hd, N, Lt, d,
+                            kv_div=B // 2, ws_kv=tk["ws"], pack_kv=not tk["packed"], kvi=kvi)
         tk["packed"] = True
+        if kvi is not None:
+            tk["kv"] = None                                     # the [rows * L, 2C] projection is read by the pack alone
         self._fl(2.0 * C * C * 2 + 4.0 * Lt * C, M)
         return o.gemm(a, blk["o2"][0], blk["o2"][1], resid=h)
 
@@ -409,7 +457,7 @@ class UNetEngine:
         self._fl(2.0 * C * C * 12, M)
         return o.gemm(f2, blk["ff2"][0], blk["ff2"][1], resid=h)
 
-    def _transformer(self, p, x, B, Fs, Hh, Ww, text, sw, pair_half=False):
+    def _transformer(self, p, x, B, Fs, Hh, Ww, text, sw, pair_half=False, kvi=None):
         """x [B*N, C], B = 2*sum(Fs) samples: the unconditional ones of all chunks, then the conditional ones; only `_attn1_merged` goes chunk by chunk.
         pair_half: x holds only the FIRST half of the B samples (see forward_many: the two classifier-free-guidance halves are identical up to
         the first text cross-attention); proj_in, norm1, the VidToMe merge and attn1 run on that half, the result is duplicated before attn2."""
@@ -426,7 +474,7 @@ class UNetEngine:
         if pair_half:                                           # from here on the halves differ (text): both exist
             h, x = torch.cat([h, h]), torch.cat([x, x])
         fuse_ln = C == 320 and sw.ln_gemm                       # norm2 / norm3 ride in the consumer's operand load (strip-resident Linear)
-        h = self._attn2(blk, h, B, N, text, fuse_ln, sw.qpanel)
+        h = self._attn2(blk, h, B, N, text, fuse_ln, sw.qpanel, kvi)
         h = self._feed_forward(blk, h, B * N, fuse_ln)
         return o.gemm(h, blk["pout"][0], blk["pout"][1], resid=x)
 
@@ -438,17 +486,24 @@ class UNetEngine:
     # orders -- data flow per chunk, bank order per block -- so inside a block only attn1 loops over the chunks; ResNet blocks,
     # norms, cross-attention, feed-forward and the non-merging levels see 8-31x more rows per GEMM and one launch instead of one
     # per chunk, and every weight matrix is streamed once per step.
-    def forward_many(self, x_in, Fs, Hh, Ww, t, text, cfg_pair=False):
+    def forward_many(self, x_in, Fs, Hh, Ww, t, text, cfg_pair=False, frames=None):
         """x_in [2*Ftot, Hh, Ww, 8] f16 (latents | concat_conds; Ftot = sum(Fs) samples in chunk order, twice: uncond, cond);
         text [2, L, 768] f16 (uncond, cond).  Fs: chunk lengths in the reference's chunk order.  -> eps [2*Ftot, Hh, Ww, 4] f16.
         cfg_pair: the caller GUARANTEES x_in[Ftot:] == x_in[:Ftot] (the classifier-free-guidance pair of generate.py:342-347: `torch.cat([latents] * 2)`
         and the same concat_conds, written twice by tcl_pack_latents_f16).  The two halves then differ only through the text, which first enters in
         attn2 of the first transformer block: conv_in, the first ResNet block and proj_in / norm1 / VidToMe merge / attn1 of that block run ONCE and
         are duplicated -- the same bits as computing them twice (every kernel is deterministic and batch-row independent; with equal scores in both
-        entries the matching picks the first: `test_cfg_pair_dedup_bit_identical`).  TCL_CFG_DEDUP=0 computes both halves."""
+        entries the matching picks the first: `test_cfg_pair_dedup_bit_identical`).  TCL_CFG_DEDUP=0 computes both halves.
+        text a FrameText (generation.prompt_path): frames = the local frame id of each of the Ftot samples, in sample order; every conditional sample
+        then attends to its own frame's text, the unconditional half to the one negative.  The prefix shared by the halves ends at the first attn2."""
         o, L, w = self.ops, self.L, self.w
         Ftot = sum(Fs)
         B = 2 * Ftot
+        kvi = None
+        if isinstance(text, FrameText):
+            if frames is None or len(frames) != Ftot:
+                raise ValueError(f"forward_many: per-frame text needs the frame id of each of the {Ftot} samples (frames=...)")
+            kvi = text.kv_index([int(f) for f in frames], self.dev)      # one upload per pass, shared by the 16 blocks
         sw = Switches.from_env()                                # per pass: callers flip switches between two passes of one engine
         half = bool(cfg_pair) and sw.cfg_dedup
         Bh = Ftot if half else B                                # samples through the text-free prefix
@@ -468,7 +523,7 @@ class UNetEngine:
                 h = self._resblock(f"down_blocks.{i}.resnets.{j}.", h, Bh if first else B, hh, ww, tproj, sw, rep=2 if first else 1)
                 c = co
                 if i < 3:
-                    h = self._transformer(f"down_blocks.{i}.attentions.{j}.", h, B, Fs, hh, ww, text, sw, pair_half=first)
+                    h = self._transformer(f"down_blocks.{i}.attentions.{j}.", h, B, Fs, hh, ww, text, sw, pair_half=first, kvi=kvi)
                 skips.append((h, c))
             if i < 3:
                 h, hh2, ww2 = o.conv3x3(h, B, hh, ww, c, *w[f"down{i}"], stride=2, pad=1)
@@ -477,7 +532,7 @@ class UNetEngine:
                 sizes.append((hh, ww))
                 skips.append((h, c))
         h = self._resblock("mid_block.resnets.0.", h, B, hh, ww, tproj, sw)
-        h = self._transformer("mid_block.attentions.0.", h, B, Fs, hh, ww, text, sw)
+        h = self._transformer("mid_block.attentions.0.", h, B, Fs, hh, ww, text, sw, kvi=kvi)
         h = self._resblock("mid_block.resnets.1.", h, B, hh, ww, tproj, sw)
         level = 3
         for i, co in enumerate(sd15.BLOCK_OUT[::-1]):
@@ -486,7 +541,7 @@ class UNetEngine:
                 h = self._resblock(f"up_blocks.{i}.resnets.{j}.", h, B, hh, ww, tproj, sw, skip=sk, cskip=cs)
                 del sk
                 if i > 0:
-                    h = self._transformer(f"up_blocks.{i}.attentions.{j}.", h, B, Fs, hh, ww, text, sw)
+                    h = self._transformer(f"up_blocks.{i}.attentions.{j}.", h, B, Fs, hh, ww, text, sw, kvi=kvi)
             if i < 3:
                 level -= 1
                 h, hh2, ww2 = o.conv3x3(h, B, hh, ww, co, *w[f"up{i}"], up=sizes[level])   # nearest upsample fused in the gather
