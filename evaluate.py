@@ -1,4 +1,4 @@
-"""Evaluate a relit video: `python evaluate.py --output_dir <run output directory> [--eval_cost] [--raft PATH] [--clip PATH] [--pick PATH] [--lpips PATH --lpips_lin PATH]` (the reference's evaluate.py).
+"""Evaluate a relit video: `python evaluate.py --output_dir <run output directory> [--eval_cost] [--raft PATH] [--clip PATH] [--pick PATH] [--lpips PATH --lpips_lin PATH] [--light [--light_path JSON]]` (the reference's evaluate.py).
 
 Reads `<output_dir>/config.yaml`, the relit video (output_opt / output, .mp4 or .avi, else output.npy) and the source video (output_gt), computes
 warp-error-ssim on the device (tc_light_amd/evaluate.py: RAFT flows of the source frames, cubic warp, forward-backward mask, SSIM) and writes
@@ -12,9 +12,13 @@ named (`models.clip` or --clip, OpenAI's ViT-B-32.pt or a transformers .safetens
 not computed; with both named result.txt holds the reference's four figures.  frame-lpips, the LPIPS-VGG distance of every relit frame but the last to
 its source frame (the reference's FrameLPIPS, which its evaluate.py ships but never calls), is added when a torchvision VGG-16 state dict is named
 (`models.lpips_vgg` or --lpips) together with LPIPS's linear layers (`models.lpips_lin` or --lpips_lin: the lpips package's weights/v0.1/vgg.pth);
-without them nothing of it is loaded and the output is unchanged.
+without them nothing of it is loaded and the output is unchanged.  --light adds light-contrast and light-follow (this project's own: the mean
+cosine between the light direction fitted to every relit frame and the one the run asked for -- generation.light_path, else the side of
+generation.init_latent or of an fbc generation.bg_source ramp; --light_path "[[0,0],[1,180]]" overrides the config, for runs made without one) and
+writes the per-frame table to `<output_dir>/light_follow.json`; without --light nothing changes.
 """
 import argparse
+import json
 import os
 import sys
 
@@ -36,13 +40,17 @@ def main(argv=None):
     ap.add_argument("--pick_tokenizer", type=str, default=None, help="tokenizer directory for pick-score; default: models.pick_tokenizer, else the snapshot, else the CLIP one")
     ap.add_argument("--lpips", type=str, default=None, help="torchvision VGG-16 state dict (.pth / .safetensors) for frame-lpips; default: models.lpips_vgg; none: no frame-lpips")
     ap.add_argument("--lpips_lin", type=str, default=None, help="LPIPS linear layers (the lpips package's weights/v0.1/vgg.pth); default: models.lpips_lin")
+    ap.add_argument("--light", action="store_true", help="add light-follow / light-contrast and write light_follow.json")
+    ap.add_argument("--light_path", type=str, default=None, help='keyframes [[pos, angle_deg], ...] as JSON, e.g. "[[0,0],[1,180]]"; default: the config\'s '
+                    "generation.light_path, else its init_latent / bg_source side (only with --light)")
     ap.add_argument("--batch", type=int, default=4, help="frame pairs per RAFT / metric batch")
     a = ap.parse_args(argv)
 
     import torch
     from tc_light_amd.config_utils import _wrap
-    from tc_light_amd.evaluate import (clip_frame, clip_settings, clip_text, cost_scores, find_videos, format_results, frame_lpips, lpips_settings,
-                                       not_computed, pick_score, pick_settings, read_video_u8, video_name, warp_ssim)
+    from tc_light_amd.evaluate import (clip_frame, clip_settings, clip_text, cost_scores, find_videos, format_results, frame_lpips, light_follow,
+                                       lpips_settings, not_computed, pick_score, pick_settings, read_video_u8, video_name, warp_ssim)
+    from tc_light_amd.lightfit import wanted_angles
     from tc_light_amd.model_utils import allow_random, load_clip_state, load_lpips_state, load_pick_state, load_raft_state
     from tc_light_amd.raft import RAFTEngine
 
@@ -53,6 +61,10 @@ def main(argv=None):
     models = config.get("models") or {}
     edit_path, source_path = find_videos(a.output_dir)
     edit, source = read_video_u8(edit_path), read_video_u8(source_path)
+    if a.light_path is not None and not a.light:
+        raise ValueError("--light_path is read only with --light")
+    # refused here, before a model is loaded: a config that names no light direction, or keyframes that are not a path
+    wanted = wanted_angles(config, len(edit), None if a.light_path is None else json.loads(a.light_path)) if a.light else None
     print(f"[INFO] edit {edit_path} ({tuple(edit.shape)}), source {source_path} ({tuple(source.shape)})")
     clip_path, tok_dir = clip_settings(models, a.clip, a.clip_tokenizer)
     pick_path, pick_tok_dir = pick_settings(models, a.pick, a.pick_tokenizer)
@@ -97,6 +109,10 @@ def main(argv=None):
         lpips_eng = LPIPSEngine(load_lpips_state(lpips_path, lpips_lin, allow=allow_random(models)), "cuda")
         scores["frame-lpips"], _ = frame_lpips(edit, source, lpips_eng, batch=a.batch)
         del lpips_eng
+    if a.light:
+        scores["light-follow"], scores["light-contrast"], frames = light_follow(edit, source, wanted, "cuda")
+        with open(os.path.join(a.output_dir, "light_follow.json"), "w") as f:
+            json.dump(frames, f, indent=1)
     if a.eval_cost:
         scores.update(cost_scores(config, edit.shape[2], edit.shape[1]))
     name = video_name(config)

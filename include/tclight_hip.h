@@ -522,6 +522,28 @@ int tcl_eval_warp_mask_u8(const void* edit, const float* fut, const float* past,
 size_t tcl_eval_ssim_workspace_bytes(int B, int H, int W);
 int tcl_eval_ssim_u8(const void* x, const void* y, double* out, int B, int H, int W, void* ws, hipStream_t st);
 
+/* ---- light-follow (evaluate.py --light): does the relit light obey its light_path?  This project's own figure (the reference has none); csrc/lightfit.hip.
+ * Definition.  E (relit) and S (source) are u8 [N,3,H,W] of one size.  Per frame and pixel (x, y):
+ *   Ye = ((0.299 R + 0.587 G) + 0.114 B) / 255 of E and Ys likewise of S, in f32, every product, sum and the IEEE division rounded on its own;
+ *   w = 1 when both Ye and Ys lie in [2/255, 253/255] (the f32 constants), else 0 -- clipped pixels are dropped;
+ *   r = log((Ye + 1/255) / (Ys + 1/255)),  u = (2x + 1)/W - 1,  v = (2y + 1)/H - 1;
+ *   sums[n] = (Sw, Swu, Swv, Swuu, Swuv, Swvv, Swr, Swru, Swrv, Swrr).
+ *   The host solves the 3x3 normal equations in f64 for r ~ a + gx u + gy v.  Angle, in light_path's convention (the side the light comes FROM: 0
+ *   left, 90 top, 180 right, 270 bottom): atan2(-gy, -gx) in degrees mod 360; contrast: hypot(gx, gy); R^2 from Swrr.  A frame has no estimate when
+ *   Sw < 3, the system is singular or the contrast is 0; it then counts with cosine 0.  light-follow = mean over frames of cos(angle - wanted angle),
+ *   light-contrast = the mean contrast.
+ * tcl_light_fit_u8: the f32 sequence per pixel, without fma contraction: a = Ye + fl(1/255); b = Ys + fl(1/255); r = logf(a / b);
+ *   u = fl(float(2x + 1 - W) * fl(1 / float(W))), v likewise with y, H; the terms w, wu, wv, (wu)(wu), (wu)(wv), (wv)(wv), wr, (wr)(wu), (wr)(wv),
+ *   (wr)(wr).  Summation order: a frame is cut into spans of 16384 consecutive pixels, one block of 256 threads each; thread t adds the terms of the
+ *   16 consecutive pixels from span*16384 + j*4096 + t*16, j = 0..3, to f32 accumulators in pixel order (64 pixels per thread, never more); the
+ *   accumulators widen to f64; a wave adds its 64 lanes by a xor butterfly (offsets 32 .. 1); the block adds its four waves in order and stores its
+ *   partial to ws; a finish launch adds a frame's partials in span order into sums [N,10] f64.  No atomics: results are bit-identical from run to
+ *   run and depend on N, H, W alone (16 B loads when H*W % 16 == 0 and E, S are 16 B aligned, byte loads otherwise: the same values, the same order).
+ *   ws: tcl_light_fit_workspace_bytes(N, H, W) bytes, 8 B aligned (0 for a shape that is refused).  N outside 1..65535, H or W <= 0, H*W >= 2^31 or a
+ *   null pointer return TCL_EINVAL with nothing launched or written. */
+size_t tcl_light_fit_workspace_bytes(int N, int H, int W);
+int tcl_light_fit_u8(const void* E, const void* S, int N, int H, int W, double* sums, void* ws, hipStream_t st);
+
 /* ---- clip-frame / clip-text (evaluate.py:39-49,119: clip.load("ViT-B/32"); utils/evaluation/eval_utils.py:129-161 clip_text / clip_frame); csrc/clip.hip.
  *   The model is OpenAI CLIP (clip/model.py: VisionTransformer, Transformer / ResidualAttentionBlock, QuickGELU, CLIP.encode_image / encode_text); its
  *   Linears and LayerNorms run on tcl_gemm_f16 / tcl_layernorm_f16, the entry points below are the rest.

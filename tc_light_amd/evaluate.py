@@ -236,6 +236,26 @@ def frame_lpips(edit_u8, source_u8, engine, batch=4):
     return float(np.mean(per)), per
 
 
+# ---- light-follow
+def light_follow(edit_u8, source_u8, wanted, device="cuda"):
+    """edit_u8 / source_u8 uint8 [N,H,W,3] (numpy or tensors), wanted: the N wanted angles in degrees (lightfit.wanted_angles) ->
+    (light-follow, light-contrast, per-frame list of dicts; lightfit.figures).  Source frames of another size are resized to the edit size first, as
+    for the other figures; the sums run on `device` (tcl_light_fit_u8), the 3x3 solves on the host in f64."""
+    from . import lightfit
+    edit, src = clip.nhwc_u8(edit_u8), clip.nhwc_u8(source_u8)
+    N, H, W = edit.shape[:3]
+    if N < 1 or len(src) < N:
+        raise ValueError(f"light-follow needs at least 1 edit frame and as many source frames, got {N} / {len(src)}")
+    if len(wanted) != N:
+        raise ValueError(f"light-follow: {len(wanted)} wanted angles for {N} frames")
+    src = src[:N]
+    if tuple(src.shape[1:3]) != (H, W):
+        src = resize_like(src, H, W)
+    e = edit.to(device).permute(0, 3, 1, 2).contiguous()
+    s = src.to(device).permute(0, 3, 1, 2).contiguous()
+    return lightfit.figures(lightfit.light_sums(e, s).cpu().numpy(), wanted)
+
+
 # ---- files
 def find_videos(output_dir):
     """-> (edit path, source path) in the reference's order: output_opt, then output, each as .mp4 then .avi, then output.npy for the edit;
