@@ -362,6 +362,20 @@ int tcl_attention_kvindex_f16(const void* q, int ldq, long qbs, const void* k, i
  * t == 0 copies the f16 bits of keys[k0], t == 1 those of keys[k1] (the formula would turn -0 into +0, and a + 1 (b - a) need not be b).
  * t is computed by the caller in f64 and rounded to f32 once.  16 B accesses when LD % 8 == 0 and out / keys are 16 B aligned.  F <= 65535. */
 int tcl_text_lerp_f16(void* out, const void* keys, int n_keys, const int* tab, const int* h_tab, int F, long LD, hipStream_t st);
+/* generation.ip_adapter: IP-Adapter's decoupled image cross-attention (Ye et al. 2023, eq. 5), added in place into the output of the text
+ * cross-attention (csrc/ip_attn.hip):  a += ip_scale * softmax(q K_ip^T * qk_scale) V_ip  per (sample, head).
+ * q [B, Tq, H*d] f16 (row stride ldq, sample stride qbs, in halves): the UN-scaled query the text attention consumed.  kv_ip [B / kv_div, Tip, 2*H*d]
+ * f16, K | V per token; sample b reads entry b / kv_div.  a [B, Tq, H*d] f16 (lda, abs_): read and written.  1 <= Tip <= 16, d in {40, 80, 160},
+ * H <= 8 a power of two, B % kv_div == 0, strides multiples of 8 halves and the three bases 16 B aligned: anything else returns TCL_EINVAL before a
+ * launch.  ip_scale == 0 returns 0 without a launch.
+ * Per (row, head), every operation rounded to f32 on its own (no fma contraction), with q_i, k_ti, v_ti, a_i the f16 operands widened to f32:
+ *   s_t = 0;  for i = 0 .. d-1 in index order:  s_t = s_t + q_i * k_ti;      s_t = s_t * qk_scale          (t = 0 .. Tip-1)
+ *   m = max_t s_t;   e_t = expf(s_t - m);   l = e_0 + e_1 + ... in index order;   w_t = e_t / l   (one division per weight)
+ *   o_i = 0;  for t = 0 .. Tip-1 in token order:  o_i = o_i + w_t * v_ti
+ *   term = ip_scale * o_i;   a_i = f16(a_i + term)   -- one rounding to f16; a term of +-0 leaves the bits of a_i as they are (V_ip = 0 changes nothing).
+ * Deterministic: a thread per (row, head), no atomics.  6 B of device memory traffic per element of [B*Tq, H*d]. */
+int tcl_attention_ip_add_f16(const void* q, int ldq, long qbs, const void* kv_ip, void* a, int lda, long abs_, int B, int H, int Tq, int Tip, int d,
+                             float qk_scale, float ip_scale, int kv_div, hipStream_t st);
 
 /* ---- VidToMe token merging (utils/VidToMe/vidtome/merge.py, patch.py:14-91); int32 maps live on the device ---- */
 /* metric / metric.norm(dim=-1) with f16 rounding of the norm and the quotient (merge.py:84, :386). */

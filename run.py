@@ -10,6 +10,8 @@ side the light comes FROM: 0 left, 90 top, 180 right, 270 bottom), the img2img s
 become normal.npy / normal.mp4 (per-frame surface normals), relit_<side>.npy and the ambient video as output.*; no stage 1 / 2.
 [--prompt_sweep PROMPT_A PROMPT_B] (generation.prompt_path: keyframes [[pos, "prompt"], ...]): a prompt that changes over the clip -- every frame's text
 conditioning of the xy passes is the blend of its two neighbouring keyframes' embeddings; -p / generation.prompt still names the run.
+[--ip_image PATH] [--ip_scale S] (generation.ip_adapter: {image, scale, path}): IP-Adapter -- the relight is steered towards a reference photograph;
+its CLIP ViT-H/14 embedding (models.image_encoder) becomes 4 image tokens every text cross-attention of the xy passes also attends to (models.ip_adapter).
 data.scene_type picks the parser (generate.py:84-95): video (VideoDataParser) or sceneflow (SceneFlowDataParser: ground-truth depth, poses and
 flows -> voxelised Unique Video Tensor ids); carla and interiornet are not built.
 
@@ -27,11 +29,11 @@ import sys
 import numpy as np
 import torch
 
-from tc_light_amd.config_utils import Config, load_config, save_config
+from tc_light_amd.config_utils import DEFAULTS as CONFIG_DEFAULTS, Config, load_config, save_config
 from tc_light_amd.dataparser import VideoDataParser, get_frame_ids, save_loss_curve, save_video
 from tc_light_amd.generate import DEFAULTS, Generator
-from tc_light_amd.hostlogic import (check_fbc, check_highres, check_highres_tokens, check_init, check_light_path, check_normal, check_prompt_path,
-                                    cond_channels, fbc_background_per_frame, highres_size, light_angles, prompt_table)
+from tc_light_amd.hostlogic import (check_fbc, check_highres, check_highres_tokens, check_init, check_ip_adapter, check_light_path, check_normal,
+                                    check_prompt_path, cond_channels, fbc_background_per_frame, highres_size, light_angles, prompt_table)
 from tc_light_amd.model_utils import allow_random, init_iclight
 from tc_light_amd.parallel import Dist
 from tc_light_amd.text import encode_prompt_pair, encode_prompt_set
@@ -120,6 +122,12 @@ def main(argv=None):
     if config.generation.prompt_path is not None:
         print("[INFO] generation.prompt_path: the xy passes are conditioned on the keyframe prompts, blended per frame; generation.prompt names the "
               "run and is recorded in config.yaml, it conditions nothing.  negative_prompt, prompt_t and negative_prompt_t are used as they are.")
+    # IP-Adapter (generation.ip_adapter; --ip_image / --ip_scale): a malformed block, a missing image, generation.normal beside it and missing weight
+    # files (models.ip_adapter, models.image_encoder; unless allow_random) are refused here, before any model is loaded
+    ip_block = check_ip_adapter(config.generation.get("ip_adapter", CONFIG_DEFAULTS["generation"]["ip_adapter"]), config.generation.normal,
+                                config.get("models") or {}, allow_random(config.get("models") or {}))
+    if ip_block is not None:
+        config.generation.ip_adapter = Config({k: ip_block[k] for k in ("image", "scale", "path")})      # what config.yaml records
     if light and fbc:
         print("[INFO] generation.light_path: the per-frame ramps are the backgrounds; generation.background_image_path is not consulted.")
     if fbc and not normal and not light and config.generation.bg_source in ("upload", "upload_flip") and not config.generation.get("background_image_path"):
@@ -206,7 +214,11 @@ def main(argv=None):
         bg_per_frame = fbc_background_per_frame(background.shape[0], len(frame_ids), g.bg_source)      # the same answer on every rank
         if bg_per_frame and world > 1:
             background = background[lo:hi]
-    gen = Generator(pipe.unet, pipe.vae, cfg, dist=d, scheduler=scheduler, rmbg=rmbg)
+    image_prompt = None
+    if ip_block is not None:      # on every rank, once per run: the image tower is built, run on the one image and freed before the UNet loop
+        from tc_light_amd import ip_adapter
+        image_prompt = ip_adapter.build(ip_block, dev, allow=ok_random)
+    gen = Generator(pipe.unet, pipe.vae, cfg, dist=d, scheduler=scheduler, rmbg=rmbg, image_prompt=image_prompt)
     for name, prompt in g.prompt.items():
         if g.prompt_path is not None:      # every distinct keyframe prompt is encoded once; the rows of this rank's frames are blended from them
             uncond, keys = encode_prompt_set(prompt_table(g.prompt_path, len(frame_ids))[0], g.negative_prompt, dev, models.get("text_encoder"),

@@ -25,8 +25,8 @@ last_hidden_state, the prompt embeddings of SD-1.5 (`SD15_TEXT`, the text tower 
 Structure: `_tower_to_hf` / `_tower_from_hf` are the per-layer renaming, one per direction, under the four state-dict maps; `_prompt_ids` is the
 tokenizer front of `tokenize` and `tokenize_truncated`; `_check_tower` holds the rules on heads, activation and eps for `_Tower`, `pick_options` and
 `text_options`.  `_Blocks` is the launches of a block sequence, built from (device, act, eps).  `_TextTower` is a `_Blocks` with the token table,
-positional rows, ln_final and the text `_Tower`: CLIPTextEngine is one plus `hidden_states`; CLIPEngine, a `_Blocks` with the image side, holds one
-for `encode_text`.  tests/test_clip_trace_cpu.py pins the launches of both.
+positional rows, ln_final and the text `_Tower`: CLIPTextEngine is one plus `hidden_states`.  `_ImageTower` is a `_Blocks` with the image side
+(`encode_image`): CLIPVisionEngine is one alone (IP-Adapter's image encoder); CLIPEngine is one that also holds a `_TextTower` for `encode_text`.  tests/test_clip_trace_cpu.py pins the launches of both.
 """
 import hashlib
 import math
@@ -405,19 +405,13 @@ def nhwc_u8(frames):
     return t
 
 
-class CLIPEngine(_Blocks):
-    """clip/model.py's CLIP (VisionTransformer image tower) in inference on the device.  The keyword arguments are what the tensors of a
-    transformers.CLIPModel checkpoint do not say (its config.json does): the head counts (None: width // 64, OpenAI's rule), the MLP's activation
-    ("quick_gelu", or "gelu" = erf, in c_fc's GEMM epilogue) and the centre-crop rule of the preprocessing ("round": clip's _transform, "floor":
-    transformers' image processor).  The defaults are OpenAI's CLIP."""
+class _ImageTower(_Blocks):
+    """The image side both engines derive from: the visual `_Tower`, the patch embedding, class / positional rows, ln_pre / ln_post and the projection,
+    with `preprocess`, `encode_patches` and `encode_image`.  `sd`: f32 tensors under OpenAI's `visual.*` names."""
 
-    def __init__(self, state_dict, device, vision_heads=None, text_heads=None, act="quick_gelu", crop="round"):
+    def __init__(self, sd, device, vision_heads, act, crop):
         if crop not in CROPS:
             raise ValueError(f"crop must be one of {sorted(CROPS)}, got {crop!r}")
-        missing =[k for k in ("visual.conv1.weight", "visual.proj", "token_embedding.weight", "text_projection", "ln_final.weight") if k not in state_dict]
-        if missing:
-            raise KeyError(f"CLIP state dict lacks {missing} (OpenAI key names; a transformers checkpoint goes through from_hf_state)")
-        sd = {k: v.float() for k, v in state_dict.items() if torch.is_tensor(v)}
         self.visual = _Tower(sd, "visual.transformer.resblocks.", device, vision_heads, act)
         super().__init__(device, act, 1e-5)
         self.crop, d = crop, self.dev
@@ -434,15 +428,11 @@ class CLIPEngine(_Blocks):
         self.ln_pre = (_h16(sd["visual.ln_pre.weight"], d), _h16(sd["visual.ln_pre.bias"], d))
         self.ln_post = (_h16(sd["visual.ln_post.weight"], d), _h16(sd["visual.ln_post.bias"], d))
         self.vproj = _h16(sd["visual.proj"].t(), d)                                                 # [embed, width]
-        self.ttower = _TextTower(sd, d, text_heads, act, self.eps)
-        self.text, self.twidth, self.context = self.ttower.tower, self.ttower.width, self.ttower.context
-        self.tproj = _h16(sd["text_projection"].t(), d)
         self.embed_dim = self.vproj.shape[0]
-        self.logit_scale = float(sd["logit_scale"]) if "logit_scale" in sd else None               # the log, as stored (CLIP.logit_scale)
         if self.vwidth % 64:
             raise ValueError(f"vision width {self.vwidth} must be a multiple of 64 (tcl_gemm_f16's K)")
 
-    # ---- the two encoders
+    # ---- the image encoder
     def preprocess(self, frames_u8, want_crop=False):
         """frames uint8 [N,H,W,3] (device) -> (patch rows [N*grid^2, ldp] f16 with ldp = 3*P*P rounded up to a multiple of 64 and the columns past
         3*P*P zero, the uint8 crop [N,side,side,3] or None)."""
@@ -478,6 +468,27 @@ class CLIPEngine(_Blocks):
             out.append(self.encode_patches(patches, f.shape[0]))
         return torch.cat(out)
 
+
+class CLIPEngine(_ImageTower):
+    """clip/model.py's CLIP (VisionTransformer image tower) in inference on the device.  The keyword arguments are what the tensors of a
+    transformers.CLIPModel checkpoint do not say (its config.json does): the head counts (None: width // 64, OpenAI's rule), the MLP's activation
+    ("quick_gelu", or "gelu" = erf, in c_fc's GEMM epilogue) and the centre-crop rule of the preprocessing ("round": clip's _transform, "floor":
+    transformers' image processor).  The defaults are OpenAI's CLIP."""
+
+    def __init__(self, state_dict, device, vision_heads=None, text_heads=None, act="quick_gelu", crop="round"):
+        if crop not in CROPS:
+            raise ValueError(f"crop must be one of {sorted(CROPS)}, got {crop!r}")
+        missing =[k for k in ("visual.conv1.weight", "visual.proj", "token_embedding.weight", "text_projection", "ln_final.weight") if k not in state_dict]
+        if missing:
+            raise KeyError(f"CLIP state dict lacks {missing} (OpenAI key names; a transformers checkpoint goes through from_hf_state)")
+        sd = {k: v.float() for k, v in state_dict.items() if torch.is_tensor(v)}
+        super().__init__(sd, device, vision_heads, act, crop)
+        d = self.dev
+        self.ttower = _TextTower(sd, d, text_heads, act, self.eps)
+        self.text, self.twidth, self.context = self.ttower.tower, self.ttower.width, self.ttower.context
+        self.tproj = _h16(sd["text_projection"].t(), d)
+        self.logit_scale = float(sd["logit_scale"]) if "logit_scale" in sd else None               # the log, as stored (CLIP.logit_scale)
+
     @torch.no_grad()
     def encode_text(self, ids):
         """CLIP.encode_text: ids int [B, T], 1 <= T <= context (clip.tokenize's padded layout, or tokenize_truncated's unpadded row, which uses the
@@ -488,6 +499,61 @@ class CLIPEngine(_Blocks):
         eot = ids.to(self.dev).argmax(-1)
         c = self._ln(x.view(B, T, W)[torch.arange(B, device=self.dev), eot].contiguous(), self.ttower.ln_final, B, W)
         return self._gemm(c, self.tproj, None, None, B).float()
+
+
+VISUAL_KEYS = ("visual.conv1.weight", "visual.proj", "visual.class_embedding", "visual.positional_embedding")
+
+
+def visual_state(sd):
+    """The `visual.*` entries of a state dict in OpenAI's names: what CLIPVisionEngine reads of a whole CLIP (a PickScore snapshot)."""
+    return {k: v for k, v in sd.items() if k.startswith("visual.")}
+
+
+def from_hf_vision_state(sd):
+    """`transformers.CLIPVisionModelWithProjection` names (vision_model.*, visual_projection.weight: the image_encoder of IP-Adapter) -> the
+    `visual.*` part of OpenAI's names; from_hf_state's image half."""
+    missing = [hf for oa, hf in _HF_TOP if oa.startswith("visual.") and hf not in sd] + [k for k in ("visual_projection.weight",) if k not in sd]
+    if missing:
+        raise KeyError(f"image encoder state dict lacks {missing[:3]} (transformers.CLIPVisionModelWithProjection's key names)")
+    out = {oa: sd[hf] for oa, hf in _HF_TOP if oa.startswith("visual.")}
+    out["visual.proj"] = sd["visual_projection.weight"].t().contiguous()
+    oa, hf = _HF_TOWERS[0]
+    _tower_from_hf(out, sd.__getitem__, _layers(sd, hf), oa, hf)
+    return out
+
+
+class CLIPVisionEngine(_ImageTower):
+    """The image tower of CLIPEngine alone (`transformers.CLIPVisionModelWithProjection`: `encode_image` returns its projected, un-normalised
+    image_embeds): what IP-Adapter conditions on.  The state dict holds the `visual.*` keys in OpenAI's names; a text tower is neither needed nor read."""
+
+    def __init__(self, state_dict, device, vision_heads=None, act="quick_gelu", crop="round"):
+        missing = [k for k in VISUAL_KEYS if k not in state_dict]
+        if missing:
+            raise KeyError(f"CLIP image tower state dict lacks {missing} (OpenAI key names; a transformers checkpoint goes through from_hf_vision_state)")
+        super().__init__({k: v.float() for k, v in visual_state(state_dict).items() if torch.is_tensor(v)}, device, vision_heads, act, crop)
+
+
+def vision_options(config=None, vision_width=None, patch=None):
+    """CLIPVisionEngine's keyword arguments for the CLIP ViT-H/14 image tower: from the dictionary of a config.json -- a CLIPVisionConfig (the fields at
+    the top level) or a CLIPConfig (under vision_config: a PickScore snapshot) -- else PICKSCORE_V1's.  The rules, and what is refused, are
+    pick_options' for the vision tower."""
+    A, D = PICKSCORE_V1, _HF_DEFAULTS
+    vc = to_hf_config(A)["vision_config"] if config is None else (config.get("vision_config") or config)
+    heads, act = vc.get("num_attention_heads", D["num_attention_heads"][0]), vc.get("hidden_act", D["hidden_act"])
+    _check_tower(vision_width or A["vision_width"], heads, act, vc.get("layer_norm_eps", D["layer_norm_eps"]), (64, 80), _HF_FIELDS, " (vision)")
+    psz = vc.get("patch_size", D["patch_size"])
+    if patch is not None and int(psz) != int(patch):
+        raise ValueError(f"patch_size {psz!r} of the config, but the checkpoint's patch embedding is {patch} x {patch}")
+    return dict(vision_heads=int(heads), act=act, crop="floor")
+
+
+def vision_engine(state, device, config=None):
+    """The CLIPVisionEngine of IP-Adapter-SD1.5's image encoder (CLIP ViT-H/14) from a state dict in OpenAI's names (model_utils.load_image_encoder_state:
+    a vision snapshot's, or the visual.* part of a PickScore one) and the snapshot's config.json dictionary: the tower pick_engine builds, alone."""
+    if "visual.conv1.weight" not in state:
+        raise KeyError("image encoder state dict lacks visual.conv1.weight (OpenAI key names; see from_hf_vision_state)")
+    w = state["visual.conv1.weight"]
+    return CLIPVisionEngine(state, device, **vision_options(config, w.shape[0], w.shape[-1]))
 
 
 class CLIPTextEngine(_TextTower):

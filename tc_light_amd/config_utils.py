@@ -8,6 +8,11 @@ from datetime import datetime
 import yaml
 
 
+# keys a YAML may leave out and that are not generation.* / post_opt.* settings of the Generator (those: generate.DEFAULTS)
+DEFAULTS = dict(generation=dict(ip_adapter=None),                       # IP-Adapter off; else {image, scale, path} (hostlogic.check_ip_adapter)
+                models=dict(ip_adapter="", image_encoder=""))           # ip-adapter_sd15.safetensors / .bin; a CLIP ViT-H/14 vision snapshot directory
+
+
 class Config(dict):
     """dict with attribute access (the subset of OmegaConf the pipeline uses)."""
 
@@ -103,8 +108,19 @@ def load_config(argv=None, print_config=True):
     ap.add_argument("--prompt_sweep", type=str, nargs=2, metavar=("PROMPT_A", "PROMPT_B"), default=None,
                     help="blend the text conditioning from PROMPT_A at the first frame to PROMPT_B at the last: generation.prompt_path "
                     "[[0, PROMPT_A], [1, PROMPT_B]]; -p / generation.prompt still names the run, for a fast usage")
+    # IP-Adapter: relight towards a reference image (generation.ip_adapter, generate.py DEFAULTS)
+    ap.add_argument("--ip_image", type=str, default=None, help="a reference image the relight is steered towards through IP-Adapter "
+                    "(models.ip_adapter, models.image_encoder): generation.ip_adapter.image, for a fast usage")
+    ap.add_argument("--ip_scale", type=float, default=None, help="weight of the image attention in [0, 2] (generation.ip_adapter.scale), for a fast usage")
     a = ap.parse_args(argv)
     cfg = load_yaml_chain(a.config, a.base_config)
+    if a.ip_image is not None or a.ip_scale is not None:
+        block = Config(cfg.generation.get("ip_adapter") or {})
+        if a.ip_image is not None:
+            block["image"] = a.ip_image
+        if a.ip_scale is not None:
+            block["scale"] = a.ip_scale
+        cfg.generation.ip_adapter = block
     if a.prompt_sweep is not None:
         cfg.generation.prompt_path = [[0.0, a.prompt_sweep[0]], [1.0, a.prompt_sweep[1]]]
     if a.light_sweep is not None:

@@ -89,6 +89,12 @@ DEFAULTS = dict(  # configs/tclight_default.yaml (generation / post_opt sections
     #   is one for all, the yt passes keep prompt_t.  generation.prompt is then only the run's name.  None (default): nothing of it is consulted and
     #   every path is what it was.  With it the K / V panels of the distinct rows stay resident (UNetEngine.text_rows_bytes: 7.6 MB per row over
     #   the 16 blocks, 2.3 GB for 300 distinct rows); the token budget below is taken from what is left.
+    ip_adapter=None,
+    # ^ IP-Adapter: relight towards a reference image.  {image: <path>, scale: <float in [0, 2]>, path: <adapter file, default models.ip_adapter>}
+    #   (HL.check_ip_adapter); the image goes once through the CLIP ViT-H/14 image tower (models.image_encoder) and the adapter's projection to 4
+    #   tokens, and every text cross-attention of the xy passes -- the highres refine included -- adds scale * Attention(q, K_ip, V_ip)
+    #   (tcl_attention_ip_add_f16); the yt passes do not (a y-t slice is not an image the photograph describes).  The Generator takes the tokens as
+    #   image_prompt= (ip_adapter.build).  None (default): nothing of it is consulted and every path is what it was.
     max_tokens_per_pass=None)
     # ^ None: TCL_MAX_TOKENS_PER_PASS (read when the Generator is built), else min(16 M, 80 % of the device's free memory / 10.5 KB) -- a block-major pass
     #   peaks at ~10.4 KB of activations per level-0 token (90 GB for the 8.64 M tokens of 300 frames at 1280x720): a 288 GB MI355X gets the 16 M
@@ -116,7 +122,7 @@ def default_max_tokens_per_pass(unet, dev, reserve=0):
 
 
 class Generator:
-    def __init__(self, unet, vae, config=None, dist=None, scheduler=None, rmbg=None):
+    def __init__(self, unet, vae, config=None, dist=None, scheduler=None, rmbg=None, image_prompt=None):
         cfg = dict(DEFAULTS)
         cfg.update(config or {})
         self.cfg = SimpleNamespace(**cfg)
@@ -143,6 +149,11 @@ class Generator:
         self.fbc = c.iclight_model == "fbc"
         self.normal_sides = HL.check_normal(c.normal, c.iclight_model, c.fbc_matting, c.apply_opt)      # () unless generation.normal
         c.prompt_path = HL.check_prompt_path(c.prompt_path, c.normal, c.highres_scale)
+        if (c.ip_adapter is not None) != (image_prompt is not None):
+            raise ValueError("generation.ip_adapter: the Generator takes the block's unet.ImagePrompt as image_prompt= (ip_adapter.build), and only then")
+        if image_prompt is not None and c.normal:
+            raise ValueError("generation.ip_adapter together with generation.normal is not supported")
+        self.ip = image_prompt             # handed to every xy pass; the yt passes run without it
         self.bg_per_frame = None           # __call__'s background_per_frame: whether the fbc background is one frame per frame (None: by its length)
         cin = getattr(self.unet, "w", {}).get("conv_in", (None, None, None))[2]      # a stand-in engine may carry no weights
         if cin is not None and cin != 4 + HL.cond_channels(c.iclight_model):
@@ -542,12 +553,14 @@ class Generator:
             groups.append(cur)
         return groups
 
-    def _run_groups(self, groups, Hh, Ww, t, text, pack, unpack):
+    def _run_groups(self, groups, Hh, Ww, t, text, pack, unpack, ip=None):
         """One block-major UNet pass per group of chunks.  pack(grp) -> (xin, idx, n); unpack(eps, idx, n)."""
         for grp in groups:
             xin, idx, n = pack(grp)
             # per-frame text (prompt_path, xy passes only): the UNet needs to know which frame each sample is
             kw = dict(frames=[f for c in grp for f in c]) if isinstance(text, FrameText) else {}
+            if ip is not None:             # generation.ip_adapter (xy passes only)
+                kw["ip"] = ip
             eps = self.unet.forward_many(xin, [len(c) for c in grp], Hh, Ww, t, text, cfg_pair=True, **kw)     # the pack kernel wrote both halves
             unpack(eps, idx, n)
 
@@ -571,7 +584,7 @@ class Generator:
         def unpack(eps, idx, n):
             L.tcl_unpack_cfg_f16(eps, idx, n, 0, 0, 0, self.h, self.w, float(self.cfg.guidance_scale), 0, 1.0, 0, noises, stream())
 
-        self._run_groups(self._groups(chunks, self.h * self.w), self.h, self.w, t, text, pack, unpack)
+        self._run_groups(self._groups(chunks, self.h * self.w), self.h, self.w, t, text, pack, unpack, ip=self.ip)
 
     def _unet_yt(self, x_full, cc_full, items, nt_full, text_t, t):
         """pred_noise on the yt chunks of one frame window: 'n c h w -> w c n h' (generate.py:265-273); items share (start, length)."""
@@ -750,7 +763,7 @@ class Generator:
         self.timing = dict(encode=t1 - t0, denoise=t2a - t1, decode=t3 - t2, stage1=t4 - t3, stage2=t5 - t4, total=t5 - t0)
         info = dict(timing=self.timing, losses_exposure=losses1, losses_unique=losses2, total_time=t5 - t0,
                     sec_per_frame=(t5 - t0) / self.n_total, total_number_of_frames=self.n_total, init_latent=c.init_latent,
-                    iclight_model=c.iclight_model,
+                    iclight_model=c.iclight_model, ip_adapter=c.ip_adapter,
                     init_strength=c.init_strength, scheduler_steps=self.schedule[0], steps_executed=self.schedule[2],
                     max_memory_allocated=torch.cuda.max_memory_allocated(self.dev) / 1024.0 ** 2)
         if self.highres:                   # decode -> u8 -> resize -> encode -> second denoise, between `denoise` and `decode`

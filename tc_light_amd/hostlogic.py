@@ -353,7 +353,47 @@ def prompt_table(path, n_total, lo=0, hi=None):
     return prompts, rows, index
 
 
-TOME_MAX_SRC_TOKENS = 64 * 1024        # tcl_tome_match_f16 / _affine_f16: source tokens of one match (csrc/merge.hip)
+IP_SCALE_DEFAULT = 0.6                 # generation.ip_adapter.scale when the block (or --ip_image alone) gives none
+_IP_KEYS = ("image", "scale", "path")
+
+
+def check_ip_adapter(block, normal=False, models=None, allow_random=False):
+    """generation.ip_adapter: None (off: nothing else is looked at) or {image: <path>, scale: <float in [0, 2]>, path: <adapter file>} ->
+    {image, scale, path, image_encoder} with the defaults filled in (scale IP_SCALE_DEFAULT, path models.ip_adapter).  run.py raises what is
+    wrong before a model is loaded: a malformed block, a scale outside [0, 2] or an image that is no file is a ValueError naming the key; together with
+    generation.normal a ValueError naming both keys (the four relights of a normal are lit by the ramps alone); a missing adapter file or
+    models.image_encoder a FileNotFoundError, unless `allow_random` (models.allow_random / TCL_ALLOW_RANDOM_WEIGHTS=1) asks for seeded stand-ins."""
+    import os
+    if block is None:
+        return None
+    if not isinstance(block, dict) or not block or any(k not in _IP_KEYS for k in block):
+        raise ValueError(f"generation.ip_adapter {block!r}: expected null or {{image: <path>, scale: <float in [0, 2]>, path: <adapter file>}}")
+    image, scale, path = block.get("image"), block.get("scale", IP_SCALE_DEFAULT), block.get("path")
+    if not isinstance(image, str) or not image:
+        raise ValueError(f"generation.ip_adapter.image {image!r}: expected the path of the reference image")
+    if not _is_number(scale) or not math.isfinite(scale) or not 0.0 <= float(scale) <= 2.0:
+        raise ValueError(f"generation.ip_adapter.scale {scale!r}: expected a number in [0, 2]")
+    if path is not None and (not isinstance(path, str) or not path):
+        raise ValueError(f"generation.ip_adapter.path {path!r}: expected null (models.ip_adapter) or the path of the adapter file")
+    if normal:
+        raise ValueError("generation.ip_adapter together with generation.normal is not supported: the normal is computed from four relights that "
+                         "differ in their ramp alone")
+    if not os.path.isfile(image):
+        raise ValueError(f"generation.ip_adapter.image {image!r}: no such file")
+    models = models or {}
+    path = path if path is not None else models.get("ip_adapter")
+    encoder = models.get("image_encoder")
+    if not allow_random:
+        if not (path and os.path.isfile(path)):
+            raise FileNotFoundError(f"IP-Adapter weights not found at {path!r} (generation.ip_adapter.path / models.ip_adapter: "
+                                    "ip-adapter_sd15.safetensors or .bin); models.allow_random / TCL_ALLOW_RANDOM_WEIGHTS=1 stands seeded tensors in")
+        if not (encoder and os.path.exists(encoder)):
+            raise FileNotFoundError(f"CLIP ViT-H/14 image encoder not found at {encoder!r} (models.image_encoder: a snapshot with config.json and "
+                                    "model.safetensors); models.allow_random / TCL_ALLOW_RANDOM_WEIGHTS=1 stands seeded tensors in")
+    return dict(image=image, scale=float(scale), path=path, image_encoder=encoder)
+
+
+TOME_MAX_SRC_TOKENS = 64 * 1024       # tcl_tome_match_f16 / _affine_f16: source tokens of one match (csrc/merge.hip)
 
 
 def check_highres_tokens(H2, W2, chunk_size):

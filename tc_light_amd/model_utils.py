@@ -187,6 +187,28 @@ def load_pick_state(path=None, seed=7, allow=False):
     return clip.from_hf_state(raw, consume=True), config
 
 
+def load_image_encoder_state(path=None, seed=9, allow=False):
+    """models.image_encoder, the CLIP ViT-H/14 image tower IP-Adapter-SD1.5 was trained on -> (the `visual.*` state dict in OpenAI's key names, the
+    config.json dictionary or None).  `path` is a transformers.CLIPVisionModelWithProjection snapshot (config.json + model.safetensors or
+    pytorch_model.bin) or one such file; a snapshot whose config.json is a CLIPConfig (vision_config / text_config: PickScore_v1, the same tower beside
+    a text tower) goes through load_pick_state and its image half is kept."""
+    from . import clip
+    if not (path and os.path.exists(path)):
+        _missing("CLIP ViT-H/14 image encoder", path, allow)
+        shapes = {k: s for k, s in clip.clip_param_shapes(**clip.arch_shapes(clip.PICKSCORE_V1)).items() if k.startswith("visual.")}
+        return clip._seeded(shapes, seed), None
+    config, file = None, path
+    if os.path.isdir(path):
+        config = _read_config(path)
+        if (config or {}).get("vision_config") is not None or os.path.isfile(os.path.join(path, "model.safetensors.index.json")):
+            sd, config = load_pick_state(path)
+            return clip.visual_state(sd), config
+        file = next((p for p in (os.path.join(path, n) for n in ("model.safetensors", "pytorch_model.bin")) if os.path.isfile(p)), None)
+        if file is None:
+            raise FileNotFoundError(f"image encoder snapshot {path!r} holds neither model.safetensors nor pytorch_model.bin (models.image_encoder)")
+    return clip.from_hf_vision_state(_read_state(file)), config
+
+
 def load_lpips_state(vgg_path=None, lin_path=None, allow=False, seed=8):
     """The two files lpips.LPIPS(net='vgg') reads (eval_utils.py:371): `vgg_path`, a torchvision vgg16 state dict (`features.N.weight / .bias`; its
     classifier is ignored), and `lin_path`, the lpips package's weights/v0.1/vgg.pth (`lin{k}.model.1.weight`); each a .pth or a .safetensors.  ->

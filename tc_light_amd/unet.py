@@ -80,6 +80,25 @@ class KVIndex(NamedTuple):
     rows: int              # entries of the K / V panels
 
 
+class ImagePrompt:
+    """generation.ip_adapter: the image conditioning of IP-Adapter (decoupled cross-attention beside every text cross-attention).  tokens [2, Tip, 768]
+    f16: entry 0 the tokens of the zero image embedding (the unconditional half), entry 1 those of the reference image; weights {transformer block
+    prefix: [2C, 768] f16 = to_k_ip ; to_v_ip of that block}; scale in [0, 2].  Every block projects the tokens to K_ip | V_ip once per run
+    (UNetEngine._ip_kv); `tcl_attention_ip_add_f16` then adds scale * softmax(q K_ip^T) V_ip to the text attention's output."""
+
+    def __init__(self, tokens, weights, scale):
+        if tokens.dim() != 3 or tokens.shape[0] != 2 or not 1 <= tokens.shape[1] <= 16 or tokens.dtype != H16:
+            raise ValueError(f"ImagePrompt: tokens {tuple(tokens.shape)} {tokens.dtype}, expected [2, 1..16, D] f16 (zero image, reference image)")
+        self.tokens, self.weights, self.scale = tokens.contiguous(), weights, float(scale)
+        self.n_tokens = int(tokens.shape[1])
+
+
+class _IpCall(NamedTuple):
+    kv: torch.Tensor       # [2, Tip, 2C] f16: K_ip | V_ip of this block, entry 0 the zero image's
+    n_tokens: int
+    scale: float
+
+
 GEMM_TABLE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "gemm_tune_gfx950.txt")
 
 
@@ -256,7 +275,7 @@ class UNetEngine:
                 o2=(_dev(sd[t + "attn2.to_out.0.weight"], d), _dev(sd[t + "attn2.to_out.0.bias"], d)),
                 ff1=(_dev(_geglu_rows(sd[t + "ff.net.0.proj.weight"]), d), _dev(_geglu_rows(sd[t + "ff.net.0.proj.bias"]), d)),
                 ff2=(_dev(sd[t + "ff.net.2.weight"], d), _dev(sd[t + "ff.net.2.bias"], d)),
-                text_kv={})
+                text_kv={}, ip_kv=None)
         for i in range(3):
             w[f"down{i}"] = (_conv_w(sd[f"down_blocks.{i}.downsamplers.0.conv.weight"], d), _dev(sd[f"down_blocks.{i}.downsamplers.0.conv.bias"], d))
             w[f"up{i}"] = (_conv_w(sd[f"up_blocks.{i}.upsamplers.0.conv.weight"], d), _dev(sd[f"up_blocks.{i}.upsamplers.0.conv.bias"], d))
@@ -330,6 +349,20 @@ class UNetEngine:
             ws = torch.empty(self.L.tcl_attention_kv_bytes(Bt, sd15.HEADS, Lt, c // sd15.HEADS), dtype=torch.uint8, device=self.dev)
             hit = blk["text_kv"][key] = dict(kv=kv, ws=ws, packed=False, L=Lt, text=text)
         return hit
+
+    def _ip_kv(self, p, blk, ip):
+        """K_ip | V_ip of block `p` for the ImagePrompt `ip`: tokens @ [to_k_ip ; to_v_ip]^T -> [2, Tip, 2C] f16, one GEMM per block and run (the last
+        ImagePrompt's projection is kept beside the text K / V)."""
+        if ip is None:
+            return None
+        hit = blk["ip_kv"]
+        if hit is None or hit[0] is not ip:
+            w = ip.weights.get(p)
+            if w is None or tuple(w.shape) != (2 * blk["c"], ip.tokens.shape[2]):
+                raise ValueError(f"ImagePrompt: block {p} needs [to_k_ip ; to_v_ip] of shape {(2 * blk['c'], ip.tokens.shape[2])}, got "
+                                 f"{None if w is None else tuple(w.shape)}")
+            hit = blk["ip_kv"] = (ip, self.ops.gemm(ip.tokens, w))
+        return _IpCall(hit[1], ip.n_tokens, ip.scale)
 
     def _q_panel(self, B, Hh, Tq, d):
         """A zero-initialised query-panel workspace per shape, reused by every block (stream order serialises them): tcl_ln_gemm_qpanel_f16 writes the
@@ -428,14 +461,21 @@ class UNetEngine:
         self.tome.unmerge_add(h, xbs, y, T, unm, FN, C, ne)
         self._fl(2.0 * T * C * C * 4 + 4.0 * T * T * C, 2, ne)
 
-    def _attn2(self, blk, h, B, N, text, fuse_ln, qpanel, kvi=None):
+    def attn2(self, p, h, B, N, text, ip=None):
+        """attn2 of transformer block `p` alone (h [B*N, C] f16 -> h + to_out(attention), B = the two guidance halves): the unit the block tests run."""
+        sw, blk = Switches.from_env(), self.tfm[p]
+        return self._attn2(blk, h, B, N, text, blk["c"] == 320 and sw.ln_gemm, sw.qpanel, ip=self._ip_kv(p, blk, ip))
+
+    def _attn2(self, blk, h, B, N, text, fuse_ln, qpanel, kvi=None, ip=None):
         """Text cross-attention on the full tokens; every sample of a guidance half shares that half's text K / V (kv_div).
         kvi (text is a FrameText): every sample attends to the K / V of its own frame's row; the rows are projected and packed once per run, after which
-        only their panels are kept."""
+        only their panels are kept.
+        ip (_IpCall): the image tokens' attention is added to the text attention's output before to_out (IP-Adapter); it reads the [M, C] query, so the
+        query-panel route, which leaves none, is not taken while it is set (the un-fused route writes the same panel bits)."""
         o, C, Hd, d, M = self.ops, blk["c"], sd15.HEADS, blk["c"] // sd15.HEADS, B * N
         tk = self._text_kv(blk, text.text if kvi is not None else text)
         Lt = tk["L"]
-        if fuse_ln and qpanel and tk["packed"]:
+        if fuse_ln and qpanel and tk["packed"] and ip is None:
             # norm2 -> to_q straight into the attention kernel's query panel (linstrip.hip Q-panel epilogue): no [M, C] output, no pack pass
             wq = self._q_panel(B, Hd, N, d)
             self.L.tcl_ln_gemm_qpanel_f16(h, *blk["ln"][1], 1e-5, blk["q2"], M, Hd, d, N, C, C, d ** -0.5, wq, stream())
@@ -445,6 +485,8 @@ class UNetEngine:
             kv = tk["kv"]
             a = o.attention(q, C, N * C, kv if kv is not None else 0, 2 * C, Lt * 2 * C, kv[:, C:] if kv is not None else 0, 2 * C, Lt * 2 * C, B, Hd, N, Lt, d,
                             kv_div=B // 2, ws_kv=tk["ws"], pack_kv=not tk["packed"], kvi=kvi)
+            if ip is not None:
+                self.L.tcl_attention_ip_add_f16(q, C, N * C, ip.kv, a, C, N * C, B, Hd, N, ip.n_tokens, d, d ** -0.5, ip.scale, B // 2, stream())
         tk["packed"] = True
         if kvi is not None:
             tk["kv"] = None                                     # the [rows * L, 2C] projection is read by the pack alone
@@ -457,7 +499,7 @@ class UNetEngine:
         self._fl(2.0 * C * C * 12, M)
         return o.gemm(f2, blk["ff2"][0], blk["ff2"][1], resid=h)
 
-    def _transformer(self, p, x, B, Fs, Hh, Ww, text, sw, pair_half=False, kvi=None):
+    def _transformer(self, p, x, B, Fs, Hh, Ww, text, sw, pair_half=False, kvi=None, ip=None):
         """x [B*N, C], B = 2*sum(Fs) samples: the unconditional ones of all chunks, then the conditional ones; only `_attn1_merged` goes chunk by chunk.
         pair_half: x holds only the FIRST half of the B samples (see forward_many: the two classifier-free-guidance halves are identical up to
         the first text cross-attention); proj_in, norm1, the VidToMe merge and attn1 run on that half, the result is duplicated before attn2."""
@@ -474,7 +516,7 @@ class UNetEngine:
         if pair_half:                                           # from here on the halves differ (text): both exist
             h, x = torch.cat([h, h]), torch.cat([x, x])
         fuse_ln = C == 320 and sw.ln_gemm                       # norm2 / norm3 ride in the consumer's operand load (strip-resident Linear)
-        h = self._attn2(blk, h, B, N, text, fuse_ln, sw.qpanel, kvi)
+        h = self._attn2(blk, h, B, N, text, fuse_ln, sw.qpanel, kvi, self._ip_kv(p, blk, ip))
         h = self._feed_forward(blk, h, B * N, fuse_ln)
         return o.gemm(h, blk["pout"][0], blk["pout"][1], resid=x)
 
@@ -486,7 +528,7 @@ class UNetEngine:
     # orders -- data flow per chunk, bank order per block -- so inside a block only attn1 loops over the chunks; ResNet blocks,
     # norms, cross-attention, feed-forward and the non-merging levels see 8-31x more rows per GEMM and one launch instead of one
     # per chunk, and every weight matrix is streamed once per step.
-    def forward_many(self, x_in, Fs, Hh, Ww, t, text, cfg_pair=False, frames=None):
+    def forward_many(self, x_in, Fs, Hh, Ww, t, text, cfg_pair=False, frames=None, ip=None):
         """x_in [2*Ftot, Hh, Ww, 8] f16 (latents | concat_conds; Ftot = sum(Fs) samples in chunk order, twice: uncond, cond);
         text [2, L, 768] f16 (uncond, cond).  Fs: chunk lengths in the reference's chunk order.  -> eps [2*Ftot, Hh, Ww, 4] f16.
         cfg_pair: the caller GUARANTEES x_in[Ftot:] == x_in[:Ftot] (the classifier-free-guidance pair of generate.py:342-347: `torch.cat([latents] * 2)`
@@ -495,7 +537,9 @@ class UNetEngine:
         are duplicated -- the same bits as computing them twice (every kernel is deterministic and batch-row independent; with equal scores in both
         entries the matching picks the first: `test_cfg_pair_dedup_bit_identical`).  TCL_CFG_DEDUP=0 computes both halves.
         text a FrameText (generation.prompt_path): frames = the local frame id of each of the Ftot samples, in sample order; every conditional sample
-        then attends to its own frame's text, the unconditional half to the one negative.  The prefix shared by the halves ends at the first attn2."""
+        then attends to its own frame's text, the unconditional half to the one negative.  The prefix shared by the halves ends at the first attn2.
+        ip (ImagePrompt; generation.ip_adapter): every attn2 also attends to the image tokens -- the unconditional half to the zero image's, the
+        conditional half to the reference image's.  None: the pass is launch for launch what it was."""
         o, L, w = self.ops, self.L, self.w
         Ftot = sum(Fs)
         B = 2 * Ftot
@@ -523,7 +567,7 @@ class UNetEngine:
                 h = self._resblock(f"down_blocks.{i}.resnets.{j}.", h, Bh if first else B, hh, ww, tproj, sw, rep=2 if first else 1)
                 c = co
                 if i < 3:
-                    h = self._transformer(f"down_blocks.{i}.attentions.{j}.", h, B, Fs, hh, ww, text, sw, pair_half=first, kvi=kvi)
+                    h = self._transformer(f"down_blocks.{i}.attentions.{j}.", h, B, Fs, hh, ww, text, sw, pair_half=first, kvi=kvi, ip=ip)
                 skips.append((h, c))
             if i < 3:
                 h, hh2, ww2 = o.conv3x3(h, B, hh, ww, c, *w[f"down{i}"], stride=2, pad=1)
@@ -532,7 +576,7 @@ class UNetEngine:
                 sizes.append((hh, ww))
                 skips.append((h, c))
         h = self._resblock("mid_block.resnets.0.", h, B, hh, ww, tproj, sw)
-        h = self._transformer("mid_block.attentions.0.", h, B, Fs, hh, ww, text, sw, kvi=kvi)
+        h = self._transformer("mid_block.attentions.0.", h, B, Fs, hh, ww, text, sw, kvi=kvi, ip=ip)
         h = self._resblock("mid_block.resnets.1.", h, B, hh, ww, tproj, sw)
         level = 3
         for i, co in enumerate(sd15.BLOCK_OUT[::-1]):
@@ -541,7 +585,7 @@ class UNetEngine:
                 h = self._resblock(f"up_blocks.{i}.resnets.{j}.", h, B, hh, ww, tproj, sw, skip=sk, cskip=cs)
                 del sk
                 if i > 0:
-                    h = self._transformer(f"up_blocks.{i}.attentions.{j}.", h, B, Fs, hh, ww, text, sw, kvi=kvi)
+                    h = self._transformer(f"up_blocks.{i}.attentions.{j}.", h, B, Fs, hh, ww, text, sw, kvi=kvi, ip=ip)
             if i < 3:
                 level -= 1
                 h, hh2, ww2 = o.conv3x3(h, B, hh, ww, co, *w[f"up{i}"], up=sizes[level])   # nearest upsample fused in the gather
@@ -552,6 +596,6 @@ class UNetEngine:
         self._fl(2.0 * B * hh * ww * 9 * 320 * 4)
         return eps
 
-    def forward_nhwc(self, x_in, F, Hh, Ww, t, text):
+    def forward_nhwc(self, x_in, F, Hh, Ww, t, text, ip=None):
         """One chunk: x_in [2F, Hh, Ww, 8] f16 -> eps [2F, Hh, Ww, 4] f16."""
-        return self.forward_many(x_in, [F], Hh, Ww, t, text)
+        return self.forward_many(x_in, [F], Hh, Ww, t, text, ip=ip)
