@@ -25,15 +25,16 @@ import os
 os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")      # RCCL between processes needs dmabuf IPC on this driver (set before HIP starts)
 import random
 import sys
+from types import SimpleNamespace
 
 import numpy as np
 import torch
 
-from tc_light_amd.config_utils import DEFAULTS as CONFIG_DEFAULTS, Config, load_config, save_config
+from tc_light_amd.config_utils import Config, load_config, save_config
 from tc_light_amd.dataparser import VideoDataParser, get_frame_ids, save_loss_curve, save_video
 from tc_light_amd.generate import DEFAULTS, Generator
-from tc_light_amd.hostlogic import (check_fbc, check_highres, check_highres_tokens, check_init, check_ip_adapter, check_light_path, check_normal,
-                                    check_prompt_path, cond_channels, fbc_background_per_frame, highres_size, light_angles, prompt_table)
+from tc_light_amd.hostlogic import (RESOLVED_KEYS, check_highres_tokens, check_ip_adapter, cond_channels, fbc_background_per_frame, highres_size,
+                                    light_angles, prompt_table, resolve_generation)
 from tc_light_amd.model_utils import allow_random, init_iclight
 from tc_light_amd.parallel import Dist
 from tc_light_amd.text import encode_prompt_pair, encode_prompt_set
@@ -43,194 +44,239 @@ def seed_everything(seed):
     torch.manual_seed(seed); torch.cuda.manual_seed_all(seed); random.seed(seed); np.random.seed(seed)
 
 
-def _save_normal_run(config, g, name, nrm, ambient, relit, info, frames_gt, frame_ids, fps):
-    """The run directory of generation.normal: normal.npy first (u8 [N,H,W,3], RGB = (u, v, h)), normal.mp4, relit_<side>.npy, the ambient video as
-    output.* beside output_gt.* (what evaluate.py looks for) and config.yaml."""
-    config.total_time += info["total_time"]
-    config.sec_per_frame = config.total_time / len(frame_ids)
-    config.max_memory_allocated = max(config.max_memory_allocated, info["max_memory_allocated"])
-    g.scheduler_steps, g.steps_executed = info["scheduler_steps"], info["steps_executed"]
-    g.normal_denoise_seconds = {s: float(t) for s, t in info["denoise_per_direction"].items()}
-    path = os.path.join(g.output_path, f"lmr_{g.local_merge_ratio}_gmr_{g.global_merge_ratio}_alpha_t_{g.alpha_t}_opt_{name}")
-    os.makedirs(path, exist_ok=True)
-    np.save(os.path.join(path, "normal.npy"), nrm.cpu().numpy())      # first: survives whatever fails behind it
-    save_config(config, path, gene=True)
-    for side, frames in relit.items():
-        np.save(os.path.join(path, f"relit_{side}.npy"), (frames.clamp(0, 1) * 255).byte().permute(0, 2, 3, 1).cpu().numpy())
-    ambient = ambient.clamp(0, 1)
-    np.save(os.path.join(path, "output.npy"), (ambient * 255).byte().permute(0, 2, 3, 1).cpu().numpy())
-    # save_video quantises trunc(255 x): (u + 0.5)/255 comes back as u whatever the rounding of the division
-    save_video((nrm.permute(0, 3, 1, 2).float() + 0.5) / 255, path, save_frame=False, stem="normal", fps=fps, gif=False)
-    save_video(ambient, path, save_frame=bool(g.get("save_frame", False)), fps=fps, gif=False)
-    gt_path = os.path.join(path, "gt")
-    if not os.path.exists(gt_path) or len(os.listdir(gt_path)) != len(frame_ids):
-        save_video(frames_gt, path, save_frame=False, post_fix="_gt", fps=fps, gif=False)
-    print(f"[INFO] normals of {len(frame_ids)} frames (4 relights each) in {info['total_time']:.1f} s "
-          f"({1 / config.sec_per_frame:.3f} frames/s) -> {path}")
-
-
-def main(argv=None):
-    config = load_config(argv)
-    seed_everything(config.seed)
+def resolve_options(config):
+    """Everything the configuration alone decides, refused here when malformed or unsupported: before a model is loaded, the video read or flows
+    estimated.  The normalised generation.* values are written back (config.yaml records them).  -> what the run is: scene_type, fbc / light / normal /
+    highres, data_hr (the data section at the final size of the highres pass), the LoRA and the IP-Adapter block."""
+    g = config.generation
     if config.sd_version != "iclight":
         raise NotImplementedError("tc_light_amd implements the IC-Light path (sd_version: iclight); see invert.py")
-    if config.generation.prompt is None:          # checked before models, video and flow estimation are paid for
+    if g.prompt is None:
         raise NotImplementedError("generation.prompt is null: the Cosmos/Pixtral prompt up-sampler (generate.py:538-549) is outside this "
                                   "engine -- give a prompt (-p ... or generation.prompt)")
-    scene_type = str(config.data.get("scene_type", "video")).lower()      # generate.py:84-95; checked before any model is loaded
+    scene_type = str(config.data.get("scene_type", "video")).lower()      # generate.py:84-95
     if scene_type in ("carla", "interiornet"):
         raise NotImplementedError(f"data.scene_type '{scene_type}': this dataparser is not yet built in tc_light_amd (video and sceneflow are)")
     if scene_type not in ("video", "sceneflow"):
         raise NotImplementedError(f"Scene type '{scene_type}' is not supported.")
-    # IC-Light's "Lighting Preference" start (generation.init_latent / init_strength; --light / --strength): refused here when malformed
-    config.generation.init_latent, config.generation.init_strength = check_init(
-        config.generation.get("init_latent", DEFAULTS["init_latent"]), config.generation.get("init_strength", DEFAULTS["init_strength"]),
-        config.generation.get("n_timesteps", DEFAULTS["n_timesteps"]))
-    # IC-Light's highres pass (generation.highres_scale / highres_denoise; --highres_scale / --highres_denoise): refused here when malformed
-    config.generation.highres_scale, config.generation.highres_denoise = check_highres(
-        config.generation.get("highres_scale", DEFAULTS["highres_scale"]), config.generation.get("highres_denoise", DEFAULTS["highres_denoise"]),
-        config.generation.get("n_timesteps", DEFAULTS["n_timesteps"]), bool(config.generation.get("background_cond")))
-    # IC-Light's background-conditioned model (generation.iclight_model / bg_source / fbc_matting; --iclight_model / --bg_source): what it does not
-    # cover (init_latent, the highres pass, background_cond) is refused here by name
-    config.generation.iclight_model, config.generation.bg_source = check_fbc(
-        config.generation.get("iclight_model", DEFAULTS["iclight_model"]), config.generation.get("bg_source", DEFAULTS["bg_source"]),
-        config.generation.init_latent, config.generation.highres_scale, bool(config.generation.get("background_cond")))
-    config.generation.fbc_matting = bool(config.generation.get("fbc_matting", DEFAULTS["fbc_matting"]))
-    fbc = config.generation.iclight_model == "fbc"
-    # an animated light (generation.light_path; --light_sweep A0 A1): one ramp per frame, the start under fc and the background under fbc; what it
-    # does not combine with (init_latent, normal, another bg_source) is refused here by both key names
-    config.generation.light_path = check_light_path(
-        config.generation.get("light_path", DEFAULTS["light_path"]), config.generation.init_latent, config.generation.get("normal", DEFAULTS["normal"]),
-        config.generation.iclight_model, config.generation.bg_source, config.generation.init_strength,
-        config.generation.get("n_timesteps", DEFAULTS["n_timesteps"]))
-    light = config.generation.light_path is not None
-    # IC-Light's "Compute Normal" (generation.normal; --normal): needs the fbc model, refused here otherwise
-    config.generation.normal = config.generation.get("normal", DEFAULTS["normal"])
-    normal = bool(check_normal(config.generation.normal, config.generation.iclight_model, config.generation.fbc_matting,
-                               config.post_opt.get("apply_opt", DEFAULTS["apply_opt"])))
-    if normal:
+    opts = {**DEFAULTS, **g, **config.post_opt}
+    opts["fbc_matting"] = bool(opts["fbc_matting"])
+    r = resolve_generation(opts)      # init_latent, the highres pass, fbc, light_path, normal, prompt_path: each refused by the names of its keys
+    g.update({k: r[k] for k in RESOLVED_KEYS}, fbc_matting=opts["fbc_matting"], normal=opts["normal"])
+    o = SimpleNamespace(scene_type=scene_type, fbc=r["fbc"], light=r["light"], normal=bool(r["normal_sides"]), highres=r["highres"], data_hr=None,
+                        lora=None)
+    if o.normal:
         print("[INFO] generation.normal: the four ramps left / right / bottom / top are the backgrounds; generation.bg_source and "
               "generation.background_image_path are not consulted.")
-        if config.post_opt.get("apply_opt", DEFAULTS["apply_opt"]):
+        if opts["apply_opt"]:
             print("[INFO] generation.normal: stage 1 / 2 do not run on the four relights and no flows are estimated (exposure alignment per direction "
                   "would bias their ratios); post_opt.apply_opt is recorded as false.")
         config.post_opt.apply_opt = False
-    # a prompt that changes over the clip (generation.prompt_path; --prompt_sweep A B): malformed lists and what it does not combine with (normal, the
-    # highres pass) are refused here by both key names
-    config.generation.prompt_path = check_prompt_path(config.generation.get("prompt_path", DEFAULTS["prompt_path"]), config.generation.normal,
-                                                      config.generation.highres_scale)
-    if config.generation.prompt_path is not None:
+    if g.prompt_path is not None:
         print("[INFO] generation.prompt_path: the xy passes are conditioned on the keyframe prompts, blended per frame; generation.prompt names the "
               "run and is recorded in config.yaml, it conditions nothing.  negative_prompt, prompt_t and negative_prompt_t are used as they are.")
     # IP-Adapter (generation.ip_adapter; --ip_image / --ip_scale): a malformed block, a missing image, generation.normal beside it and missing weight
-    # files (models.ip_adapter, models.image_encoder; unless allow_random) are refused here, before any model is loaded
-    ip_block = check_ip_adapter(config.generation.get("ip_adapter", CONFIG_DEFAULTS["generation"]["ip_adapter"]), config.generation.normal,
-                                config.get("models") or {}, allow_random(config.get("models") or {}))
-    if ip_block is not None:
-        config.generation.ip_adapter = Config({k: ip_block[k] for k in ("image", "scale", "path")})      # what config.yaml records
-    if light and fbc:
+    # files (models.ip_adapter, models.image_encoder; unless allow_random) are refused too
+    models = config.get("models") or {}
+    o.ip_block = check_ip_adapter(opts["ip_adapter"], g.normal, models, allow_random(models))
+    if o.ip_block is not None:
+        g.ip_adapter = Config({k: o.ip_block[k] for k in ("image", "scale", "path")})      # what config.yaml records
+    if o.light and o.fbc:
         print("[INFO] generation.light_path: the per-frame ramps are the backgrounds; generation.background_image_path is not consulted.")
-    if fbc and not normal and not light and config.generation.bg_source in ("upload", "upload_flip") and not config.generation.get("background_image_path"):
-        raise ValueError(f"generation.bg_source {config.generation.bg_source} needs generation.background_image_path")
-    highres = config.generation.highres_scale != 1.0
-    data_hr = None
-    if highres:       # the final size; the producers (flows, masks, ids) and output_gt live there, so a second parser is built at that size
-        H2, W2 = highres_size(config.data["height"], config.data["width"], config.generation.highres_scale)
-        check_highres_tokens(H2, W2, config.generation.get("chunk_size", DEFAULTS["chunk_size"]))
-        data_hr = Config(dict(config.data, height=H2, width=W2))
-    lora = None
-    if config.generation.get("use_lora"):         # generate_utils.py:95-96; the file is read and its layout checked before any model is loaded
+    o.upload = o.fbc and not o.normal and not o.light and g.bg_source in ("upload", "upload_flip")      # fbc is conditioned on a background file
+    if o.upload and not g.get("background_image_path"):
+        raise ValueError(f"generation.bg_source {g.bg_source} needs generation.background_image_path")
+    if o.highres:     # the final size; the producers (flows, masks, ids) and output_gt live there, so a second parser is built at that size
+        H2, W2 = highres_size(config.data["height"], config.data["width"], g.highres_scale)
+        check_highres_tokens(H2, W2, opts["chunk_size"])
+        o.data_hr = Config(dict(config.data, height=H2, width=W2))
+    if g.get("use_lora"):             # generate_utils.py:95-96; the file is read and its layout checked here
         from tc_light_amd.lora import from_config
-        lora = from_config(config.generation.get("lora"))
+        o.lora = from_config(g.get("lora"))
+    return o
+
+
+def setup_device():
+    """This process's device and its place among the ranks (torchrun's environment); more than one rank: the process group."""
     world, rank, local = (int(os.environ.get(k, d)) for k, d in (("WORLD_SIZE", 1), ("RANK", 0), ("LOCAL_RANK", 0)))
     dev = torch.device("cuda", local)
     torch.cuda.set_device(dev)
     if world > 1:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         torch.distributed.init_process_group("nccl", device_id=dev)
-    models = config.get("models") or {}
-    ok_random = allow_random(models)
-    pipe, scheduler, config.model_key = init_iclight(dev, models, seed=config.seed, lora=lora,
-                                                     cond_channels=cond_channels(config.generation.iclight_model))
-    config.max_memory_allocated, config.total_time = 0, 0
-    if scene_type == "sceneflow":
+    return dev, Dist(rank, world)
+
+
+def load_frames(config, o, dev):
+    """-> the clip: parser, parser_hr (where stage 1 / 2 run: the second parser at the final size under the highres pass, else the same), frame_ids,
+    frames (all frames at the working size) and frames_out (the source frames at the size of the result)."""
+    if o.scene_type == "sceneflow":
         from tc_light_amd.sceneflow import SceneFlowDataParser
         parser = SceneFlowDataParser(config.data, dev)
     else:
         parser = VideoDataParser(config.data, dev)
-    parser_hr = type(parser)(data_hr, dev) if highres else parser       # where stage 1 / 2 run
+    parser_hr = type(parser)(o.data_hr, dev) if o.highres else parser
     g = config.generation
     frame_ids = get_frame_ids(g.frame_range, parser.n_frames, g.frame_ids)
     config.total_number_of_frames = len(frame_ids)
-    d = Dist(rank, world)
-    lo, hi = d.range(len(frame_ids))
-    frames_all = parser.load_video(frame_ids)
-    frames_out = frames_all                       # the source frames at the size of the result
-    if highres:
-        if scene_type == "video":
+    frames = frames_out = parser.load_video(frame_ids)
+    if o.highres:
+        if o.scene_type == "video":
             parser_hr._all = parser._all          # the clip is read once
         frames_out = parser_hr.load_video(frame_ids)
-    flows = scene = None
-    if config.post_opt.apply_opt and scene_type == "sceneflow":
-        # every rank reads the files itself: ground-truth (or RAFT) flows, masks and the voxelised ids all come from load_data
-        scene = parser_hr.load_data(frame_ids, models=models, allow_random=ok_random)
-    elif config.post_opt.apply_opt:
-        # rank 0 owns the flow cache (read, or estimated with MemFlowNet / RAFT (data.flow_model) and written: video_dataparser.py:63-110); the other ranks
-        # receive the tensors.  A failure on rank 0 (e.g. missing MemFlow weights) is announced before the payload so that every
-        # rank raises instead of waiting in the broadcast until the collective times out.
-        err = None
-        if rank == 0:
-            try:
-                # the on-disk cache belongs to the working size: with the highres pass on it is neither read nor written
-                flows = None if highres else parser.load_flow_cache(frame_ids)
-                if flows is None:
-                    flows = parser_hr.estimate_and_cache_flow(frames_out, frame_ids, parser_hr.make_flow_engine(models, ok_random), save_flow=not highres)
-            except Exception as e:            # noqa: BLE001 - re-raised below on every rank
-                err = e
-        if world > 1:
-            ok = torch.tensor([0 if err is not None else 1], device=dev)
-            torch.distributed.broadcast(ok, src=0)
-            if int(ok.item()) == 0:
-                torch.distributed.destroy_process_group()
-                raise err if err is not None else RuntimeError("rank 0 failed to load / estimate the optical flow (see its traceback)")
-            flows = flows if rank == 0 else tuple(torch.empty(len(frame_ids), 2, parser_hr.h, parser_hr.w, device=dev) for _ in range(2))
-            for t in flows:
-                torch.distributed.broadcast(t, src=0)
-        elif err is not None:
-            raise err
-    cfg = dict(g); cfg.update(config.post_opt); cfg["seed"] = config.seed
-    cfg["frame_ids"], cfg["model_key"] = frame_ids, config.model_key      # generation.latents_path: which saved start latents are this run's
+    return SimpleNamespace(parser=parser, parser_hr=parser_hr, frame_ids=frame_ids, frames=frames, frames_out=frames_out)
+
+
+def load_flows(config, o, clip, models, dev, d):
+    """The stage-1 / 2 producers' input -> (flows, scene), both None without post_opt.apply_opt.  sceneflow: every rank reads the files itself --
+    ground-truth (or RAFT) flows, masks and the voxelised ids all come from load_data.  video: rank 0 owns the flow cache (read, or estimated with
+    MemFlowNet / RAFT (data.flow_model) and written: video_dataparser.py:63-110); the other ranks receive the tensors.  A failure on rank 0 (e.g.
+    missing MemFlow weights) is announced before the payload so that every rank raises instead of waiting in the broadcast until the collective
+    times out."""
+    if not config.post_opt.apply_opt:
+        return None, None
+    ok_random, frame_ids, parser_hr = allow_random(models), clip.frame_ids, clip.parser_hr
+    if o.scene_type == "sceneflow":
+        return None, parser_hr.load_data(frame_ids, models=models, allow_random=ok_random)
+    flows = err = None
+    if d.rank == 0:
+        try:
+            # the on-disk cache belongs to the working size: with the highres pass on it is neither read nor written
+            flows = None if o.highres else clip.parser.load_flow_cache(frame_ids)
+            if flows is None:
+                flows = parser_hr.estimate_and_cache_flow(clip.frames_out, frame_ids, parser_hr.make_flow_engine(models, ok_random),
+                                                          save_flow=not o.highres)
+        except Exception as e:            # noqa: BLE001 - re-raised below on every rank
+            err = e
+    if d.world > 1:
+        ok = torch.tensor([0 if err is not None else 1], device=dev)
+        torch.distributed.broadcast(ok, src=0)
+        if int(ok.item()) == 0:
+            torch.distributed.destroy_process_group()
+            raise err if err is not None else RuntimeError("rank 0 failed to load / estimate the optical flow (see its traceback)")
+        flows = flows if d.rank == 0 else tuple(torch.empty(len(frame_ids), 2, parser_hr.h, parser_hr.w, device=dev) for _ in range(2))
+        for t in flows:
+            torch.distributed.broadcast(t, src=0)
+    elif err is not None:
+        raise err
+    return flows, None
+
+
+def load_background(config, o, clip, models, dev, d):
+    """-> (rmbg, background, bg_per_frame): the matting engine where it is needed (background compositing, generate.py:68-69, 147-167; fbc: the alpha
+    of the grey matte), and this rank's frames of generation.background_image_path -- composited behind the foreground (background_cond), or the
+    background the fbc model is conditioned on: one frame for all, or one per frame (bg_per_frame, the same answer on every rank)."""
+    g, n = config.generation, len(clip.frame_ids)
+    lo, hi = d.range(n)
     rmbg = background = bg_per_frame = None
-    if g.get("background_cond") or (fbc and g.fbc_matting):    # generate.py:68-69, 147-167; fbc: the alpha of the grey matte
+    if g.get("background_cond") or (o.fbc and g.fbc_matting):
         from tc_light_amd.model_utils import load_rmbg_state
         from tc_light_amd.rmbg import RMBGEngine
-        rmbg = RMBGEngine(load_rmbg_state(models.get("rmbg"), allow=ok_random), dev)
+        rmbg = RMBGEngine(load_rmbg_state(models.get("rmbg"), allow=allow_random(models)), dev)
     if g.get("background_cond"):
-        background = parser.load_video(path=g.background_image_path)
-        if background.shape[0] == len(frame_ids) and world > 1:     # a per-frame background video: this rank's block of it
+        background = clip.parser.load_video(path=g.background_image_path)
+        if background.shape[0] == n and d.world > 1:     # a per-frame background video: this rank's block of it
             background = background[lo:hi]
-    elif fbc and not normal and not light and g.bg_source in ("upload", "upload_flip"):     # the background the fbc model is conditioned on: one frame for all, or one per frame
-        background = parser.load_video(path=g.background_image_path)
-        bg_per_frame = fbc_background_per_frame(background.shape[0], len(frame_ids), g.bg_source)      # the same answer on every rank
-        if bg_per_frame and world > 1:
+    elif o.upload:
+        background = clip.parser.load_video(path=g.background_image_path)
+        bg_per_frame = fbc_background_per_frame(background.shape[0], n, g.bg_source)
+        if bg_per_frame and d.world > 1:
             background = background[lo:hi]
+    return rmbg, background, bg_per_frame
+
+
+def save_run(config, name, info, out, clip, first=None, then=None):
+    """What every run directory holds, rank 0 only: the time and memory bookkeeping, config.yaml with the reference's metric keys, output.npy --
+    written before anything that needs an encoder, so it survives whatever fails behind it -- output.* and output_gt.* (generate.py:613-630).
+    first(path) runs before all of it, then(path) between output.npy and the videos.  -> the directory."""
+    g, n, fps = config.generation, len(clip.frame_ids), clip.parser.fps
+    config.total_time += info["total_time"]
+    config.sec_per_frame = config.total_time / n
+    config.max_memory_allocated = max(config.max_memory_allocated, info["max_memory_allocated"])
+    g.scheduler_steps, g.steps_executed = info["scheduler_steps"], info["steps_executed"]
+    path = os.path.join(g.output_path, f"lmr_{g.local_merge_ratio}_gmr_{g.global_merge_ratio}_alpha_t_{g.alpha_t}_opt_{name}")
+    os.makedirs(path, exist_ok=True)
+    if first is not None:
+        first(path)
+    save_config(config, path, gene=True)
+    out = out.clamp(0, 1)
+    np.save(os.path.join(path, "output.npy"), (out * 255).byte().permute(0, 2, 3, 1).cpu().numpy())
+    if then is not None:
+        then(path)
+    save_video(out, path, save_frame=bool(g.get("save_frame", False)), fps=fps, gif=False)
+    gt_path = os.path.join(path, "gt")
+    if not os.path.exists(gt_path) or len(os.listdir(gt_path)) != n:
+        save_video(clip.frames_out, path, save_frame=False, post_fix="_gt", fps=fps, gif=False)
+    return path
+
+
+def save_normal_run(config, name, nrm, ambient, relit, info, clip):
+    """The run directory of generation.normal: normal.npy first (u8 [N,H,W,3], RGB = (u, v, h)), then relit_<side>.npy and normal.mp4 beside the
+    ambient video as output.* and output_gt.* (what evaluate.py looks for)."""
+    config.generation.normal_denoise_seconds = {s: float(t) for s, t in info["denoise_per_direction"].items()}
+
+    def sides(path):
+        for side, frames in relit.items():
+            np.save(os.path.join(path, f"relit_{side}.npy"), (frames.clamp(0, 1) * 255).byte().permute(0, 2, 3, 1).cpu().numpy())
+        # save_video quantises trunc(255 x): (u + 0.5)/255 comes back as u whatever the rounding of the division
+        save_video((nrm.permute(0, 3, 1, 2).float() + 0.5) / 255, path, save_frame=False, stem="normal", fps=clip.parser.fps, gif=False)
+    path = save_run(config, name, info, ambient, clip, first=lambda p: np.save(os.path.join(p, "normal.npy"), nrm.cpu().numpy()), then=sides)
+    print(f"[INFO] normals of {len(clip.frame_ids)} frames (4 relights each) in {info['total_time']:.1f} s "
+          f"({1 / config.sec_per_frame:.3f} frames/s) -> {path}")
+
+
+def save_relit_run(config, o, name, out, info, clip):
+    """The run directory of a relight: what the run was (light_path, the highres pass) recorded in config.yaml, and the loss curves of stage 1 / 2."""
+    g, n = config.generation, len(clip.frame_ids)
+    if o.light:                               # light_path is in g already; the angles of the first and the last frame of the run
+        g.light_angle_first, g.light_angle_last = (float(a) for a in light_angles(g.light_path, [0.0, 1.0 if n > 1 else 0.0]))
+    if o.highres:                             # total_time / sec_per_frame cover both passes
+        g.highres_size = list(info["highres_size"])
+        g.highres_scheduler_steps, g.highres_steps_executed = info["highres_scheduler_steps"], info["highres_steps_executed"]
+
+    def curves(path):
+        if config.post_opt.apply_opt:
+            save_loss_curve(info["losses_exposure"], path, "loss_exposure")
+            if info["losses_unique"] is not None:
+                save_loss_curve(info["losses_unique"], path, "loss_unique_tensor")
+    path = save_run(config, name, info, out, clip, then=curves)
+    print(f"[INFO] {n} frames in {info['total_time']:.1f} s ({1 / config.sec_per_frame:.3f} frames/s) -> {path}")
+
+
+def main(argv=None):
+    config = load_config(argv)
+    seed_everything(config.seed)
+    o = resolve_options(config)               # before any model
+    dev, d = setup_device()
+    models = config.get("models") or {}
+    ok_random = allow_random(models)
+    pipe, scheduler, config.model_key = init_iclight(dev, models, seed=config.seed, lora=o.lora,
+                                                     cond_channels=cond_channels(config.generation.iclight_model))
+    config.max_memory_allocated, config.total_time = 0, 0
+    clip = load_frames(config, o, dev)
+    flows, scene = load_flows(config, o, clip, models, dev, d)
+    rmbg, background, bg_per_frame = load_background(config, o, clip, models, dev, d)
+    g, n = config.generation, len(clip.frame_ids)
+    lo, hi = d.range(n)
+    cfg = dict(g); cfg.update(config.post_opt); cfg["seed"] = config.seed
+    cfg["frame_ids"], cfg["model_key"] = clip.frame_ids, config.model_key      # generation.latents_path: which saved start latents are this run's
     image_prompt = None
-    if ip_block is not None:      # on every rank, once per run: the image tower is built, run on the one image and freed before the UNet loop
+    if o.ip_block is not None:    # on every rank, once per run: the image tower is built, run on the one image and freed before the UNet loop
         from tc_light_amd import ip_adapter
-        image_prompt = ip_adapter.build(ip_block, dev, allow=ok_random)
+        image_prompt = ip_adapter.build(o.ip_block, dev, allow=ok_random)
     gen = Generator(pipe.unet, pipe.vae, cfg, dist=d, scheduler=scheduler, rmbg=rmbg, image_prompt=image_prompt)
+    text = dict(allow_random=ok_random, lora=o.lora)
     for name, prompt in g.prompt.items():
         if g.prompt_path is not None:      # every distinct keyframe prompt is encoded once; the rows of this rank's frames are blended from them
-            uncond, keys = encode_prompt_set(prompt_table(g.prompt_path, len(frame_ids))[0], g.negative_prompt, dev, models.get("text_encoder"),
-                                             allow_random=ok_random, lora=lora)
-            conds = gen.frame_text(uncond, keys, hi - lo, n_total=len(frame_ids))
+            uncond, keys = encode_prompt_set(prompt_table(g.prompt_path, n)[0], g.negative_prompt, dev, models.get("text_encoder"), **text)
+            conds = gen.frame_text(uncond, keys, hi - lo, n_total=n)
         else:
-            conds = encode_prompt_pair(prompt, g.negative_prompt, dev, models.get("text_encoder"), allow_random=ok_random, lora=lora)
-        conds_t = encode_prompt_pair(g.prompt_t, g.negative_prompt_t, dev, models.get("text_encoder"), allow_random=ok_random, lora=lora)
-        if normal:
-            nrm, ambient, relit, info = gen.normals(frames_all[lo:hi], conds, conds_t, n_total=len(frame_ids))
-            if rank == 0:
-                _save_normal_run(config, g, name, nrm, ambient, relit, info, frames_out, frame_ids, parser.fps)
+            conds = encode_prompt_pair(prompt, g.negative_prompt, dev, models.get("text_encoder"), **text)
+        conds_t = encode_prompt_pair(g.prompt_t, g.negative_prompt_t, dev, models.get("text_encoder"), **text)
+        if o.normal:
+            nrm, ambient, relit, info = gen.normals(clip.frames[lo:hi], conds, conds_t, n_total=n)
+            if d.rank == 0:
+                save_normal_run(config, name, nrm, ambient, relit, info, clip)
             continue
         masks = inv = k = past = None
         if scene is not None:
@@ -238,34 +284,12 @@ def main(argv=None):
         elif config.post_opt.apply_opt:
             from tc_light_amd.flow_ids import soft_masks_and_ids
             fut, past = flows
-            masks, inv, k = soft_masks_and_ids(frames_out, fut, past, alpha=parser.alpha)
-        out, info = gen(frames_all[lo:hi], conds, conds_t, past, masks, inv, n_total=len(frame_ids), k=k, background=background,
-                        frames_hr=frames_out[lo:hi] if highres else None, background_per_frame=bg_per_frame)
-        if rank == 0:
-            config.total_time += info["total_time"]
-            config.sec_per_frame = config.total_time / len(frame_ids)
-            config.max_memory_allocated = max(config.max_memory_allocated, info["max_memory_allocated"])
-            g.scheduler_steps, g.steps_executed = info["scheduler_steps"], info["steps_executed"]      # init_latent / init_strength are in g already
-            if light:                             # light_path is in g already; the angles of the first and the last frame of the run
-                g.light_angle_first, g.light_angle_last = (float(a) for a in light_angles(g.light_path, [0.0, 1.0 if len(frame_ids) > 1 else 0.0]))
-            if highres:                           # total_time / sec_per_frame cover both passes
-                g.highres_size = list(info["highres_size"])
-                g.highres_scheduler_steps, g.highres_steps_executed = info["highres_scheduler_steps"], info["highres_steps_executed"]
-            # generate.py:613-630: save_name, config.yaml, output.mp4 (+ frames), output_gt.mp4, loss curves
-            path = os.path.join(g.output_path, f"lmr_{g.local_merge_ratio}_gmr_{g.global_merge_ratio}_alpha_t_{g.alpha_t}_opt_{name}")
-            save_config(config, path, gene=True)
-            out = out.clamp(0, 1)
-            np.save(os.path.join(path, "output.npy"), (out * 255).byte().permute(0, 2, 3, 1).cpu().numpy())    # first: survives any encoder failure
-            if config.post_opt.apply_opt:
-                save_loss_curve(info["losses_exposure"], path, "loss_exposure")
-                if info["losses_unique"] is not None:
-                    save_loss_curve(info["losses_unique"], path, "loss_unique_tensor")
-            save_video(out, path, save_frame=bool(g.get("save_frame", False)), fps=parser.fps, gif=False)
-            gt_path = os.path.join(path, "gt")
-            if not os.path.exists(gt_path) or len(os.listdir(gt_path)) != len(frame_ids):
-                save_video(frames_out, path, save_frame=False, post_fix="_gt", fps=parser.fps, gif=False)
-            print(f"[INFO] {len(frame_ids)} frames in {info['total_time']:.1f} s ({1 / config.sec_per_frame:.3f} frames/s) -> {path}")
-    if world > 1:
+            masks, inv, k = soft_masks_and_ids(clip.frames_out, fut, past, alpha=clip.parser.alpha)
+        out, info = gen(clip.frames[lo:hi], conds, conds_t, past, masks, inv, n_total=n, k=k, background=background,
+                        frames_hr=clip.frames_out[lo:hi] if o.highres else None, background_per_frame=bg_per_frame)
+        if d.rank == 0:
+            save_relit_run(config, o, name, out, info, clip)
+    if d.world > 1:
         torch.distributed.destroy_process_group()
 
 

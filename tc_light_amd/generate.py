@@ -2,20 +2,9 @@
 
   prepare_data -> _prepare_prompts_and_conditions -> ddim_sample{pred_noise per xy-chunk; temporal_denoise (yt-plane);
   scheduler.step} -> decode_latents_batch -> exposure_align -> unique_tensor_optimization        (generate.py:560-611)
-generation.init_latent (not in the reference's run.py; IC-Light's "Lighting Preference", gradio_demo_iclight.py:235-299): build_start replaces the noise
-start by an img2img one and ddim_sample enters a longer schedule part-way; the loop itself is the same.
-generation.highres_scale > 1 (the second half of the same function, :301-334): highres_pass sits between ddim_sample and the decode -- decode ->
-u8 -> PIL-exact LANCZOS resize (csrc/resize.hip) -> encode -> img2img start -> the same ddim_sample at the larger size; decode and stages 1 / 2 then
-run on the frames the user gets.
-generation.normal (fbc only; the background demo's process_normal): Generator.normals runs the matte and the foreground encode once, ddim_sample and the
-decode once per ramp (left, right, bottom, top) from the same start, and one tcl_fbc_normal launch over the four results; no stage 1 / 2.
-
-generation.light_path (an animated light; in neither the reference nor the demos): light_ramps renders one ramp per distinct angle of the rank's frames;
-build_start (fc) makes them the per-frame img2img start, prepare_fbc (fbc) the per-frame backgrounds; distinct ramps are encoded once and gathered.
-
-generation.prompt_path (a text conditioning that changes over the clip; in neither the reference nor the demos): frame_text blends the keyframe prompts'
-embeddings into one row per distinct (k0, k1, t) of the rank's frames (tcl_text_lerp_f16); the xy passes hand the frame ids of their samples to the UNet,
-whose text cross-attention then reads every sample's own K / V (unet.FrameText).  The yt passes keep prompt_t.
+Generator.__call__: prepare_data, encode_conds and (img2img) build_start -> ddim_sample -> optional highres_pass -> decode_gather -> post_optimize.
+What each option adds to that is said at its key in DEFAULTS; hostlogic.resolve_generation checks and resolves them all, once.  Generator.normals
+(generation.normal) runs ddim_sample and the decode once per ramp from the same start and one tcl_fbc_normal launch over the four results.
 
 Python sequences kernel launches and collectives; tensors never leave the device inside the timed region and there is no
 per-iteration host sync (the reference syncs on loss.item() and moves the token bank through the CPU).
@@ -46,14 +35,12 @@ DEFAULTS = dict(  # configs/tclight_default.yaml (generation / post_opt sections
     final_factor_t=0.01, win_size_t=64, apply_opt=True, epochs_exposure=35, epochs=70, batch_size=16, lambda_dssim=0.2,
     lambda_flow=0.8, lambda_tv=0.05, feature_lr=0.05, exposure_lr_init=0.01, exposure_lr_final=0.001, seed=12345,
     post_opt_mode="replicated",      # multi-GPU only: how stage 1 / stage 2 run once the decoded frames are all-gathered.
-                                     # "replicated" (default): every rank runs stage 2 in full on all frames, no collective at all -- it is
-                                     #   bound by streams that do not shrink with the mini-batch share (Adam over the codebook rows, scatters), and
-                                     #   path 2 is bit-reproducible, so the replicas agree bit for bit; stage 1, whose per-iteration work IS
-                                     #   the mini-batch's slots and whose only exchange is the [N,3,4] gradient (14 KB all-reduce), is dealt over
-                                     #   the ranks (round 5).  "replicated_all": stage 1 replicated too -- the one-GPU result, bit for bit.  "global": ONE parameter set with the mini-batch dealt over the ranks, gradients meet in
-                                     #   all_reduce / reduce_scatter (2 x 12 K bytes per stage-2 iteration over xGMI: slower than replication
-                                     #   from K ~ 1e7 up; kept for memory-bound cases).  "shard": the round-1 approximation, each rank's frame
-                                     #   block as a video of its own (tracks cut at the block seams) -- NOT the reference's result.
+                                     # "replicated" (default): every rank runs stage 2 in full on all frames, no collective (path 2 is
+                                     #   bit-reproducible, so the replicas agree bit for bit); stage 1 is dealt over the ranks, its only exchange
+                                     #   the [N,3,4] gradient.  "replicated_all": stage 1 replicated too -- the one-GPU result, bit for bit.
+                                     # "global": ONE parameter set with the mini-batch dealt over the ranks, gradients meet in all_reduce /
+                                     #   reduce_scatter (kept for memory-bound cases).  "shard": each rank's frame block as a video of its own
+                                     #   (tracks cut at the block seams) -- NOT the reference's result.
     shard_post_opt=False,            # legacy spelling of post_opt_mode="shard"
     latents_path=None, model_key="iclight", frame_ids=None,
     # ^ generation.latents_path (generate.py:563-566): saved start latents `<latents_path>/<model_key>/noisy_latents_<first timestep>.pt`, a tensor
@@ -96,14 +83,11 @@ DEFAULTS = dict(  # configs/tclight_default.yaml (generation / post_opt sections
     #   (tcl_attention_ip_add_f16); the yt passes do not (a y-t slice is not an image the photograph describes).  The Generator takes the tokens as
     #   image_prompt= (ip_adapter.build).  None (default): nothing of it is consulted and every path is what it was.
     max_tokens_per_pass=None)
-    # ^ None: TCL_MAX_TOKENS_PER_PASS (read when the Generator is built), else min(16 M, 80 % of the device's free memory / 10.5 KB) -- a block-major pass
-    #   peaks at ~10.4 KB of activations per level-0 token (90 GB for the 8.64 M tokens of 300 frames at 1280x720): a 288 GB MI355X gets the 16 M
-    #   below, a smaller part or a GPU shared with other processes a cap that fits.
-    #   level-0 tokens (samples x pixels) one block-major UNet pass may carry; longer chunk lists are split into consecutive groups.  16 M = the
-    #   whole xy step of 555 frames at 1280x720 in ONE pass (8.6 M tokens, 90 GB peak at 300 frames): rounds 1-3 used 1.5 M (int32-sized tensors);
-    #   one group is 1.4 % faster (177.3 vs 179.8 s denoise, profiles/r4_ab_tokens_per_pass.txt) and, more important, its GEMM shapes do not
-    #   depend on the random chunk lengths (groups cut at a cap hold 153-156 frames depending on the draws: every step met un-tabled shapes and
-    #   the in-call tuner -- the 4.5 M line of that file).  tests/test_gpu_fullsize.py pins pass-size invariance (same bits) beyond 2^31 elements.
+    # ^ level-0 tokens (samples x pixels) one block-major UNet pass may carry; longer chunk lists are split into consecutive groups.  None:
+    #   TCL_MAX_TOKENS_PER_PASS (read when the Generator is built), else min(16 M, 80 % of the device's free memory / 10.5 KB) -- a pass peaks at
+    #   ~10.4 KB of activations per token (90 GB for the 8.64 M tokens of 300 frames at 1280x720).  16 M is the whole xy step of 555 frames at
+    #   1280x720 in ONE pass: one group is faster than several and its GEMM shapes do not depend on the random chunk lengths.
+    #   tests/test_gpu_fullsize.py pins pass-size invariance (same bits) beyond 2^31 elements.
 
 
 def default_max_tokens_per_pass(unet, dev, reserve=0):
@@ -125,7 +109,12 @@ class Generator:
     def __init__(self, unet, vae, config=None, dist=None, scheduler=None, rmbg=None, image_prompt=None):
         cfg = dict(DEFAULTS)
         cfg.update(config or {})
+        r = HL.resolve_generation(cfg)     # every option checked once, in run.py's order; what is refused is refused before anything is built
+        cfg.update({k: r[k] for k in HL.RESOLVED_KEYS})
         self.cfg = SimpleNamespace(**cfg)
+        self.fbc, self.light, self.img2img, self.highres = r["fbc"], r["light"], r["img2img"], r["highres"]
+        self.normal_sides = r["normal_sides"]                                      # () unless generation.normal
+        self.schedule, self.schedule_highres = r["schedule"], r["schedule_highres"]      # (scheduler steps, begin index, steps executed)
         self.unet, self.vae, self.rmbg = unet, vae, rmbg
         self.dev = unet.dev
         self.L = lib()
@@ -136,25 +125,14 @@ class Generator:
         t = self.unet.tome
         t.args.update(local_merge_ratio=c.local_merge_ratio, merge_global=c.merge_global, global_merge_ratio=c.global_merge_ratio,
                       global_rand=c.global_rand, align_batch=bool(c.align_batch))
-        c.init_latent, c.init_strength = HL.check_init(c.init_latent, c.init_strength, c.n_timesteps)
-        c.light_path = HL.check_light_path(c.light_path, c.init_latent, c.normal, c.iclight_model, c.bg_source, c.init_strength, c.n_timesteps)
-        self.light = c.light_path is not None
-        self.img2img = c.init_latent != "none" or (self.light and str(c.iclight_model).lower() != "fbc")      # fc: the path's ramps are the start
-        # (scheduler steps, begin index, steps executed): the whole n_timesteps schedule unless the start is an img2img one
-        self.schedule = HL.img2img_schedule(c.n_timesteps, c.init_strength) if self.img2img else (c.n_timesteps, 0, c.n_timesteps)
-        c.highres_scale, c.highres_denoise = HL.check_highres(c.highres_scale, c.highres_denoise, c.n_timesteps)
-        self.highres = c.highres_scale != 1.0
-        self.schedule_highres = HL.img2img_schedule(c.n_timesteps, c.highres_denoise) if self.highres else None      # the second pass's schedule
-        c.iclight_model, c.bg_source = HL.check_fbc(c.iclight_model, c.bg_source, c.init_latent, c.highres_scale, bool(cfg.get("background_cond")))
-        self.fbc = c.iclight_model == "fbc"
-        self.normal_sides = HL.check_normal(c.normal, c.iclight_model, c.fbc_matting, c.apply_opt)      # () unless generation.normal
-        c.prompt_path = HL.check_prompt_path(c.prompt_path, c.normal, c.highres_scale)
         if (c.ip_adapter is not None) != (image_prompt is not None):
             raise ValueError("generation.ip_adapter: the Generator takes the block's unet.ImagePrompt as image_prompt= (ip_adapter.build), and only then")
         if image_prompt is not None and c.normal:
             raise ValueError("generation.ip_adapter together with generation.normal is not supported")
         self.ip = image_prompt             # handed to every xy pass; the yt passes run without it
-        self.bg_per_frame = None           # __call__'s background_per_frame: whether the fbc background is one frame per frame (None: by its length)
+        self.n_total = None                # the run's frames over all ranks (_total); a caller may assign it before prepare_data
+        self.bg_index = None               # fbc under light_path: the image of bg_frames that is each frame's background (None: bg_frames as they are)
+        self._bg_per_frame = None          # fbc: is the background one frame per frame?  The entry point says (None: by the length of its latents)
         cin = getattr(self.unet, "w", {}).get("conv_in", (None, None, None))[2]      # a stand-in engine may carry no weights
         if cin is not None and cin != 4 + HL.cond_channels(c.iclight_model):
             raise ValueError(f"generation.iclight_model {c.iclight_model}: the UNet's conv_in takes {cin} channels, expected "
@@ -191,7 +169,7 @@ class Generator:
         img2img start, or the saved latents of latents_path).  Generator.normals calls it once per direction, so all four start alike."""
         c = self.cfg
         self.h, self.w = H // 8, W // 8
-        self.n_total = getattr(self, "n_total", None) or n * self.dist.world
+        self._total(n)
         self.rng_dev = torch.Generator(device=self.dev).manual_seed(int(c.seed))
         self.start_noise = None
         if self.img2img:
@@ -200,28 +178,60 @@ class Generator:
                 print(f"[INFO] {what}: the start is built from it, generation.latents_path is not consulted.")
         elif c.latents_path is not None and self._load_start_latents(n):
             return
-        if c.noise_mode.lower() == "same":        # prepare_latents(1, 4, H, W) repeated (generate.py:183-188)
-            z = torch.randn(1, 4, self.h, self.w, generator=self.rng_dev, device=self.dev, dtype=torch.float32)
-            if self.img2img:
-                self.start_noise = z              # f32, one frame for all: build_start broadcasts it
-                return
-            self.init_noise = (z * self.scheduler.init_noise_sigma).to(H16).repeat(n, 1, 1, 1).contiguous()
-        elif c.noise_mode.lower() == "vanilla":
-            z = torch.randn(self.n_total, 4, self.h, self.w, generator=self.rng_dev, device=self.dev, dtype=torch.float32)
-            lo, hi = self.dist.range(self.n_total)
-            if self.img2img:
-                self.start_noise = z[lo:hi]       # f32, this rank's block
-                return
-            self.init_noise = (z[lo:hi] * self.scheduler.init_noise_sigma).to(H16).contiguous()
+        z = self._draw_start(self.h, self.w)
+        if self.img2img:
+            self.start_noise = z           # f32: build_start adds it to x0
+        else:                              # prepare_latents (generate.py:183-188); `same`: the one frame repeated
+            self.init_noise = (z * self.scheduler.init_noise_sigma).to(H16).expand(n, -1, -1, -1).contiguous()
+
+    def _total(self, n, n_total=None, keep=True):
+        """The run's frames over all ranks, set here and nowhere else: what the caller says, else (keep) what is known already -- a caller may have
+        assigned n_total -- else n local frames on every rank."""
+        self.n_total = n_total or (self.n_total if keep else None) or n * self.dist.world
+        return self.n_total
+
+    def _now(self):
+        """A timing point of __call__ / normals: the device drained, then the host clock."""
+        torch.cuda.synchronize(self.dev)
+        return time.perf_counter()
+
+    def _draw_start(self, h, w):
+        """z of one start at latent size (h, w), f32 from rng_dev.  noise_mode same: [1,4,h,w], one frame for all; vanilla: n_total frames are
+        drawn and this rank's block is taken."""
+        mode = self.cfg.noise_mode.lower()
+        if mode == "same":
+            return torch.randn(1, 4, h, w, generator=self.rng_dev, device=self.dev, dtype=torch.float32)
+        if mode != "vanilla":
+            raise NotImplementedError(f"Noise mode '{self.cfg.noise_mode}' is not supported.")
+        lo, hi = self.dist.range(self.n_total)
+        return torch.randn(self.n_total, 4, h, w, generator=self.rng_dev, device=self.dev, dtype=torch.float32)[lo:hi]
+
+    def _noised_start(self, n, x0, x0_stride, z, schedule):
+        """The f16 start latents [n,4,h,w] of an img2img denoise (the img2img pipeline's add_noise): alpha*x0 + sigma_t*z at the first executed sigma
+        of `schedule`.  x0_stride: elements between the x0 of two frames, 0 when one serves all; z as _draw_start returns it."""
+        self.scheduler.set_timesteps(*schedule[:2])
+        alpha, sigma_t = (float(np.float32(v)) for v in self.scheduler.add_noise_coefficients())
+        same = self.cfg.noise_mode.lower() == "same"
+        assert z.shape[0] == (1 if same else n)
+        chw = 4 * z.shape[-2] * z.shape[-1]
+        out = torch.empty(n, *z.shape[1:], dtype=H16, device=self.dev)
+        self.L.tcl_light_start_f16(out, x0.contiguous(), x0_stride, z.contiguous(), 0 if same else chw, n, chw, alpha, sigma_t, stream())
+        return out
+
+    def _axis_ramp(self, side, H, W, levels=None):
+        """One axis-aligned ramp in the [0,1] convention VAEEngine.encode takes, [1,3,H,W] f32 = uint8(linspace)/254.  side: the TCL_LIGHT_* index
+        naming the axis; levels None: tcl_light_gradient_f32 (255 at that side, 0 opposite), else (first, last) sample of tcl_bg_ramp_f32."""
+        img = torch.empty(1, 3, H, W, dtype=torch.float32, device=self.dev)
+        if levels is None:
+            self.L.tcl_light_gradient_f32(img, H, W, side, stream())
         else:
-            raise NotImplementedError(f"Noise mode '{c.noise_mode}' is not supported.")
+            self.L.tcl_bg_ramp_f32(img, H, W, side, int(levels[0]), int(levels[1]), stream())
+        return img
 
     def bg_ramp(self, source, H, W):
-        """bg_source left | right | top | bottom | grey as the [0,1]-convention image VAEEngine.encode takes: [1,3,H,W] f32 = uint8(linspace)/254."""
+        """bg_source left | right | top | bottom | grey: the ramp (or flat grey) of HL.BG_RAMPS."""
         side, start, stop = HL.BG_RAMPS[source]
-        img = torch.empty(1, 3, H, W, dtype=torch.float32, device=self.dev)
-        self.L.tcl_bg_ramp_f32(img, H, W, side, start, stop, stream())
-        return img
+        return self._axis_ramp(side, H, W, (start, stop))
 
     def matte_grey(self, frames, alpha, sigma=None):
         """The background demo's run_rmbg composite: frames [n,3,H,W] f32, alpha [n,1,H,W] f32 -> trunc(clamp(127 + (255 f - 127) a))/254.
@@ -234,21 +244,26 @@ class Generator:
             self.L.tcl_matte_grey_sigma_f32(frames.float().contiguous(), alpha.float().contiguous(), out, n, H, W, float(sigma), stream())
         return out
 
+    def foreground(self, frames, sigma=None):
+        """The foreground image of the fbc model -> (fg_frames [n,3,H,W] f32, alpha [n,1,H,W] | None): the frames matted onto grey with BriaRMBG's
+        alpha (matte_grey), or, with fbc_matting false, as they are (alpha None, no RMBGEngine needed)."""
+        if not self.cfg.fbc_matting:
+            return frames.float().contiguous(), None
+        if self.rmbg is None:
+            raise RuntimeError("generation.fbc_matting needs an RMBGEngine (Generator(..., rmbg=...)); fbc_matting: false feeds the frames as they are")
+        alpha = self.rmbg.estimate_alpha(frames, self.batch_size)
+        return self.matte_grey(frames, alpha, sigma), alpha
+
     def prepare_fbc(self, frames, background):
         """The two condition images of the fbc model: fg_frames [n_local,3,H,W] (matted onto grey, or as given) and bg_frames [1|n_local,3,H,W]
         (bg_source).  A background of one frame serves every frame and is encoded once."""
         c = self.cfg
         n, _, H, W = frames.shape
-        if c.fbc_matting:
-            if self.rmbg is None:
-                raise RuntimeError("generation.fbc_matting needs an RMBGEngine (Generator(..., rmbg=...)); fbc_matting: false feeds the frames as they are")
-            self.fg_frames = self.matte_grey(frames, self.rmbg.estimate_alpha(frames, self.batch_size))
-        else:
-            self.fg_frames = frames.float().contiguous()
-        self.bg_index = None               # light_path only: the image of bg_frames that is each frame's background (None: bg_frames as they are)
+        self.fg_frames, _ = self.foreground(frames)
+        self.bg_index = None
         if self.light:                     # bg_frames = the DISTINCT ramps of this rank's frames; __call__ encodes those and gathers the latents
-            self.bg_frames, index, self.bg_per_frame = self.light_images(n, H, W)
-            if self.bg_per_frame:
+            self.bg_frames, index, several = self.light_images(n, H, W)
+            if several:
                 self.bg_index = torch.tensor(index, dtype=torch.long, device=self.dev)
         elif c.bg_source in HL.BG_RAMPS:
             self.bg_frames = self.bg_ramp(c.bg_source, H, W)
@@ -286,19 +301,12 @@ class Generator:
         c, d = self.cfg, self.dist
         if not self.normal_sides:
             raise ValueError("Generator.normals needs generation.normal: true (and generation.iclight_model fbc)")
-        self.bg_per_frame = False
-        self.n_total = n_total or frames.shape[0] * d.world
+        self._bg_per_frame = False          # every direction's ramp is one frame for all
         n, _, H, W = frames.shape
-        ev = lambda: (torch.cuda.synchronize(self.dev), time.perf_counter())[1]
+        self._total(n, n_total, keep=False)
+        ev = self._now
         t0 = ev()
-        alpha = None
-        if c.fbc_matting:
-            if self.rmbg is None:
-                raise RuntimeError("generation.fbc_matting needs an RMBGEngine (Generator(..., rmbg=...)); fbc_matting: false feeds the frames as they are")
-            alpha = self.rmbg.estimate_alpha(frames, self.batch_size).float().contiguous()
-            self.fg_frames = self.matte_grey(frames, alpha, sigma=HL.NORMAL_MATTE_SIGMA)
-        else:
-            self.fg_frames = frames.float().contiguous()
+        self.fg_frames, alpha = self.foreground(frames, sigma=HL.NORMAL_MATTE_SIGMA)
         self.frames = frames.contiguous()
         fg = self.vae.encode_imgs_batch(self.fg_frames, self.batch_size)
         tome_rng = getattr(self.unet.tome, "rng", None)
@@ -332,9 +340,7 @@ class Generator:
 
     def light_gradient(self, side, H, W):
         """The demo's bg_source image (gradio_demo_iclight.py:241-256) in VAEEngine.encode's [0,1] convention: [1,3,H,W] f32 = uint8(linspace)/254."""
-        img = torch.empty(1, 3, H, W, dtype=torch.float32, device=self.dev)
-        self.L.tcl_light_gradient_f32(img, H, W, HL.INIT_LATENTS.index(side) - 1, stream())
-        return img
+        return self._axis_ramp(HL.INIT_LATENTS.index(side) - 1, H, W)
 
     def light_ramps(self, angles, H, W, hi, lo):
         """generation.light_path: the ramps of frames at `angles` (degrees).  Frames are grouped by bitwise-equal reduced angle and every distinct
@@ -364,10 +370,7 @@ class Generator:
             elif (hi, lo) == HL.LIGHT_LEVELS["fc"]:
                 images.append(self.light_gradient(side, H, W))
             else:
-                img = torch.empty(1, 3, H, W, dtype=torch.float32, device=self.dev)
-                start, stop = (hi, lo) if side in ("left", "top") else (lo, hi)
-                self.L.tcl_bg_ramp_f32(img, H, W, HL.INIT_LATENTS.index(side) - 1, int(start), int(stop), stream())
-                images.append(img)
+                images.append(self._axis_ramp(HL.INIT_LATENTS.index(side) - 1, H, W, (hi, lo) if side in ("left", "top") else (lo, hi)))
         return (images[0] if len(images) == 1 else torch.cat(images)), index
 
     def light_images(self, n, H, W):
@@ -375,7 +378,7 @@ class Generator:
         rank would): (distinct images [D,3,H,W], [index per local frame], whether the run as a whole has more than one distinct ramp -- the same
         answer on every rank, as the per-frame background of fbc needs it)."""
         c = self.cfg
-        n_total = getattr(self, "n_total", None) or n * self.dist.world
+        n_total = self._total(n)
         lo, hi = self.dist.range(n_total)
         assert hi - lo == n
         angles = HL.light_angles(c.light_path, HL.light_positions(n_total))
@@ -392,7 +395,7 @@ class Generator:
         c = self.cfg
         if c.prompt_path is None:
             raise ValueError("Generator.frame_text needs generation.prompt_path")
-        n_total = n_total or getattr(self, "n_total", None) or n * self.dist.world
+        n_total = self._total(n, n_total)
         lo, hi = self.dist.range(n_total)
         assert hi - lo == n
         prompts, rows, index = HL.prompt_table(c.prompt_path, n_total, lo, hi)
@@ -409,10 +412,7 @@ class Generator:
         """img2img start (gradio_demo_iclight.py:283-299 -> the img2img pipeline's add_noise): init_noise = alpha*x0 + sigma_t*z at the first executed
         sigma, with z the f32 draw of prepare_data and x0 the light gradient's latent (encoded once, shared by all frames) or, for `source`,
         the frames' own clean latents `concat_conds` [n_local,4,h,w] f16, or, under light_path, the latent of each frame's own ramp."""
-        c, sch = self.cfg, self.scheduler
-        n_sched, begin, _ = self.schedule
-        sch.set_timesteps(n_sched, begin)
-        alpha, sigma_t = (float(np.float32(v)) for v in sch.add_noise_coefficients())
+        c = self.cfg
         n, chw = self.frames.shape[0], 4 * self.h * self.w
         if c.init_latent == "source":
             x0, x0_stride = concat_conds.contiguous(), chw
@@ -425,11 +425,7 @@ class Generator:
                 x0, x0_stride = x0[torch.tensor(index, dtype=torch.long, device=self.dev)].contiguous(), chw
         else:
             x0, x0_stride = self.vae.encode(self.light_gradient(c.init_latent, *self.frames.shape[-2:])).contiguous(), 0
-        same = c.noise_mode.lower() == "same"
-        z = self.start_noise.contiguous()
-        assert z.shape[0] == (1 if same else n)
-        self.init_noise = torch.empty(n, 4, self.h, self.w, dtype=H16, device=self.dev)
-        self.L.tcl_light_start_f16(self.init_noise, x0, x0_stride, z, 0 if same else chw, n, chw, alpha, sigma_t, stream())
+        self.init_noise = self._noised_start(n, x0, x0_stride, self.start_noise, self.schedule)
         return self.init_noise
 
     # ------------------------------------------------------------------ highres pass (gradio_demo_iclight.py:301-334)
@@ -480,21 +476,8 @@ class Generator:
     def highres_start(self, x0):
         """The second pass's start latents: alpha*x0 + sigma_t*z at the first executed sigma of schedule_highres, z a fresh f32 draw from rng_dev
         (noise_mode same: one frame for all; vanilla: n_total frames, this rank's block taken, as prepare_data does)."""
-        c, sch = self.cfg, self.scheduler
         n, _, h2, w2 = x0.shape
-        sch.set_timesteps(*self.schedule_highres[:2])
-        alpha, sigma_t = (float(np.float32(v)) for v in sch.add_noise_coefficients())
-        same = c.noise_mode.lower() == "same"
-        if same:
-            z = torch.randn(1, 4, h2, w2, generator=self.rng_dev, device=self.dev, dtype=torch.float32)
-        else:
-            lo, hi = self.dist.range(self.n_total)
-            z = torch.randn(self.n_total, 4, h2, w2, generator=self.rng_dev, device=self.dev, dtype=torch.float32)[lo:hi].contiguous()
-        assert z.shape[0] == (1 if same else n)
-        chw = 4 * h2 * w2
-        start = torch.empty(n, 4, h2, w2, dtype=H16, device=self.dev)
-        self.L.tcl_light_start_f16(start, x0.contiguous(), chw, z, 0 if same else chw, n, chw, alpha, sigma_t, stream())
-        return start
+        return self._noised_start(n, x0, 4 * h2 * w2, self._draw_start(h2, w2), self.schedule_highres)
 
     def highres_pass(self, x, frames_hr, conds, conds_t):
         """x: the first pass's latents [n_local,4,h,w]; frames_hr: this rank's source frames at the final size [n_local,3,H2,W2] f32 in [0,1] (the
@@ -567,47 +550,41 @@ class Generator:
     def _unet_xy(self, x, cc, chunks, text, t, noises):
         """pred_noise on the xy chunks of one step (generate.py:220-224, 288-352): chunks = lists of local frame ids, reference order.
         The chunks go through the UNet in block-major passes (`forward_many`, see unet.py): one pack, one unpack per pass."""
-        L = self.L
-
         def pack(grp):
-            frames = [f for c in grp for f in c]
-            n = len(frames)
-            idx = torch.tensor(frames, dtype=I32, device=self.dev)
-            if self.fbc:                   # cc = (foreground latents [n_local,4,h,w], background latents [1|n_local,4,h,w])
-                xin = torch.empty(2 * n, self.h, self.w, 12, dtype=H16, device=self.dev)
-                L.tcl_pack_latents12_f16(x, cc[0], cc[1], cc[1].shape[0], idx, n, 0, 0, 0, self.h, self.w, xin, stream())
-                return xin, idx, n
-            xin = torch.empty(2 * n, self.h, self.w, 8, dtype=H16, device=self.dev)
-            L.tcl_pack_latents_f16(x, cc, idx, n, 0, 0, 0, self.h, self.w, xin, stream())
-            return xin, idx, n
+            return self._pack(x, cc, [f for c in grp for f in c], 0, 0, 0, self.h, self.w)
 
         def unpack(eps, idx, n):
-            L.tcl_unpack_cfg_f16(eps, idx, n, 0, 0, 0, self.h, self.w, float(self.cfg.guidance_scale), 0, 1.0, 0, noises, stream())
+            self.L.tcl_unpack_cfg_f16(eps, idx, n, 0, 0, 0, self.h, self.w, float(self.cfg.guidance_scale), 0, 1.0, 0, noises, stream())
 
         self._run_groups(self._groups(chunks, self.h * self.w), self.h, self.w, t, text, pack, unpack, ip=self.ip)
 
     def _unet_yt(self, x_full, cc_full, items, nt_full, text_t, t):
         """pred_noise on the yt chunks of one frame window: 'n c h w -> w c n h' (generate.py:265-273); items share (start, length)."""
-        L = self.L
         sl, nwin, _, scale_upto, nkeep = items[0]
 
         def pack(grp):
-            cols = [c for ch in grp for c in ch]
-            n = len(cols)
-            idx = torch.tensor(cols, dtype=I32, device=self.dev)
-            if self.fbc:                   # cc_full = (foreground latents of all frames, background latents of one frame or of all)
-                xin = torch.empty(2 * n, nwin, self.h, 12, dtype=H16, device=self.dev)
-                L.tcl_pack_latents12_f16(x_full, cc_full[0], cc_full[1], cc_full[1].shape[0], idx, n, 1, sl, nwin, self.h, self.w, xin, stream())
-                return xin, idx, n
-            xin = torch.empty(2 * n, nwin, self.h, 8, dtype=H16, device=self.dev)
-            L.tcl_pack_latents_f16(x_full, cc_full, idx, n, 1, sl, nwin, self.h, self.w, xin, stream())
-            return xin, idx, n
+            return self._pack(x_full, cc_full, [c for ch in grp for c in ch], 1, sl, nwin, nwin, self.h)
 
         def unpack(eps, idx, n):
-            L.tcl_unpack_cfg_f16(eps, idx, n, 1, sl, nwin, self.h, self.w, float(self.cfg.guidance_scale), scale_upto, math.sqrt(0.5),
-                                 nkeep, nt_full, stream())
+            self.L.tcl_unpack_cfg_f16(eps, idx, n, 1, sl, nwin, self.h, self.w, float(self.cfg.guidance_scale), scale_upto, math.sqrt(0.5),
+                                      nkeep, nt_full, stream())
 
         self._run_groups(self._groups([it[2] for it in items], nwin * self.h), nwin, self.h, t, text_t, pack, unpack)
+
+    def _pack(self, x, cc, ids, axis, start, window, rows, cols):
+        """The UNet input of one pass, both CFG halves: [2 n, rows, cols, 8 | 12] f16 for the samples `ids` -- frames of x (axis 0) or latent columns of
+        the frame window (start, window) (axis 1).  cc: the condition latents in the form ddim_sample takes them, a tensor (fc) or the pair
+        (foreground, background [1 | frames]) (fbc, checked by _check_fbc_conds).  -> (xin, ids on the device, n)."""
+        n = len(ids)
+        idx = torch.tensor(ids, dtype=I32, device=self.dev)
+        if isinstance(cc, (tuple, list)):
+            fg, bg = cc
+            xin = torch.empty(2 * n, rows, cols, 12, dtype=H16, device=self.dev)
+            self.L.tcl_pack_latents12_f16(x, fg, bg, bg.shape[0], idx, n, axis, start, window, self.h, self.w, xin, stream())
+        else:
+            xin = torch.empty(2 * n, rows, cols, 8, dtype=H16, device=self.dev)
+            self.L.tcl_pack_latents_f16(x, cc, idx, n, axis, start, window, self.h, self.w, xin, stream())
+        return xin, idx, n
 
     def _yt_items(self, w_chunks):
         """(window start, length, columns, scale_upto, nkeep) in the reference's loop order (generate.py:265-278)."""
@@ -628,12 +605,22 @@ class Generator:
         if not isinstance(concat_conds, (tuple, list)) or len(concat_conds) != 2:
             raise ValueError("iclight_model fbc: concat_conds is the pair (foreground latents, background latents)")
         fg, bg = concat_conds
-        per_frame = bg.shape[0] > 1 if self.bg_per_frame is None else self.bg_per_frame      # __call__'s background_per_frame, when it was given
+        per_frame = bg.shape[0] > 1 if self._bg_per_frame is None else self._bg_per_frame      # the entry point's word, when it gave one
         ok_bg = bg.shape[0] == (n if per_frame else 1) and tuple(bg.shape[1:]) == (4, self.h, self.w)
         if tuple(fg.shape) != (n, 4, self.h, self.w) or not ok_bg or fg.dtype != H16 or bg.dtype != H16 or not (fg.is_contiguous() and bg.is_contiguous()):
             raise ValueError(f"iclight_model fbc: foreground latents {tuple(fg.shape)} {fg.dtype}, background latents {tuple(bg.shape)} {bg.dtype}; "
                              f"expected {(n, 4, self.h, self.w)} and {(n if per_frame else 1, 4, self.h, self.w)} contiguous f16")
         return per_frame
+
+    def _conds_full(self, x, concat_conds):
+        """Once per denoise: the fbc pair is checked, and for the yt passes (alpha_t > 0, else None) the conditions of ALL frames are gathered, in
+        the form they came in -- the background of fbc only when it is one per frame."""
+        d, yt = self.dist, self.cfg.alpha_t > 0
+        if self.fbc:
+            per_frame = self._check_fbc_conds(x, concat_conds)
+            fg, bg = concat_conds
+            return (d.gather_frames(fg, self.n_total), d.gather_frames(bg, self.n_total) if per_frame else bg) if yt else None
+        return d.gather_frames(concat_conds, self.n_total) if yt else None
 
     # ------------------------------------------------------------------ hot loop 1
     @torch.no_grad()
@@ -653,13 +640,7 @@ class Generator:
         alphas = HL.alpha_schedule(c.alpha_t, c.final_factor_t, len(sch.timesteps))
         xy_sampler = HL.ChunkSampler(c.seed + 7919 * d.rank, c.chunk_size, c.merge_global, c.chunk_ord)
         yt_sampler = HL.ChunkSampler(c.seed + 1, c.chunk_size, c.merge_global, c.chunk_ord)
-        per_frame = self._check_fbc_conds(x, concat_conds) if self.fbc else False
-        cc_full = None
-        if c.alpha_t > 0 and self.fbc:     # the foreground latents of all frames; the background's only when it is per-frame
-            fg, bg = concat_conds
-            cc_full = (d.gather_frames(fg, self.n_total), d.gather_frames(bg, self.n_total) if per_frame else bg)
-        elif c.alpha_t > 0:
-            cc_full = d.gather_frames(concat_conds, self.n_total)
+        cc_full = self._conds_full(x, concat_conds)
         lo, hi = d.range(self.n_total)
         for i, t in enumerate(sch.timesteps.tolist()):
             self._unet_xy(x, concat_conds, xy_sampler.get_chunks(n_local), conds, t, noises)
@@ -689,85 +670,99 @@ class Generator:
         rank's block of a per-frame clip); background_per_frame says which when the block alone cannot (None: more than one frame handed in) --
         every rank must give the same answer, since a per-frame background is all-gathered for the yt pass."""
         c, d = self.cfg, self.dist
-        self.bg_per_frame = None if background_per_frame is None else bool(background_per_frame)
         if self.highres and background is not None:
             raise ValueError("generation.background_cond together with generation.highres_scale > 1 is not supported")
-        self.n_total = n_total or frames.shape[0] * d.world
+        self._total(frames.shape[0], n_total, keep=False)
         if (c.prompt_path is not None) != isinstance(conds, FrameText) or (isinstance(conds, FrameText) and len(conds.index) != frames.shape[0]):
             raise ValueError("generation.prompt_path: conds must be the FrameText of Generator.frame_text for this rank's frames (and only then)")
-        ev = lambda: (torch.cuda.synchronize(self.dev), time.perf_counter())[1]
+        ev = self._now
         t0 = ev()
         self.prepare_data(frames, background)
-        if self.fbc:                       # (foreground, background) latents: model_utils.py:97-179 concat_conds, kept apart (one background frame stays one)
-            concat_conds = (self.vae.encode_imgs_batch(self.fg_frames, self.batch_size), self.vae.encode_imgs_batch(self.bg_frames, self.batch_size))
-            if self.bg_index is not None:      # light_path: bg_frames are the distinct ramps; their latents are gathered to one per frame
-                concat_conds = (concat_conds[0], concat_conds[1][self.bg_index].contiguous())
-        else:
-            concat_conds = self.vae.encode_imgs_batch(self.frames, self.batch_size)
+        # fbc: is the background one frame per frame?  Under light_path when the run has several ramps, else the caller's word (None: by its length)
+        self._bg_per_frame = (self.bg_index is not None) if self.light else (None if background_per_frame is None else bool(background_per_frame))
+        concat_conds = self.encode_conds()
         if self.img2img:
             self.build_start(concat_conds)
         t1 = ev()
         x = self.ddim_sample(self.init_noise.clone(), conds, conds_t, concat_conds)
         self.latents = x                   # the first pass's result (with highres on: what the second pass starts from)
         t2 = t2a = ev()
-        if self.highres:
+        if self.highres:                   # decode -> u8 -> resize -> encode -> second denoise, between `denoise` and `decode`
             x = self.highres_pass(x, frames_hr, conds, conds_t)
             t2 = ev()
         mode = "shard" if c.shard_post_opt else str(c.post_opt_mode)
         if mode not in ("replicated", "replicated_all", "global", "shard"):
             raise ValueError(f"post_opt_mode {mode!r}: expected replicated | replicated_all | global | shard")
         shard = d.multi and mode == "shard" and c.apply_opt
-        lo, hi = d.range(self.n_total)
-        if d.multi and not shard:
-            # decode slab by slab; every slab goes into an async all-gather while the next one decodes (parallel.gather_frames_pipelined)
-            clean_local = None
-            clean = d.gather_frames_pipelined(lambda a, b: self.vae.decode_latents_batch(x[a:b], self.batch_size), x.shape[0], self.n_total,
-                                              slab=int(os.environ.get("TCL_DECODE_SLAB", "8")))
-        else:
-            clean_local = self.vae.decode_latents_batch(x, self.batch_size)
-        if shard:
-            # Opt-in approximation: stage 1/2 on this rank's frame block as a video of its own (its first frame has no predecessor, tracks
-            # are cut at the block boundary; the global track ids restricted to the block and renumbered densely give the partition
-            # get_flowid would produce when started at the block's first frame).  No collective, but NOT the reference's result.
-            clean = clean_local
-            past_flows, mask_bwds = past_flows[lo:hi], mask_bwds[lo:hi]
-            hw = clean_local.shape[-2] * clean_local.shape[-1]
-            uniq, inv_local = torch.unique(unq_inv[lo * hw:hi * hw], return_inverse=True)
-            unq_inv, k = inv_local.to(torch.int32), int(uniq.numel())
-        elif clean_local is not None:
-            clean = clean_local
-        t3 = ev()
+        clean, past_flows, mask_bwds, unq_inv, k = self.decode_gather(x, shard, past_flows, mask_bwds, unq_inv, k)
+        t3 = t4 = t5 = ev()
         losses1 = losses2 = None
         if c.apply_opt:
-            N = clean.shape[0]
-            pd = d if (mode == "global" and d.multi) else None      # global: the ranks split every mini-batch and share one parameter set;
-            #                                                           # replicated / shard: every rank optimises on its own (no collective)
-            pd1 = d if (mode in ("global", "replicated") and d.multi) else None      # stage 1: dealt over the ranks unless replicated_all / shard
-            ds = post_opt.OptDataset(clean, past_flows, mask_bwds, device=self.dev)
-            rng = np.random.default_rng(c.seed + (d.rank if shard else 0))      # global mode: the identical schedule on every rank
-            s1 = post_opt.make_schedule(N, c.batch_size, c.epochs_exposure, rng)
-            _, _, losses1 = post_opt.exposure_align(ds, s1, c.epochs_exposure, c.batch_size, c.exposure_lr_init, c.exposure_lr_final,
-                                                    c.lambda_dssim, c.lambda_flow, dist=pd1)
-            t4 = ev()
-            if c.epochs > 0:
-                s2 = post_opt.make_schedule(N, c.batch_size, c.epochs, rng)
-                clean, _, losses2 = post_opt.unique_tensor_optimization(ds, unq_inv, s2, c.batch_size, c.feature_lr, c.lambda_dssim,
-                                                                        c.lambda_flow, c.lambda_tv, k=k, dist=pd)
-            else:
-                clean = ds.edited_images
-            if shard:
-                clean = d.gather_frames(clean.contiguous(), self.n_total)
+            clean, losses1, losses2, t4 = self.post_optimize(clean, mode, shard, past_flows, mask_bwds, unq_inv, k)
             t5 = ev()
-        else:
-            t4 = t5 = t3
         self.timing = dict(encode=t1 - t0, denoise=t2a - t1, decode=t3 - t2, stage1=t4 - t3, stage2=t5 - t4, total=t5 - t0)
         info = dict(timing=self.timing, losses_exposure=losses1, losses_unique=losses2, total_time=t5 - t0,
                     sec_per_frame=(t5 - t0) / self.n_total, total_number_of_frames=self.n_total, init_latent=c.init_latent,
                     iclight_model=c.iclight_model, ip_adapter=c.ip_adapter,
                     init_strength=c.init_strength, scheduler_steps=self.schedule[0], steps_executed=self.schedule[2],
                     max_memory_allocated=torch.cuda.max_memory_allocated(self.dev) / 1024.0 ** 2)
-        if self.highres:                   # decode -> u8 -> resize -> encode -> second denoise, between `denoise` and `decode`
+        if self.highres:
             self.timing["highres"] = t2 - t2a
             info.update(highres_scale=c.highres_scale, highres_denoise=c.highres_denoise, highres_size=[8 * self.h, 8 * self.w],
                         highres_scheduler_steps=self.schedule_highres[0], highres_steps_executed=self.schedule_highres[2])
         return clean, info
+
+    def encode_conds(self):
+        """ddim_sample's concat_conds from what prepare_data left.  fc: the latents of the frames.  fbc: the pair (foreground, background) latents
+        (model_utils.py:97-179 concat_conds, kept apart: one background frame stays one); under light_path bg_frames are the distinct ramps and
+        their latents are gathered to one per frame."""
+        enc = lambda images: self.vae.encode_imgs_batch(images, self.batch_size)
+        if self.fbc:
+            fg, bg = enc(self.fg_frames), enc(self.bg_frames)
+            return fg, (bg if self.bg_index is None else bg[self.bg_index].contiguous())
+        return enc(self.frames)
+
+    def decode_gather(self, x, shard, past_flows, mask_bwds, unq_inv, k):
+        """The latents of this rank's frames -> (decoded frames, then the stage-1 / 2 inputs that go with them).  Multi-rank: the frames of all ranks,
+        decoded slab by slab, every slab in an async all-gather while the next one decodes (parallel.gather_frames_pipelined).
+        shard (opt-in approximation): the rank keeps its own block as a video of its own -- its first frame has no predecessor, tracks are cut at
+        the block boundary; the global track ids restricted to the block and renumbered densely give the partition get_flowid would produce when
+        started at the block's first frame.  No collective, but NOT the reference's result."""
+        d = self.dist
+        if d.multi and not shard:
+            clean = d.gather_frames_pipelined(lambda a, b: self.vae.decode_latents_batch(x[a:b], self.batch_size), x.shape[0], self.n_total,
+                                              slab=int(os.environ.get("TCL_DECODE_SLAB", "8")))
+            return clean, past_flows, mask_bwds, unq_inv, k
+        clean = self.vae.decode_latents_batch(x, self.batch_size)
+        if shard:
+            lo, hi = d.range(self.n_total)
+            past_flows, mask_bwds = past_flows[lo:hi], mask_bwds[lo:hi]
+            hw = clean.shape[-2] * clean.shape[-1]
+            uniq, inv_local = torch.unique(unq_inv[lo * hw:hi * hw], return_inverse=True)
+            unq_inv, k = inv_local.to(torch.int32), int(uniq.numel())
+        return clean, past_flows, mask_bwds, unq_inv, k
+
+    def post_optimize(self, clean, mode, shard, past_flows, mask_bwds, unq_inv, k):
+        """Stage 1 (exposure alignment) and stage 2 (unique video tensor) on the decoded frames under post_opt_mode `mode` (DEFAULTS).
+        -> (frames, stage-1 losses, stage-2 losses | None, the timing point between the stages)."""
+        c, d = self.cfg, self.dist
+        N = clean.shape[0]
+        pd = d if (mode == "global" and d.multi) else None      # global: the ranks split every mini-batch and share one parameter set;
+        #                                                           # replicated / shard: every rank optimises on its own (no collective)
+        pd1 = d if (mode in ("global", "replicated") and d.multi) else None      # stage 1: dealt over the ranks unless replicated_all / shard
+        ds = post_opt.OptDataset(clean, past_flows, mask_bwds, device=self.dev)
+        rng = np.random.default_rng(c.seed + (d.rank if shard else 0))      # global mode: the identical schedule on every rank
+        s1 = post_opt.make_schedule(N, c.batch_size, c.epochs_exposure, rng)
+        _, _, losses1 = post_opt.exposure_align(ds, s1, c.epochs_exposure, c.batch_size, c.exposure_lr_init, c.exposure_lr_final,
+                                                c.lambda_dssim, c.lambda_flow, dist=pd1)
+        t4 = self._now()
+        losses2 = None
+        if c.epochs > 0:
+            s2 = post_opt.make_schedule(N, c.batch_size, c.epochs, rng)
+            clean, _, losses2 = post_opt.unique_tensor_optimization(ds, unq_inv, s2, c.batch_size, c.feature_lr, c.lambda_dssim,
+                                                                    c.lambda_flow, c.lambda_tv, k=k, dist=pd)
+        else:
+            clean = ds.edited_images
+        if shard:
+            clean = d.gather_frames(clean.contiguous(), self.n_total)
+        return clean, losses1, losses2, t4

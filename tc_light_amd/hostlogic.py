@@ -393,7 +393,32 @@ def check_ip_adapter(block, normal=False, models=None, allow_random=False):
     return dict(image=image, scale=float(scale), path=path, image_encoder=encoder)
 
 
-TOME_MAX_SRC_TOKENS = 64 * 1024       # tcl_tome_match_f16 / _affine_f16: source tokens of one match (csrc/merge.hip)
+# what resolve_generation normalises: run.py writes these back into the configuration (config.yaml records them), Generator into its cfg
+RESOLVED_KEYS = ("init_latent", "init_strength", "highres_scale", "highres_denoise", "iclight_model", "bg_source", "light_path", "prompt_path")
+
+
+def resolve_generation(cfg):
+    """The one resolution of the generation options, for run.py (before a model is loaded) and Generator alike.  cfg: generate.DEFAULTS overlaid
+    with generation.*, post_opt.* and background_cond.  Every check_* above runs once, in this order, so two faults at once are reported the same
+    way everywhere; check_ip_adapter (models, the file system) is the caller's.  -> the RESOLVED_KEYS normalised, and what follows from them:
+    fbc / light / img2img / highres, normal_sides (() unless generation.normal), schedule = (scheduler steps, begin index, steps executed) -- the
+    whole n_timesteps unless the start is an img2img one -- and schedule_highres (the second pass's; None when it is off)."""
+    n, normal, bg_cond = cfg["n_timesteps"], cfg["normal"], bool(cfg.get("background_cond"))
+    r = {}
+    r["init_latent"], r["init_strength"] = check_init(cfg["init_latent"], cfg["init_strength"], n)
+    r["highres_scale"], r["highres_denoise"] = check_highres(cfg["highres_scale"], cfg["highres_denoise"], n, bg_cond)
+    r["iclight_model"], r["bg_source"] = check_fbc(cfg["iclight_model"], cfg["bg_source"], r["init_latent"], r["highres_scale"], bg_cond)
+    r["light_path"] = check_light_path(cfg["light_path"], r["init_latent"], normal, r["iclight_model"], r["bg_source"], r["init_strength"], n)
+    r["normal_sides"] = check_normal(normal, r["iclight_model"], cfg["fbc_matting"], cfg["apply_opt"])
+    r["prompt_path"] = check_prompt_path(cfg["prompt_path"], normal, r["highres_scale"])
+    r["fbc"], r["light"], r["highres"] = r["iclight_model"] == "fbc", r["light_path"] is not None, r["highres_scale"] != 1.0
+    r["img2img"] = r["init_latent"] != "none" or (r["light"] and not r["fbc"])      # fc: the path's ramps are the start
+    r["schedule"] = img2img_schedule(n, r["init_strength"]) if r["img2img"] else (n, 0, n)
+    r["schedule_highres"] = img2img_schedule(n, r["highres_denoise"]) if r["highres"] else None
+    return r
+
+
+TOME_MAX_SRC_TOKENS = 64 * 1024      # tcl_tome_match_f16 / _affine_f16: source tokens of one match (csrc/merge.hip)
 
 
 def check_highres_tokens(H2, W2, chunk_size):
