@@ -149,7 +149,11 @@ int tcl_groupnorm_f16(const void* x1, int C1, const void* x2, int C2, const void
                       int groups, float eps, int silu, void* ws, hipStream_t st);
 /* The same with a second output: yraw [B,HW,C1+C2] (may be NULL) receives the un-normalised channel concat cat([x1, x2]) -- the operand of the
  * up-block ResnetBlock2D's conv_shortcut (diffusers ResnetBlock2D.forward: `input_tensor = conv_shortcut(input_tensor)` on the concatenated
- * input) -- from the pass that reads x1 / x2 anyway, instead of a concat pass of its own (tcl_concat_channels_f16). */
+ * input) -- from the pass that reads x1 / x2 anyway, instead of a concat pass of its own (tcl_concat_channels_f16).
+ * Channel groupings (both entries): groups <= 64, C % groups == 0, cpg = C / groups >= 4, C1 and C2 multiples of 8, and NO 8-channel chunk [8k, 8k + 8)
+ * may touch three groups -- the kernels split a chunk once, between the group of its first and the group of its last channel.  A chunk that starts
+ * off = 8k mod cpg channels into a group touches three when 2*cpg - off < 8; of the admitted cpg only 5 has such an offset (off = 3 at channel 8 of
+ * C = 160, groups = 32).  Such a grouping returns TCL_EINVAL before any launch, like every other unsupported shape; nothing is written. */
 int tcl_groupnorm_concat_f16(const void* x1, int C1, const void* x2, int C2, const void* gamma, const void* beta, void* y, void* yraw, int B, int HW,
                              int groups, float eps, int silu, void* ws, hipStream_t st);
 /* torch.nn.LayerNorm(C) (BasicTransformerBlock.norm1/2/3). */

@@ -644,6 +644,15 @@ int tcl_conv1x1_small_f16(const void* x, int ldi, const void* W, const void* b, 
 // or in a batch of 600 (unet.py relies on it: the identical CFG halves are computed once).  (Until round 3 the cap shrank with B.)
 static inline int gn_blocks_cap(int B) { (void)B; return 256; }
 size_t tcl_groupnorm_workspace_bytes(int B, int C) { (void)C; return ((size_t)B * gn_blocks_cap(B) + B) * 64 * 2 * 4 + 256; }
+// k_gn_stats / k_gn_apply split an 8-channel chunk ONCE (head -> its first group, tail -> the group of its last channel): a chunk that starts
+// `off` channels into a group and still reaches a third one (cpg - off channels of the first, cpg of the second, and some left: 2*cpg - off < 8) would
+// be normalised with the wrong statistics.  The offsets 8k mod cpg repeat after cpg chunks at the latest.
+static bool gn_chunk_spans_three_groups(int C, int cpg) {
+    const int nchunk = C / 8;
+    for (int k = 0; k < nchunk && k < cpg; ++k)
+        if (2 * cpg - (8 * k) % cpg < 8) return true;
+    return false;
+}
 int tcl_groupnorm_f16(const void* x1, int C1, const void* x2, int C2, const void* gamma, const void* beta, void* y, int B, int HW,
                       int groups, float eps, int silu, void* ws, hipStream_t st) {
     return tcl_groupnorm_concat_f16(x1, C1, x2, C2, gamma, beta, y, nullptr, B, HW, groups, eps, silu, ws, st);
@@ -653,6 +662,7 @@ int tcl_groupnorm_concat_f16(const void* x1, int C1, const void* x2, int C2, con
     const int C = C1 + C2;
     TCL_CHECK_ARG(x1 && gamma && beta && y && ws && B > 0 && HW > 0 && groups > 0 && groups <= 64 && C % groups == 0 && C / groups >= 4 && C1 % 8 == 0 && C2 % 8 == 0);
     TCL_CHECK_ARG(C2 == 0 || x2);
+    TCL_CHECK_ARG(!gn_chunk_spans_three_groups(C, C / groups));
     int blocks = cdiv(HW, 64); if (blocks > gn_blocks_cap(B)) blocks = gn_blocks_cap(B);
     int rpb = cdiv(HW, blocks); blocks = cdiv(HW, rpb);
     float* part = (float*)ws; float* sums = part + (size_t)B * gn_blocks_cap(B) * 64 * 2;
