@@ -28,8 +28,8 @@ import numpy as np
 import torch
 
 from . import clip
+from .flow_core import pad8
 from .lib import lib, stream
-from .memflow import _pad8
 from .raft import estimate_flows_raft
 
 EDIT_STEMS = ("output_opt", "output")          # evaluate.py:27: output_opt.mp4 if it exists, else output.mp4
@@ -147,7 +147,7 @@ def warp_ssim(edit_u8, source_u8, raft_engine, batch=4):
     if tuple(src.shape[1:3]) != (H, W):
         src = resize_like(src, H, W)
     x = src[:N].to(raft_engine.dev).permute(0, 3, 1, 2).float()            # load_image: float 0..255
-    x, pad = _pad8(x)
+    x, pad = pad8(x)
     check_size(*x.shape[-2:])
     fut, past = estimate_flows_raft(raft_engine, x, batch=batch)            # 0..255 in: RAFT's own normalisation is then the right one
     del x

@@ -442,3 +442,19 @@ def expon_lr(step, lr_init, lr_final, max_steps):
     """get_expon_lr_func(lr_init, lr_final, lr_delay_steps=0, max_steps=max_steps)(step)  (utils/general_utils.py:31-64, delay off)."""
     t = min(max(step / max_steps, 0.0), 1.0)
     return math.exp(math.log(lr_init) * (1 - t) + math.log(lr_final) * t)
+
+
+def pad8_amounts(H, W):
+    """eval_utils.InputPadder -> (left, right, top, bottom) up to multiples of 8, split as evenly as possible."""
+    ph, pw = (((H // 8) + 1) * 8 - H) % 8, (((W // 8) + 1) * 8 - W) % 8
+    return pw // 2, pw - pw // 2, ph // 2, ph - ph // 2
+
+
+def memflow_splitkv_chunks(P, T, want=3):
+    """Key chunks of MemFlowNet's memory-read attention (P queries, T keys, one head): tcl_attention_splitkv_f16 takes chunks of a multiple of 64
+    keys and at most 1024 blocks of 128 queries x chunks.  `want` if it fits, else the first of (3, 2, 5, 4, 6) that does, else 0 = the one-pass
+    kernel; a `want` below 2 asks for the one-pass kernel."""
+    fits = lambda c: T % (64 * c) == 0 and -(-P // 128) * c <= 1024
+    if want < 2:
+        return 0
+    return want if fits(want) else next((c for c in (3, 2, 5, 4, 6) if fits(c)), 0)

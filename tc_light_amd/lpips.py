@@ -24,6 +24,7 @@ import math
 
 import torch
 
+from .hostlogic import pad8_amounts
 from .lib import lib, stream
 
 H16 = torch.float16
@@ -77,12 +78,6 @@ def check_state(state):
 def tap_sizes(H, W):
     """The (h, w) of the five taps of an H x W image: floor halving, as MaxPool2d(2, 2)."""
     return [(H >> k, W >> k) for k in range(5)]
-
-
-def pad8_amounts(H, W):
-    """eval_utils.InputPadder's default mode -> (left, right, top, bottom) up to multiples of 8, split as evenly as possible (memflow._pad8's)."""
-    ph, pw = (((H // 8) + 1) * 8 - H) % 8, (((W // 8) + 1) * 8 - W) % 8
-    return pw // 2, pw - pw // 2, ph // 2, ph - ph // 2
 
 
 def pad8_u8(frames):

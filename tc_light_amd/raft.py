@@ -1,10 +1,10 @@
 """RAFT inference on the device: the second flow estimator of the stage-2 inputs (`data.flow_model: raft`).
 
 `RAFTEngine` = the reference's RAFT (utils/evaluation/core/raft.py:73-131, not small, no alternate_corr, no mixed precision) with
-`forward(test_mode=True)` semantics.  The two BasicEncoders and the correlation lookup are MemFlowNet's (tc_light_amd.memflow: the keys, shapes
-and the CorrBlock are the same); the fnet stem keeps its convolution in f32 up to the instance norm (tcl_conv7x7s2_instnorm_f16), because the
-stage-2 frames reach RAFT in [0, 1] rather than [0, 255] (see `estimate_flows_raft`) and the f16 rounding of the stem would then be amplified by
-the normalisation.  The update block (update.py:60-136) runs on f16 NHWC rows: convc1 / mask.2 as GEMMs, the 3x3 convolutions on the implicit-GEMM
+`forward(test_mode=True)` semantics.  The two BasicEncoders, the correlation lookup and the engine steps are the ones MemFlowNet uses
+(tc_light_amd.flow_core: the keys, shapes and the CorrBlock are the same); the fnet stem keeps its convolution in f32 up to the instance norm
+(tcl_conv7x7s2_instnorm_f16), because the stage-2 frames reach RAFT in [0, 1] rather than [0, 255] (see `estimate_flows_raft`) and the f16 rounding
+of the stem would then be amplified by the normalisation.  The update block (update.py:60-136) runs on f16 NHWC rows: convc1 / mask.2 as GEMMs, the 3x3 convolutions on the implicit-GEMM
 kernel, convf1 (7x7 over the 2-channel flow) in csrc/raft.hip, and each SepConvGRU half-step as two fused kernels (gate: [z | r] + r*h;
 candidate: q + the blend, in place).  The GRU input is x = [inp | motion] and `inp` is the same on every iteration: its share of the six
 convolutions (with their biases) is computed once per pair as an f32 per-pixel bias (the "context fold"), so the per-iteration K is 1 280.
@@ -13,10 +13,10 @@ Pinned against the reference by tests/golden/raft.npz (tests/test_gpu_raft.py).
 """
 import torch
 
-from .lib import lib, stream
-from .memflow import CorrBlock, EncoderEngine, _Lin, _pad_to, encoder_param_shapes, seeded_state_dict as _seeded
+from . import flow_core
+from .flow_core import H16, CorrBlock, EncoderEngine, FlowEngine, Lin, encoder_param_shapes
+from .lib import stream
 
-H16 = torch.float16
 ITERS = 20                                                              # video_dataparser.py:149
 
 
@@ -42,9 +42,9 @@ def raft_param_shapes():
 
 
 def seeded_state_dict(seed=5):
-    """Seeded stand-in weights: memflow.seeded_state_dict's rules (He-scaled convs, BatchNorm statistics near identity), with
+    """Seeded stand-in weights: flow_core.seeded_state_dict's rules (He-scaled convs, BatchNorm statistics near identity), with
     update_block.flow_head.conv2 scaled down so that 20 iterations stay bounded."""
-    sd = _seeded(raft_param_shapes(), seed)
+    sd = flow_core.seeded_state_dict(raft_param_shapes(), seed)
     for k in ("update_block.flow_head.conv2.weight", "update_block.flow_head.conv2.bias"):
         sd[k] = sd[k] * 0.05
     return sd
@@ -59,42 +59,23 @@ def check_size(H, W):
         raise ValueError(f"RAFT needs H/64 >= 2 and W/64 >= 2 (a 1-pixel coarsest correlation level gives NaN in the reference), got {H}x{W}")
 
 
-class _FNet(EncoderEngine):
-    """The instance-norm encoder with the stem in f32 up to the normalisation (tcl_conv7x7s2_instnorm_f16)."""
-
-    def _stem(self, img):
-        B, _, H, W = img.shape
-        h, w = (H - 1) // 2 + 1, (W - 1) // 2 + 1
-        x = torch.empty(B * h * w, 64, dtype=H16, device=self.dev)
-        ws = torch.empty(self.L.tcl_stem_instnorm_workspace_bytes(B, H, W), dtype=torch.uint8, device=self.dev)
-        self.L.tcl_conv7x7s2_instnorm_f16(img.float().contiguous(), self.stem[0], self.stem[1], x, B, H, W, 1e-5, ws, stream())
-        return x, h, w
-
-
-def _conv3(w, b, co_pad, dev):
-    """3x3 conv weights for tcl_conv3x3_f16: [co_pad, 9*ci] tap-major f16, bias [co_pad] f16 (zero rows for the padding)."""
-    co, ci = w.shape[:2]
-    w = _pad_to(w, 0, co_pad)
-    return (w.permute(0, 2, 3, 1).reshape(co_pad, 9 * ci).to(H16).contiguous().to(dev), _pad_to(b, 0, co_pad).to(H16).contiguous().to(dev), ci, co_pad)
-
-
-class RAFTEngine:
+class RAFTEngine(FlowEngine):
     """RAFT (raft.py:73-131) on the device for B >= 1 independent pairs."""
 
     def __init__(self, state_dict, device, iters=ITERS):
         missing = [k for k in raft_param_shapes() if k not in state_dict]
         if missing:
             raise KeyError(f"RAFT state dict lacks {len(missing)} keys, e.g. {missing[:3]}")
-        self.dev, self.L, self.iters = torch.device(device), lib(), iters
-        d = self.dev
-        self.fnet = _FNet(state_dict, "fnet.", "instance", d)
+        super().__init__(device)
+        d, self.iters = self.dev, iters
+        self.fnet = EncoderEngine(state_dict, "fnet.", "instance", d, f32_stem=True)
         self.cnet = EncoderEngine(state_dict, "cnet.", "batch", d)
         f = {k[len("update_block."):]: v.float() for k, v in state_dict.items() if k.startswith("update_block.")}
-        self.convc1 = _Lin(f["encoder.convc1.weight"], f["encoder.convc1.bias"], d)                       # 324 -> 384 padded input channels
-        self.convc2 = _conv3(f["encoder.convc2.weight"], f["encoder.convc2.bias"], 192, d)
+        self.convc1 = Lin(f["encoder.convc1.weight"], f["encoder.convc1.bias"], d)                       # 324 -> 384 padded input channels
+        self.convc2 = self._conv3w(f["encoder.convc2.weight"], f["encoder.convc2.bias"], 192)
         self.convf1 = (f["encoder.convf1.weight"].reshape(128, 98).t().contiguous().to(d), f["encoder.convf1.bias"].contiguous().to(d))
-        self.convf2 = _conv3(f["encoder.convf2.weight"], f["encoder.convf2.bias"], 64, d)
-        self.conv = _conv3(f["encoder.conv.weight"], f["encoder.conv.bias"], 128, d)                       # 126 + 2 zero channels (the flow goes there)
+        self.convf2 = self._conv3w(f["encoder.convf2.weight"], f["encoder.convf2.bias"], 64)
+        self.conv = self._conv3w(f["encoder.conv.weight"], f["encoder.conv.bias"], 128)                       # 126 + 2 zero channels (the flow goes there)
         self.gru = []
         for dn in ("1", "2"):
             taps = lambda g: f[f"gru.conv{g}{dn}.weight"].reshape(128, 384, 5).permute(0, 2, 1)            # [co, tap, ci]: ci = h | inp | motion
@@ -108,23 +89,12 @@ class RAFTEngine:
 
             bzr = torch.cat([f[f"gru.convz{dn}.bias"], f[f"gru.convr{dn}.bias"]]).contiguous().to(d)
             self.gru.append(dict(w_zr=hm(zr), w_q=hm(q), c_zr=ctx(zr), c_q=ctx(q), b_zr=bzr, b_q=f[f"gru.convq{dn}.bias"].contiguous().to(d)))
-        self.fh1 = _conv3(f["flow_head.conv1.weight"], f["flow_head.conv1.bias"], 256, d)
-        self.fh2 = _conv3(f["flow_head.conv2.weight"], f["flow_head.conv2.bias"], 64, d)                  # 2 channels + zero padding
-        self.mask0 = _conv3(f["mask.0.weight"], f["mask.0.bias"], 256, d)
-        self.mask2 = _Lin(f["mask.2.weight"], f["mask.2.bias"], d)
+        self.fh1 = self._conv3w(f["flow_head.conv1.weight"], f["flow_head.conv1.bias"], 256)
+        self.fh2 = self._conv3w(f["flow_head.conv2.weight"], f["flow_head.conv2.bias"], 64)                  # 2 channels + zero padding
+        self.mask0 = self._conv3w(f["mask.0.weight"], f["mask.0.bias"], 256)
+        self.mask2 = Lin(f["mask.2.weight"], f["mask.2.bias"], d)
 
     # ---- building blocks
-    def _c3(self, x, spec, B, h, w, relu):
-        wt, b, ci, co = spec
-        y = torch.empty(B * h * w, co, dtype=H16, device=self.dev)
-        self.L.tcl_conv3x3_f16(x, wt, b, 0, y, B, h, w, ci, co, 1, 1, 0, 0, 3 if relu else 0, stream())
-        return y
-
-    def _gemm(self, x, lin, M, act=0):
-        y = torch.empty(M, lin.co, dtype=H16, device=self.dev)
-        self.L.tcl_gemm_f16(x, lin.w, lin.b, 0, y, M, lin.co, lin.ci, lin.ci, lin.ci, lin.co, lin.co, act, stream())
-        return y
-
     def context_fold(self, inp, B, h, w):
         """The inp share of the six GRU convolutions + their biases, f32 per pixel: [(gate [P,256], cand [P,128]) for the 1x5 and the 5x1 half]."""
         P, out = B * h * w, []
@@ -173,11 +143,9 @@ class RAFTEngine:
         # one CorrBlock per pair: the lookup that shares neighbour rows between 8 x 8 pixel tiles serves one entry at a time
         f1, f2 = f1.float().view(B, h, w, 256), f2.float().view(B, h, w, 256)
         corrs = [CorrBlock.from_nhwc(f1[j:j + 1], f2[j:j + 1]) for j in range(B)]
-        net = torch.empty(P, 128, dtype=H16, device=d); inp = torch.empty(P, 128, dtype=H16, device=d)
-        L.tcl_context_split_f16(c, net, inp, P, stream())
+        net, inp = self._context_split(c, P)
         fold = self.context_fold(inp, B, h, w)
-        ys, xs = torch.meshgrid(torch.arange(h, device=d).float(), torch.arange(w, device=d).float(), indexing="ij")
-        coords0 = torch.stack([xs, ys])[None].expand(B, 2, h, w).contiguous()
+        coords0 = self.coords_grid(B, h, w)
         coords1 = coords0.clone() if flow_init is None else (coords0 + flow_init.to(d).float()).contiguous()
         corr_rows = torch.zeros(P, 384, dtype=H16, device=d)              # 324 channels + zero padding
         fl1 = torch.empty(P, 128, dtype=H16, device=d)
@@ -199,11 +167,7 @@ class RAFTEngine:
             delta = self._c3(self._c3(net, self.fh1, B, h, w, True), self.fh2, B, h, w, False)               # [P,64]: 2 + zero padding
             L.tcl_rows_f16_to_nchw_f32(delta, coords1, B, 2, h * w, 64, 0, 1.0, 1.0, stream())
         # the mask of the last iteration only (the reference computes it on every one and returns the last up-sampling)
-        mask = self._gemm(self._c3(net, self.mask0, B, h, w, True), self.mask2, P)                            # [P,576]; x0.25 in the kernel
-        flow_low = coords1 - coords0
-        up = torch.empty(B, 2, 8 * h, 8 * w, dtype=torch.float32, device=d)
-        L.tcl_upsample_flow_f32(flow_low.contiguous(), mask, 576, 0.25, up, B, h, w, stream())
-        return flow_low, up
+        return self._upsample(net, coords0, coords1, B, h, w)
 
 
 def useful_flops(H, W, iters=ITERS):

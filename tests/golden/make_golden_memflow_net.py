@@ -8,12 +8,11 @@ import numpy as np
 import torch
 
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..")
+sys.path.insert(0, ROOT)
+from tc_light_amd import flow_core as FC, memflow as MF  # noqa: E402  (shapes / seeded weights only; the library loads lazily, none is needed here)
+
 sys.path.insert(0, "/root/reference/utils/evaluation/memflow")
 from core.Networks.MemFlowNet.cnn import BasicEncoder  # noqa: E402
-
-src = open(os.path.join(ROOT, "tc_light_amd", "memflow.py")).read()
-ns = {}
-exec(compile(src.replace("from .lib import lib, stream", "lib = stream = None"), "memflow_shapes", "exec"), ns)    # shapes / seeded weights only
 
 out = {}
 g = np.random.default_rng(9)
@@ -21,9 +20,9 @@ img = torch.from_numpy((g.random((2, 3, 64, 96)) * 2 - 1).astype(np.float32))
 out["img"] = img.numpy()
 for name, norm, seed in (("fnet", "instance", 21), ("cnet", "batch", 22)):
     m = BasicEncoder(output_dim=256, norm_fn=norm).eval()
-    shapes = ns["encoder_param_shapes"]("", norm)
+    shapes = FC.encoder_param_shapes("", norm)
     assert set(shapes) == set(m.state_dict().keys()), (set(shapes) ^ set(m.state_dict().keys()))
-    m.load_state_dict(ns["seeded_state_dict"](shapes, seed), strict=True)
+    m.load_state_dict(FC.seeded_state_dict(shapes, seed), strict=True)
     with torch.no_grad():
         out[name] = m(img).numpy()
     out[name + "_seed"] = seed
@@ -53,9 +52,9 @@ icfg = Cfg(mem_every=1, enable_long_term=False, enable_long_term_count_usage=Tru
            val_decoder_depth=15, train_avg_length=TAL, top_k=None)
 SEED = 31
 net = MemFlowNet(cfg).eval()
-shapes = ns["memflow_param_shapes"]()
+shapes = MF.memflow_param_shapes()
 assert set(shapes) == set(net.state_dict().keys())
-net.load_state_dict(ns["seeded_state_dict"](shapes, SEED), strict=True)
+net.load_state_dict(MF.seeded_state_dict(shapes, SEED), strict=True)
 proc = InferenceCore(net, config=icfg)
 frames = torch.from_numpy((np.random.default_rng(13).random((4, 3, 128, 192)) * 2 - 1).astype(np.float32))
 # smooth the frames a little and make consecutive frames related (shifted copies + noise) so the flow is not pure noise

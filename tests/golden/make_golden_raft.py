@@ -11,6 +11,9 @@ import torch
 
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..")
 REF = "/root/reference"
+sys.path.insert(0, ROOT)
+from tc_light_amd import raft as TR  # noqa: E402  (shapes / seeded weights only; the library loads lazily, none is needed here)
+
 sys.path.insert(0, REF)
 sys.path.insert(0, os.path.join(REF, "utils", "evaluation"))
 
@@ -42,24 +45,14 @@ def import_with_stubs(modname):
 
 RAFT = import_with_stubs("core.raft").RAFT
 
-src = open(os.path.join(ROOT, "tc_light_amd", "memflow.py")).read()
-ns = {}
-exec(compile(src.replace("from .lib import lib, stream", "lib = stream = None"), "memflow_shapes", "exec"), ns)    # shapes / seeded weights only
-rsrc = open(os.path.join(ROOT, "tc_light_amd", "raft.py")).read()
-rsrc = rsrc.replace("from .lib import lib, stream", "lib = stream = None")
-rsrc = rsrc.replace("from .memflow import CorrBlock, EncoderEngine, _Lin, _pad_to, encoder_param_shapes, seeded_state_dict as _seeded",
-                    "CorrBlock = _Lin = _pad_to = None\nEncoderEngine = object")
-rns = dict(encoder_param_shapes=ns["encoder_param_shapes"], _seeded=ns["seeded_state_dict"])
-exec(compile(rsrc, "raft_shapes", "exec"), rns)
-
 torch.manual_seed(0)
 torch.set_num_threads(min(16, os.cpu_count() or 8))
 SEED = 5
 model = RAFT(argparse.Namespace(small=False, mixed_precision=False, alternate_corr=False)).eval()
 ref_sd = model.state_dict()
-shapes = rns["raft_param_shapes"]()
+shapes = TR.raft_param_shapes()
 assert set(shapes) == set(ref_sd) and all(tuple(ref_sd[k].shape) == tuple(s) for k, s in shapes.items())
-model.load_state_dict(rns["seeded_state_dict"](SEED), strict=True)
+model.load_state_dict(TR.seeded_state_dict(SEED), strict=True)
 
 out = {"seed": SEED, "keys": np.array(";".join(f"{k}:{','.join(map(str, v.shape))}" for k, v in ref_sd.items()))}
 g = np.random.default_rng(17)

@@ -111,34 +111,33 @@ def test_estimate_flows_vs_oracle_driver(dev):
                 prev[is_future] = MF.forward_interpolate(low[0])[None].to(dev)
 
 
-def test_step_graph_replay_equals_eager(dev, monkeypatch):
-    """Round 6: with TCL_MEMFLOW_GRAPH=1 MemFlowEngine.step replays a captured HIP graph from the third step of a shape on (first eager, second captured).  Ten frame pairs through one
-    working memory with warm starts, graphs on against TCL_MEMFLOW_GRAPH=0: every flow bit-identical, and the graph path really replayed (>= 6 replays)."""
+def test_step_one_pass_attention_vs_oracle(dev):
+    """A 136x200 pair has P = 17 * 25 = 425 positions: no chunk count divides T = 425 or 850 into multiples of 64 keys, so
+    hostlogic.memflow_splitkv_chunks gives 0 and the memory read runs on the one-pass kernel.  Two steps (the second reads a working memory of two
+    frames) against oracle.memflow.InferenceCore on the seeded weights, at the bound of this chain: rel-L2 < 1.5e-2 on flow_up."""
+    from oracle import memflow as OM
     from tc_light_amd import memflow as MF
-    G = np.load(os.path.join(os.path.dirname(__file__), "golden", "memflow_full.npz"))
-    sd = MF.seeded_state_dict(MF.memflow_param_shapes(), int(G["seed"]))
-    frames = torch.from_numpy(G["frames"]).to(dev)
-    n = frames.shape[0]
-
-    def run(graph):
-        monkeypatch.setenv("TCL_MEMFLOW_GRAPH", "1" if graph else "0")             # (opt-in: measured no faster, profiles/r6_ab_memflow_graph_nw.txt)
-        eng, outs, init = MF.MemFlowEngine(sd, dev), [], None
-        for i in range(10):
-            a, b = frames[i % n], frames[(i * 3 + 1) % n]
-            low, up = eng.step(torch.stack([a, b])[None], flow_init=init)
-            outs.append((low.clone(), up.clone()))
-            init = (0.5 * low).contiguous()                                    # a device-side warm start (the driver's scipy one is host work)
-        torch.cuda.synchronize()
-        return outs, eng
-    o1, e1 = run(True)
-    o0, _ = run(False)
-    for i, ((l1, u1), (l0, u0)) in enumerate(zip(o1, o0)):
-        assert torch.equal(l1, l0) and torch.equal(u1, u0), i
-    replayed = [v for v in e1._graphs.values() if isinstance(v, dict)]
-    assert len(replayed) >= 1 and len(e1._graphs) <= 3, e1._graphs.keys()
+    from tc_light_amd.hostlogic import memflow_splitkv_chunks
+    assert memflow_splitkv_chunks(425, 425) == 0 and memflow_splitkv_chunks(425, 850) == 0
+    sd = MF.seeded_state_dict(MF.memflow_param_shapes(), 31)
+    g = torch.Generator().manual_seed(14)
+    noise = torch.rand(3, 3, 136, 200, generator=g) * 2 - 1
+    base = torch.nn.functional.avg_pool2d(noise[0:1], 5, 1, 2)
+    frames = torch.cat([torch.roll(base, (k, 2 * k), (2, 3)) + 0.05 * noise[k:k + 1] for k in range(3)])     # shifted copies + a little noise
+    eng, core = MF.MemFlowEngine(sd, dev), OM.InferenceCore(sd)
+    with torch.no_grad():
+        for i in range(2):
+            pair = torch.stack([frames[i], frames[i + 1]])[None]
+            low, up = eng.step(pair.to(dev))
+            low_o, up_o = core.step(pair)
+            assert tuple(up.shape) == (1, 2, 136, 200) and tuple(low.shape) == (1, 2, 17, 25)
+            err = ((up.cpu() - up_o).norm() / up_o.norm()).item()
+            print(f"[one-pass memory read] step {i}, T = {425 * (i + 1)}: flow_up rel-L2 {err:.2e}")
+            assert err < 1.5e-2, (i, err)
+    assert eng.mem_k.shape[0] == 425                                                    # two frames were held, then compressed to the last one
 
 
-def test_corr_lookup_tiled_rows_vs_per_pixel_kernel(dev, monkeypatch):
+def test_corr_lookup_tiled_rows_vs_per_pixel_kernel(dev):
     """Round 6: lookup_rows through the tile-sharing kernel (f16 feature maps, 8 x 8 pixel tiles share one bounding box of neighbour rows in LDS) against the
     per-pixel f32 kernel on the SAME f16-representable features (the encoder's outputs are f16): (a) a smooth flow -- every tile compact, no fallback; (b) the
     same plus a few torn tiles and windows hanging over every image border -- those tiles take the per-pixel route inside the same call; a 2.6x zoom whose tile
@@ -164,11 +163,9 @@ def test_corr_lookup_tiled_rows_vs_per_pixel_kernel(dev, monkeypatch):
         co = co.to(dev).contiguous()
         rows_t = torch.zeros(H * W, 384, dtype=torch.float16, device=dev)
         rows_p = torch.zeros_like(rows_t)
-        monkeypatch.setenv("TCL_CORR_TILED", "1")
-        cb.lookup_rows(co, rows_t)
+        cb.lookup_rows(co, rows_t, tiled=True)
         fb = int(cb._flags.sum().item())
-        monkeypatch.setenv("TCL_CORR_TILED", "0")
-        cb.lookup_rows(co, rows_p)
+        cb.lookup_rows(co, rows_p, tiled=False)
         torch.cuda.synchronize()
         a, b = rows_t.float().cpu(), rows_p.float().cpu()
         assert torch.equal(a[:, 324:], b[:, 324:])                                     # padding channels untouched

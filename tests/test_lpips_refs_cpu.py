@@ -116,8 +116,9 @@ def test_border_rule_padding_after_scaling(state):
 # ---------------------------------------------------------------------------------------------------------------- the padder, [:-1]
 @pytest.mark.parametrize("H,W,amounts", [(36, 52, (2, 2, 2, 2)), (37, 53, (1, 2, 1, 2)), (40, 56, (0, 0, 0, 0)), (33, 49, (3, 4, 3, 4))])
 def test_padder_vs_hand_written(H, W, amounts):
-    from tc_light_amd.lpips import pad8_amounts, pad8_u8
-    from tc_light_amd.memflow import _pad8
+    from tc_light_amd.flow_core import pad8
+    from tc_light_amd.hostlogic import pad8_amounts
+    from tc_light_amd.lpips import pad8_u8
     l, r, t, b = amounts
     assert pad8_amounts(H, W) == amounts
     g = np.random.default_rng(H)
@@ -131,7 +132,7 @@ def test_padder_vs_hand_written(H, W, amounts):
     assert got.dtype == torch.uint8 and got.is_contiguous() and np.array_equal(got.numpy(), want)
     nchw = torch.from_numpy(x).permute(0, 3, 1, 2).double()
     assert np.array_equal(R.pad8(nchw).permute(0, 2, 3, 1).numpy(), want.astype(np.float64))
-    ref, pad = _pad8(nchw)
+    ref, pad = pad8(nchw)
     assert tuple(pad) == amounts and np.array_equal(ref.permute(0, 2, 3, 1).numpy(), want.astype(np.float64))
 
 

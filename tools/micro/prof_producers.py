@@ -45,13 +45,11 @@ def gemm_prof(fn):
 
 if "memflow" in a.what:
     eng = MF.MemFlowEngine(MF.seeded_state_dict(MF.memflow_param_shapes(), 31), dev)
-    MF.estimate_flows(eng, fr[:4], warm_start=False)                      # tiles of its shapes tuned / tabled, panels allocated, step graphs captured
+    MF.estimate_flows(eng, fr[:4], warm_start=False)                      # tiles of its shapes tuned / tabled, panels allocated
     torch.cuda.synchronize(); t0 = time.perf_counter()
     MF.estimate_flows(eng, fr, warm_start=False)
     torch.cuda.synchronize(); dt_graph = time.perf_counter() - t0
-    os.environ["TCL_MEMFLOW_GRAPH"] = "0"                                 # eager launches: what round 5 timed, and the only mode the launch profiler can bracket
     (fut, past), dt, ms, fl, cnt = gemm_prof(lambda: MF.estimate_flows(eng, fr, warm_start=False))
-    os.environ.pop("TCL_MEMFLOW_GRAPH")
     pairs = 2 * (a.frames - 1)
     res["memflow"] = {"pairs": pairs, "ms_per_pair": dt_graph / pairs * 1e3, "ms_per_pair_eager_launches": dt / pairs * 1e3,
                       "gemm_class_tflop_per_pair": fl / pairs / 1e12, "gemm_class_launches_per_pair": cnt / pairs,
