@@ -658,6 +658,33 @@ int tcl_voxel_keys(const float* mean_rgb, const float* mean_xyz, const float* xy
 size_t tcl_unique_rows_workspace_bytes(size_t n);
 int tcl_unique_rows_i32(const int* keys, size_t n, int C, int* inv, int* count, void* ws, hipStream_t st);
 
+/* ===================================================================== detail transfer (generation.detail_transfer); csrc/detail.hip */
+/* tcl_detail_transfer_f32 (replaces the "detail transfer" node of IC-Light workflows -- two Gaussian blurs and a handful of element-wise image
+ *   operations): src S, relit R [N,3,H,W] f32 in [0,1], mask m [N,1,H,W] f32 in [0,1] or NULL (= 1 everywhere) -> out O [N,3,H,W] f32; all frames in
+ *   one call, every frame on its own.  h_taps is a HOST array of n_taps = 2*radius + 1 floats in [0, 1] (detail.gaussian_taps: exp(-k^2 / 2 sigma^2)
+ *   normalised in f64, rounded once to f32), copied into the kernel arguments.  G below is the separable blur with those taps, rows first, then
+ *   columns, borders reflected without repeating the edge sample (index -i -> i, L-1+i -> L-1-i).  Each 1-D pass is  a = 0; for k = 0 .. 2r:
+ *   a = fmaf(w_k, v_k, a)  in ascending index order; the intermediate between the passes is f32 (the workspace).  Everything else in f32 with no fma
+ *   contraction, IEEE division; Y(x) = fmaf(0.114f, x_B, fmaf(0.587f, x_G, 0.299f * x_R));  bm = blend * m (blend when mask is NULL):
+ *     TCL_DETAIL_ADD    D = S - R;  P = D - G(D) per channel (luma: P = Y(D) - G(Y(D)), the same for the three channels);
+ *                       O = min(max(R + bm * P, 0), 1).  S == R gives D = +0, G(D) = +0, P = 0 and O = R bit for bit for R in [0,1].
+ *     TCL_DETAIL_RATIO  q = (G(R) + e) / (G(S) + e) per channel, e = 1.f/255.f (luma: of G(Y(R)) and G(Y(S)), one q for the three channels);
+ *                       T = S * q;  O = min(max(R + bm * (T - R), 0), 1).
+ *   ws: tcl_detail_transfer_workspace_bytes(N, H, W, mode, luma) bytes = N * planes * H * W * 4 with planes 3 | 1 (add rgb | luma) and 6 | 2 (ratio);
+ *   the size is 0 for arguments the call would refuse.  out and ws may alias neither each other nor an input.
+ *   Two launches: rows (one block per TCL_DETAIL_ROW_SEG pixels of a row) and columns fused with the combine (one block per TCL_DETAIL_TILE_W x
+ *   TCL_DETAIL_TILE_H tile).  TCL_EINVAL, with nothing launched or written: null pointers (mask excepted), N, H, W <= 0, radius outside
+ *   1 .. TCL_DETAIL_MAX_RADIUS, n_taps != 2*radius + 1, radius >= min(H, W), an unknown mode, luma other than 0 / 1, blend outside [0,1] or NaN, a tap
+ *   outside [0,1], a workspace that is too small, aliasing as above, N > 21845 or H > 65535. */
+#define TCL_DETAIL_ROW_SEG 256
+#define TCL_DETAIL_TILE_W 64
+#define TCL_DETAIL_TILE_H 32
+#define TCL_DETAIL_MAX_RADIUS 48
+enum { TCL_DETAIL_ADD = 0, TCL_DETAIL_RATIO = 1 };
+size_t tcl_detail_transfer_workspace_bytes(int N, int H, int W, int mode, int luma);
+int tcl_detail_transfer_f32(const float* src, const float* relit, const float* mask, float* out, int N, int H, int W, const float* h_taps, int n_taps,
+                            int radius, int mode, int luma, float blend, void* ws, long ws_bytes, hipStream_t st);
+
 #ifdef __cplusplus
 }
 #endif

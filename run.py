@@ -12,6 +12,8 @@ become normal.npy / normal.mp4 (per-frame surface normals), relit_<side>.npy and
 conditioning of the xy passes is the blend of its two neighbouring keyframes' embeddings; -p / generation.prompt still names the run.
 [--ip_image PATH] [--ip_scale S] (generation.ip_adapter: {image, scale, path}): IP-Adapter -- the relight is steered towards a reference photograph;
 its CLIP ViT-H/14 embedding (models.image_encoder) becomes 4 image tokens every text cross-attention of the xy passes also attends to (models.ip_adapter).
+[--detail [SIGMA]] [--detail_mode add|ratio] [--detail_blend B] (generation.detail_transfer: {sigma, mode, blend, channels}): detail transfer -- the last
+step gives the relit frames the source's high frequencies (texture, small text, faces) back and keeps the relight's low ones (the new light).
 data.scene_type picks the parser (generate.py:84-95): video (VideoDataParser) or sceneflow (SceneFlowDataParser: ground-truth depth, poses and
 flows -> voxelised Unique Video Tensor ids); carla and interiornet are not built.
 
@@ -33,8 +35,8 @@ import torch
 from tc_light_amd.config_utils import Config, load_config, save_config
 from tc_light_amd.dataparser import VideoDataParser, get_frame_ids, save_loss_curve, save_video
 from tc_light_amd.generate import DEFAULTS, Generator
-from tc_light_amd.hostlogic import (RESOLVED_KEYS, check_highres_tokens, check_ip_adapter, cond_channels, fbc_background_per_frame, highres_size,
-                                    light_angles, prompt_table, resolve_generation)
+from tc_light_amd.hostlogic import (RESOLVED_KEYS, check_detail, check_highres_tokens, check_ip_adapter, cond_channels, fbc_background_per_frame,
+                                    highres_size, light_angles, prompt_table, resolve_generation)
 from tc_light_amd.model_utils import allow_random, init_iclight
 from tc_light_amd.parallel import Dist
 from tc_light_amd.text import encode_prompt_pair, encode_prompt_set
@@ -81,6 +83,11 @@ def resolve_options(config):
     o.ip_block = check_ip_adapter(opts["ip_adapter"], g.normal, models, allow_random(models))
     if o.ip_block is not None:
         g.ip_adapter = Config({k: o.ip_block[k] for k in ("image", "scale", "path")})      # what config.yaml records
+    # detail transfer (generation.detail_transfer; --detail / --detail_mode / --detail_blend): a malformed block, generation.normal beside it and fbc
+    # without its matte are refused too; the normalised block is what config.yaml records
+    o.detail = check_detail(opts["detail_transfer"], normal=bool(g.normal), iclight_model=r["iclight_model"], fbc_matting=opts["fbc_matting"])
+    if o.detail is not None:
+        g.detail_transfer = Config(o.detail)
     if o.light and o.fbc:
         print("[INFO] generation.light_path: the per-frame ramps are the backgrounds; generation.background_image_path is not consulted.")
     o.upload = o.fbc and not o.normal and not o.light and g.bg_source in ("upload", "upload_flip")      # fbc is conditioned on a background file
@@ -286,7 +293,8 @@ def main(argv=None):
             fut, past = flows
             masks, inv, k = soft_masks_and_ids(clip.frames_out, fut, past, alpha=clip.parser.alpha)
         out, info = gen(clip.frames[lo:hi], conds, conds_t, past, masks, inv, n_total=n, k=k, background=background,
-                        frames_hr=clip.frames_out[lo:hi] if o.highres else None, background_per_frame=bg_per_frame)
+                        frames_hr=clip.frames_out[lo:hi] if o.highres else None, background_per_frame=bg_per_frame,
+                        source=clip.frames_out if o.detail is not None else None)
         if d.rank == 0:
             save_relit_run(config, o, name, out, info, clip)
     if d.world > 1:

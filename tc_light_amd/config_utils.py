@@ -9,7 +9,8 @@ import yaml
 
 
 # keys a YAML may leave out and that are not generation.* / post_opt.* settings of the Generator (those: generate.DEFAULTS)
-DEFAULTS = dict(generation=dict(ip_adapter=None),                       # IP-Adapter off; else {image, scale, path} (hostlogic.check_ip_adapter)
+DEFAULTS = dict(generation=dict(ip_adapter=None,                        # IP-Adapter off; else {image, scale, path} (hostlogic.check_ip_adapter)
+                                detail_transfer=None),                  # detail transfer off; else {sigma, mode, blend, channels} (hostlogic.check_detail)
                 models=dict(ip_adapter="", image_encoder=""))           # ip-adapter_sd15.safetensors / .bin; a CLIP ViT-H/14 vision snapshot directory
 
 
@@ -112,6 +113,13 @@ def load_config(argv=None, print_config=True):
     ap.add_argument("--ip_image", type=str, default=None, help="a reference image the relight is steered towards through IP-Adapter "
                     "(models.ip_adapter, models.image_encoder): generation.ip_adapter.image, for a fast usage")
     ap.add_argument("--ip_scale", type=float, default=None, help="weight of the image attention in [0, 2] (generation.ip_adapter.scale), for a fast usage")
+    # detail transfer: the source's high frequencies back onto the relit frames (generation.detail_transfer, generate.py DEFAULTS)
+    ap.add_argument("--detail", type=float, nargs="?", const=3.0, default=None, metavar="SIGMA",
+                    help="give the relit frames the source's detail back, the blur's sigma in [0.5, 16] (3 when left out): "
+                    "generation.detail_transfer.sigma, for a fast usage")
+    ap.add_argument("--detail_mode", choices=("add", "ratio"), default=None, help="add: the source's high-pass is added; ratio: the source times the "
+                    "ratio of the two blurs (generation.detail_transfer.mode), for a fast usage")
+    ap.add_argument("--detail_blend", type=float, default=None, help="strength of the step in [0, 1] (generation.detail_transfer.blend), for a fast usage")
     a = ap.parse_args(argv)
     cfg = load_yaml_chain(a.config, a.base_config)
     if a.ip_image is not None or a.ip_scale is not None:
@@ -121,6 +129,13 @@ def load_config(argv=None, print_config=True):
         if a.ip_scale is not None:
             block["scale"] = a.ip_scale
         cfg.generation.ip_adapter = block
+    if a.detail is not None or a.detail_mode is not None or a.detail_blend is not None:
+        block = cfg.generation.get("detail_transfer")
+        block = Config(dict(sigma=block) if isinstance(block, (int, float)) and not isinstance(block, bool) else (block or {}))
+        for key, v in (("sigma", a.detail), ("mode", a.detail_mode), ("blend", a.detail_blend)):
+            if v is not None:
+                block[key] = v
+        cfg.generation.detail_transfer = block
     if a.prompt_sweep is not None:
         cfg.generation.prompt_path = [[0.0, a.prompt_sweep[0]], [1.0, a.prompt_sweep[1]]]
     if a.light_sweep is not None:

@@ -82,6 +82,11 @@ DEFAULTS = dict(  # configs/tclight_default.yaml (generation / post_opt sections
     #   tokens, and every text cross-attention of the xy passes -- the highres refine included -- adds scale * Attention(q, K_ip, V_ip)
     #   (tcl_attention_ip_add_f16); the yt passes do not (a y-t slice is not an image the photograph describes).  The Generator takes the tokens as
     #   image_prompt= (ip_adapter.build).  None (default): nothing of it is consulted and every path is what it was.
+    detail_transfer=None,
+    # ^ detail transfer: {sigma, mode: add | ratio, blend, channels: rgb | luma} or a bare sigma (HL.check_detail).  The last step of __call__, behind
+    #   stage 1 / 2: the returned frames keep their low frequencies (the new light) and take the high ones (texture, small text, faces) from the source
+    #   frames handed in as source= -- one tcl_detail_transfer_f32 call over all frames (detail.py), weighted by the matting alpha under fbc.
+    #   None (default): nothing of it is consulted and every path is what it was.
     max_tokens_per_pass=None)
     # ^ level-0 tokens (samples x pixels) one block-major UNet pass may carry; longer chunk lists are split into consecutive groups.  None:
     #   TCL_MAX_TOKENS_PER_PASS (read when the Generator is built), else min(16 M, 80 % of the device's free memory / 10.5 KB) -- a pass peaks at
@@ -114,6 +119,9 @@ class Generator:
         self.cfg = SimpleNamespace(**cfg)
         self.fbc, self.light, self.img2img, self.highres = r["fbc"], r["light"], r["img2img"], r["highres"]
         self.normal_sides = r["normal_sides"]                                      # () unless generation.normal
+        # the caller's check, as check_ip_adapter is: not part of resolve_generation's result
+        self.cfg.detail_transfer = HL.check_detail(cfg["detail_transfer"], normal=bool(cfg["normal"]), iclight_model=r["iclight_model"],
+                                                   fbc_matting=cfg["fbc_matting"])
         self.schedule, self.schedule_highres = r["schedule"], r["schedule_highres"]      # (scheduler steps, begin index, steps executed)
         self.unet, self.vae, self.rmbg = unet, vae, rmbg
         self.dev = unet.dev
@@ -133,6 +141,7 @@ class Generator:
         self.n_total = None                # the run's frames over all ranks (_total); a caller may assign it before prepare_data
         self.bg_index = None               # fbc under light_path: the image of bg_frames that is each frame's background (None: bg_frames as they are)
         self._bg_per_frame = None          # fbc: is the background one frame per frame?  The entry point says (None: by the length of its latents)
+        self.fbc_alpha = None              # fbc with matting: the alpha of this rank's frames (prepare_fbc), the weight of detail_transfer
         cin = getattr(self.unet, "w", {}).get("conv_in", (None, None, None))[2]      # a stand-in engine may carry no weights
         if cin is not None and cin != 4 + HL.cond_channels(c.iclight_model):
             raise ValueError(f"generation.iclight_model {c.iclight_model}: the UNet's conv_in takes {cin} channels, expected "
@@ -259,7 +268,7 @@ class Generator:
         (bg_source).  A background of one frame serves every frame and is encoded once."""
         c = self.cfg
         n, _, H, W = frames.shape
-        self.fg_frames, _ = self.foreground(frames)
+        self.fg_frames, self.fbc_alpha = self.foreground(frames)
         self.bg_index = None
         if self.light:                     # bg_frames = the DISTINCT ramps of this rank's frames; __call__ encodes those and gathers the latents
             self.bg_frames, index, several = self.light_images(n, H, W)
@@ -660,7 +669,7 @@ class Generator:
 
     # ------------------------------------------------------------------ end to end
     def __call__(self, frames, conds, conds_t, past_flows, mask_bwds, unq_inv, n_total=None, k=None, background=None, frames_hr=None,
-                 background_per_frame=None):
+                 background_per_frame=None, source=None):
         """frames: local block [n_local,3,H,W]; conds / conds_t: [2,L,768] f16 (uncond, cond) text embeddings for the xy / yt
         passes (generate.py:553-555) -- under generation.prompt_path conds is the FrameText of frame_text; past_flows / mask_bwds / unq_inv: stage-2 inputs for ALL frames (device).
         Returns (relit frames [N,3,H,W] f32, info dict).
@@ -668,13 +677,19 @@ class Generator:
         and so do the returned frames.
         With generation.iclight_model fbc: background [1|n_local,3,H,W] is the bg_source upload / upload_flip image (one frame for all, or this
         rank's block of a per-frame clip); background_per_frame says which when the block alone cannot (None: more than one frame handed in) --
-        every rank must give the same answer, since a per-frame background is all-gathered for the yt pass."""
+        every rank must give the same answer, since a per-frame background is all-gathered for the yt pass.
+        With generation.detail_transfer: source [N,3,H,W] f32 in [0,1] holds the source frames of ALL ranks at the size of the result (the final size
+        under the highres pass); see detail_step."""
         c, d = self.cfg, self.dist
         if self.highres and background is not None:
             raise ValueError("generation.background_cond together with generation.highres_scale > 1 is not supported")
         self._total(frames.shape[0], n_total, keep=False)
         if (c.prompt_path is not None) != isinstance(conds, FrameText) or (isinstance(conds, FrameText) and len(conds.index) != frames.shape[0]):
             raise ValueError("generation.prompt_path: conds must be the FrameText of Generator.frame_text for this rank's frames (and only then)")
+        detail = c.detail_transfer is not None and c.detail_transfer["blend"] > 0.0      # blend 0: nothing runs, the frames are returned as they are
+        if detail and (source is None or source.dim() != 4 or source.shape[0] != self.n_total):
+            raise ValueError(f"generation.detail_transfer: source frames {None if source is None else tuple(source.shape)}, expected all "
+                             f"{self.n_total} frames of the run at the size of the result (Generator(...)(..., source=...))")
         ev = self._now
         t0 = ev()
         self.prepare_data(frames, background)
@@ -700,17 +715,44 @@ class Generator:
         if c.apply_opt:
             clean, losses1, losses2, t4 = self.post_optimize(clean, mode, shard, past_flows, mask_bwds, unq_inv, k)
             t5 = ev()
-        self.timing = dict(encode=t1 - t0, denoise=t2a - t1, decode=t3 - t2, stage1=t4 - t3, stage2=t5 - t4, total=t5 - t0)
-        info = dict(timing=self.timing, losses_exposure=losses1, losses_unique=losses2, total_time=t5 - t0,
-                    sec_per_frame=(t5 - t0) / self.n_total, total_number_of_frames=self.n_total, init_latent=c.init_latent,
+        t6 = t5
+        if detail:
+            clean = self.detail_step(clean, source)
+            t6 = ev()
+        self.timing = dict(encode=t1 - t0, denoise=t2a - t1, decode=t3 - t2, stage1=t4 - t3, stage2=t5 - t4, total=t6 - t0)
+        info = dict(timing=self.timing, losses_exposure=losses1, losses_unique=losses2, total_time=t6 - t0,
+                    sec_per_frame=(t6 - t0) / self.n_total, total_number_of_frames=self.n_total, init_latent=c.init_latent,
                     iclight_model=c.iclight_model, ip_adapter=c.ip_adapter,
                     init_strength=c.init_strength, scheduler_steps=self.schedule[0], steps_executed=self.schedule[2],
                     max_memory_allocated=torch.cuda.max_memory_allocated(self.dev) / 1024.0 ** 2)
+        if detail:
+            self.timing["detail"] = t6 - t5
+            info["detail"] = dict(c.detail_transfer)
         if self.highres:
             self.timing["highres"] = t2 - t2a
             info.update(highres_scale=c.highres_scale, highres_denoise=c.highres_denoise, highres_size=[8 * self.h, 8 * self.w],
                         highres_scheduler_steps=self.schedule_highres[0], highres_steps_executed=self.schedule_highres[2])
         return clean, info
+
+    def detail_step(self, clean, source):
+        """generation.detail_transfer, the last step: clean [N,3,H,W], the frames __call__ is about to return (all of the run's, on every rank) ->
+        the same with the high frequencies of `source`, which must match them frame for frame.  It runs behind stage 1 / 2: stage 2's codebook
+        averages along tracks and would smooth re-injected detail, and both stages stay what they are without the key.  Every rank does the whole
+        clip, no collective.  Under fbc the weight is the matting alpha: on one rank the one prepare_fbc estimated, with several ranks it is
+        estimated again on the full source (a rank holds the alpha of its own block only)."""
+        from .detail import detail_transfer
+        c = self.cfg
+        if source is None or tuple(source.shape) != tuple(clean.shape):
+            raise ValueError(f"generation.detail_transfer: source frames {None if source is None else tuple(source.shape)}, expected "
+                             f"{tuple(clean.shape)} -- all frames of the run at the size of the result (Generator(...)(..., source=...))")
+        mask = None
+        if self.fbc:
+            mask = self.fbc_alpha
+            if mask is None or mask.shape[0] != clean.shape[0]:
+                mask = self.rmbg.estimate_alpha(source, self.batch_size)
+            mask = mask.float().contiguous()
+        b = c.detail_transfer
+        return detail_transfer(source.float().contiguous(), clean.float().contiguous(), b["sigma"], b["mode"], b["blend"], b["channels"], mask)
 
     def encode_conds(self):
         """ddim_sample's concat_conds from what prepare_data left.  fc: the latents of the frames.  fbc: the pair (foreground, background) latents

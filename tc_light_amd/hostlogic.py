@@ -393,6 +393,46 @@ def check_ip_adapter(block, normal=False, models=None, allow_random=False):
     return dict(image=image, scale=float(scale), path=path, image_encoder=encoder)
 
 
+DETAIL_MODES = ("add", "ratio")          # generation.detail_transfer.mode, in the order of TCL_DETAIL_ADD / TCL_DETAIL_RATIO
+DETAIL_CHANNELS = ("rgb", "luma")        # generation.detail_transfer.channels
+DETAIL_SIGMA = (0.5, 16.0)               # the radius ceil(3 sigma) stays within the kernel's 48
+DETAIL_DEFAULTS = dict(sigma=3.0, mode="add", blend=1.0, channels="rgb")
+
+
+def check_detail(block, normal=False, iclight_model="fc", fbc_matting=True):
+    """generation.detail_transfer: None (off: nothing else is looked at) or {sigma, mode: add | ratio, blend, channels: rgb | luma} -> the block with
+    the defaults filled in (DETAIL_DEFAULTS); a bare number is {sigma: number}.  run.py and Generator raise what is wrong before a model is loaded,
+    each by the name of its key: an unknown key, a sigma outside DETAIL_SIGMA, a blend outside [0, 1], an unknown mode or channels.  Refused by both
+    key names: generation.normal (its outputs are ratios of four relights, not a relight), and iclight_model fbc with fbc_matting false (an fbc run
+    may carry a new background; without the matte as the weight the old background would ghost into it)."""
+    if block is None:
+        return None
+    if _is_number(block):
+        block = dict(sigma=block)
+    if not isinstance(block, dict) or any(k not in DETAIL_DEFAULTS for k in block):
+        raise ValueError(f"generation.detail_transfer {block!r}: expected null, a number (sigma) or {{sigma: <float>, mode: add | ratio, "
+                         "blend: <float in [0, 1]>, channels: rgb | luma}")
+    out = dict(DETAIL_DEFAULTS, **block)
+    sigma, blend = out["sigma"], out["blend"]
+    if not _is_number(sigma) or not DETAIL_SIGMA[0] <= float(sigma) <= DETAIL_SIGMA[1]:
+        raise ValueError(f"generation.detail_transfer.sigma {sigma!r}: expected a number in [{DETAIL_SIGMA[0]}, {DETAIL_SIGMA[1]}]")
+    if not _is_number(blend) or not 0.0 <= float(blend) <= 1.0:
+        raise ValueError(f"generation.detail_transfer.blend {blend!r}: expected a number in [0, 1]")
+    for key, allowed in (("mode", DETAIL_MODES), ("channels", DETAIL_CHANNELS)):
+        if not isinstance(out[key], str) or out[key].lower() not in allowed:
+            raise ValueError(f"generation.detail_transfer.{key} {out[key]!r}: expected one of {' | '.join(allowed)}")
+        out[key] = out[key].lower()
+    out["sigma"], out["blend"] = float(sigma), float(blend)
+    if normal:
+        raise ValueError("generation.detail_transfer together with generation.normal is not supported: the normal's outputs are ratios of four "
+                         "relights, not a relight")
+    model = "fc" if iclight_model is None else str(iclight_model).lower()
+    if model == "fbc" and not fbc_matting:
+        raise ValueError("generation.detail_transfer under generation.iclight_model fbc needs generation.fbc_matting: true: the matte is the step's "
+                         "weight, without it the source's background would ghost into a new one")
+    return out
+
+
 # what resolve_generation normalises: run.py writes these back into the configuration (config.yaml records them), Generator into its cfg
 RESOLVED_KEYS = ("init_latent", "init_strength", "highres_scale", "highres_denoise", "iclight_model", "bg_source", "light_path", "prompt_path")
 
