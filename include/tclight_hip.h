@@ -685,6 +685,61 @@ size_t tcl_detail_transfer_workspace_bytes(int N, int H, int W, int mode, int lu
 int tcl_detail_transfer_f32(const float* src, const float* relit, const float* mask, float* out, int N, int H, int W, const float* h_taps, int n_taps,
                             int radius, int mode, int luma, float blend, void* ws, long ws_bytes, hipStream_t st);
 
+/* ===================================================================== keyframe relighting (generation.keyframes); csrc/keyframe.hip */
+/* Only every K-th frame (the keys) is denoised; the gain field relit / source of the two neighbouring keys is carried to the frames in between along
+ *   the chained flows.  All tensors f32 NCHW, contiguous.  Pixel centres sit at integer coordinates, p = (x, y).  fut [N,2,H,W]: fut[i] maps frame i to
+ *   i+1 (fut[N-1] = 0); past [N,2,H,W]: past[i] maps i to i-1 (past[0] = 0); channel 0 is dx, channel 1 dy.  Everything in f32 with no fma contraction,
+ *   IEEE division and square root, in the order written.
+ *     inb(q)     0 <= qx <= W-1 && 0 <= qy <= H-1                                                                    (false for a NaN)
+ *     bil(T, q)  qx' = min(max(qx, 0), W-1), qy' likewise (a q that is inb is unchanged; the clamp keeps every address inside the frame);
+ *                x0 = floor(qx'), x1 = min(x0 + 1, W-1), fx = qx' - x0, the same in y;  top = T[y0,x0] + fx * (T[y0,x1] - T[y0,x0]);
+ *                bot = T[y1,x0] + fx * (T[y1,x1] - T[y1,x0]);  bil = top + fy * (bot - top)
+ *   h_keys: HOST int32 [M], the frame numbers of the keys, strictly increasing from 0 to N-1, no gap (difference of neighbours) above
+ *   TCL_KEYFRAME_MAX_GAP.  Gap g lies between keys g and g+1.  One call works on the gaps g0 <= g < g1 (a batch): the frames f0 = h_keys[g0] ..
+ *   f1 = h_keys[g1], at most TCL_KEYFRAME_BATCH_FRAMES of them, so the workspace stays bounded whatever N is.
+ *   ws: [f1 - f0 + 1 slots][2 directions][3][H][W] f32, slot = frame - f0, direction 0 = CL (towards the left key), 1 = CR (right key), planes
+ *   (dx, dy, valid); the slots of key frames are not touched.  tcl_keyframe_workspace_bytes(N, H, W, K) = min(N, TCL_KEYFRAME_BATCH_FRAMES) * 24 * H * W
+ *   is enough for every batch of a clip whose gaps are at most K; 0 for arguments the calls would refuse (K outside 1 .. TCL_KEYFRAME_MAX_GAP).
+ *
+ * tcl_flow_chain_f32: for every non-key frame j of the batch, with its keys a < j < b, CL[j] = the flow from j to a and CR[j] = the flow from j to b.
+ *   Left direction, d = j - a (the right direction is the mirror image: fut and past exchanged, j+1 for j-1, CR for CL, d = b - j):
+ *     A = past[j](p);  q = p + A;  g = bil(fut[j-1], q) per component;
+ *     e = A + g;  fb = e.x*e.x + e.y*e.y < t*t  with  t = alpha * (sqrt(A.x*A.x + A.y*A.y) + sqrt(g.x*g.x + g.y*g.y)) + alpha;
+ *     d = 1:  C = A;                          valid = inb(q) && fb
+ *     d > 1:  C = A + bil(CL[j-1].xy, q);     valid = inb(q) && fb && the four taps (y0|y1, x0|x1) of CL[j-1].valid at q are all 1
+ *     CL[j](p) = valid ? (C.x, C.y, 1) : (0, 0, 0): the workspace never holds a value computed from outside the frame.
+ *   One launch per distance d = 1 .. (longest gap of the batch) - 1 covers both directions of all gaps of the batch (one block per TCL_KEYFRAME_TILE_W
+ *   x TCL_KEYFRAME_TILE_H pixels of one frame and direction): at most TCL_KEYFRAME_MAX_GAP - 1 launches, each reading what the one before wrote.
+ *
+ * tcl_keyframe_propagate_f32: source S [N,3,H,W], relit_keys R [M,3,H,W] (R_k: the relit frame h_keys[k]) -> out [N,3,H,W], holes [N] u32, both
+ *   written for the frames f0 .. f1 of the batch only.  HOST tables over all N frames, copied into the kernel arguments: h_left / h_right int32 [N],
+ *   the index into h_keys of the last key at or before / the first key at or after frame i (a key frame: its own index twice), and h_tw f32 [2,N]:
+ *   ta = (b - i) / (b - a) in [0][i], tb = 1 - ta in [1][i], a and b the FRAME numbers of the two keys, each computed in f64 and rounded once
+ *   (a key frame: 1, 0).  A key frame is copied from relit_keys bit for bit, holes 0.  A non-key frame i, per pixel p and key k in {a, b} with
+ *   C_k = CL[i] | CR[i] of the workspace tcl_flow_chain_f32 filled for the same batch:
+ *     q = p + C_k.xy;  s_c = bil(S_k,c, q);  r_c = bil(R_k,c, q);  m = max(max(|s_0 - S_i,0(p)|, |s_1 - S_i,1(p)|), |s_2 - S_i,2(p)|);
+ *     w_k = t_k * C_k.valid * (m < diff_threshold ? 1 : 0);  G_k,c = (r_c + eps) / (s_c + eps)
+ *     w = w_a + w_b;  w > 0:   G_c = (w_a * G_a,c + w_b * G_b,c) / w
+ *                     else:    a hole, visible in neither key: G_c = ta * G'_a,c + tb * G'_b,c with G'_k,c = (R_k,c(p) + eps) / (S_k,c(p) + eps),
+ *                              the gains unwarped at p itself; holes[i] is incremented (an integer atomic: the count is exact in any order)
+ *     out_c = (S_i,c(p) + eps) * G_c - eps.                            No clamping: the frames stay unclamped until they are saved.
+ *   One launch (and one clear of holes[f0 .. f1]) per call.
+ *
+ * TCL_EINVAL from both, with nothing launched or written: a null pointer, N, H, W, M <= 0, H * W > 2^30, H > 65535 * TCL_KEYFRAME_TILE_H, alpha or
+ *   diff_threshold not a finite number > 0, eps outside (0, 0.25], h_keys not as above, g0 / g1 outside 0 <= g0 <= g1 <= M-1 or a batch of more than
+ *   TCL_KEYFRAME_BATCH_FRAMES frames, a workspace below (f1 - f0 + 1) * 24 * H * W bytes, h_left / h_right that do not agree with h_keys, a weight
+ *   outside [0, 1]. */
+#define TCL_KEYFRAME_TILE_W 64
+#define TCL_KEYFRAME_TILE_H 4
+#define TCL_KEYFRAME_MAX_GAP 16
+#define TCL_KEYFRAME_BATCH_FRAMES 33
+size_t tcl_keyframe_workspace_bytes(int N, int H, int W, int K);
+int tcl_flow_chain_f32(const float* fut, const float* past, const int* h_keys, int M, int g0, int g1, int N, int H, int W, float alpha, void* ws,
+                       long ws_bytes, hipStream_t st);
+int tcl_keyframe_propagate_f32(const float* source, const float* relit_keys, float* out, unsigned* holes, const int* h_keys, int M, int g0, int g1,
+                               const int* h_left, const int* h_right, const float* h_tw, int N, int H, int W, float diff_threshold, float eps,
+                               const void* ws, long ws_bytes, hipStream_t st);
+
 #ifdef __cplusplus
 }
 #endif

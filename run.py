@@ -14,6 +14,8 @@ conditioning of the xy passes is the blend of its two neighbouring keyframes' em
 its CLIP ViT-H/14 embedding (models.image_encoder) becomes 4 image tokens every text cross-attention of the xy passes also attends to (models.ip_adapter).
 [--detail [SIGMA]] [--detail_mode add|ratio] [--detail_blend B] (generation.detail_transfer: {sigma, mode, blend, channels}): detail transfer -- the last
 step gives the relit frames the source's high frequencies (texture, small text, faces) back and keeps the relight's low ones (the new light).
+[--keyframes K] (generation.keyframes: K or {interval, alpha, diff_threshold, eps}): keyframe relighting -- only every K-th frame is denoised; the frames
+in between are their source frame times the two neighbouring keys' gain field relit / source, carried along the chained flows; stage 1 / 2 see all frames.
 data.scene_type picks the parser (generate.py:84-95): video (VideoDataParser) or sceneflow (SceneFlowDataParser: ground-truth depth, poses and
 flows -> voxelised Unique Video Tensor ids); carla and interiornet are not built.
 
@@ -36,7 +38,7 @@ from tc_light_amd.config_utils import Config, load_config, save_config
 from tc_light_amd.dataparser import VideoDataParser, get_frame_ids, save_loss_curve, save_video
 from tc_light_amd.generate import DEFAULTS, Generator
 from tc_light_amd.hostlogic import (RESOLVED_KEYS, check_detail, check_highres_tokens, check_ip_adapter, cond_channels, fbc_background_per_frame,
-                                    highres_size, light_angles, prompt_table, resolve_generation)
+                                    highres_size, keyframe_ids, light_angles, prompt_table, resolve_generation)
 from tc_light_amd.model_utils import allow_random, init_iclight
 from tc_light_amd.parallel import Dist
 from tc_light_amd.text import encode_prompt_pair, encode_prompt_set
@@ -63,10 +65,13 @@ def resolve_options(config):
         raise NotImplementedError(f"Scene type '{scene_type}' is not supported.")
     opts = {**DEFAULTS, **g, **config.post_opt}
     opts["fbc_matting"] = bool(opts["fbc_matting"])
-    r = resolve_generation(opts)      # init_latent, the highres pass, fbc, light_path, normal, prompt_path: each refused by the names of its keys
+    opts["scene_type"] = scene_type       # generation.keyframes is refused beside sceneflow
+    # init_latent, the highres pass, fbc, light_path, normal, prompt_path, keyframes: each refused by the names of its keys
+    r = resolve_generation(opts)
     g.update({k: r[k] for k in RESOLVED_KEYS}, fbc_matting=opts["fbc_matting"], normal=opts["normal"])
     o = SimpleNamespace(scene_type=scene_type, fbc=r["fbc"], light=r["light"], normal=bool(r["normal_sides"]), highres=r["highres"], data_hr=None,
-                        lora=None)
+                        lora=None, keyframes=r.get("keyframes"))      # the normalised block; None when off (interval 1 included)
+    g.keyframes = None if o.keyframes is None else Config(o.keyframes)      # what config.yaml records
     if o.normal:
         print("[INFO] generation.normal: the four ramps left / right / bottom / top are the backgrounds; generation.bg_source and "
               "generation.background_image_path are not consulted.")
@@ -135,12 +140,13 @@ def load_frames(config, o, dev):
 
 
 def load_flows(config, o, clip, models, dev, d):
-    """The stage-1 / 2 producers' input -> (flows, scene), both None without post_opt.apply_opt.  sceneflow: every rank reads the files itself --
+    """The stage-1 / 2 producers' input -> (flows, scene), both None without post_opt.apply_opt -- unless generation.keyframes is on: propagation
+    needs the flows of the whole clip even without the optimiser.  sceneflow: every rank reads the files itself --
     ground-truth (or RAFT) flows, masks and the voxelised ids all come from load_data.  video: rank 0 owns the flow cache (read, or estimated with
     MemFlowNet / RAFT (data.flow_model) and written: video_dataparser.py:63-110); the other ranks receive the tensors.  A failure on rank 0 (e.g.
     missing MemFlow weights) is announced before the payload so that every rank raises instead of waiting in the broadcast until the collective
     times out."""
-    if not config.post_opt.apply_opt:
+    if not config.post_opt.apply_opt and o.keyframes is None:
         return None, None
     ok_random, frame_ids, parser_hr = allow_random(models), clip.frame_ids, clip.parser_hr
     if o.scene_type == "sceneflow":
@@ -169,12 +175,14 @@ def load_flows(config, o, clip, models, dev, d):
     return flows, None
 
 
-def load_background(config, o, clip, models, dev, d):
+def load_background(config, o, clip, models, dev, d, kf_ids=None):
     """-> (rmbg, background, bg_per_frame): the matting engine where it is needed (background compositing, generate.py:68-69, 147-167; fbc: the alpha
     of the grey matte), and this rank's frames of generation.background_image_path -- composited behind the foreground (background_cond), or the
-    background the fbc model is conditioned on: one frame for all, or one per frame (bg_per_frame, the same answer on every rank)."""
+    background the fbc model is conditioned on: one frame for all, or one per frame (bg_per_frame, the same answer on every rank).
+    kf_ids (generation.keyframes): the frames that are denoised -- a per-frame background is indexed by them before the ranks take their blocks."""
     g, n = config.generation, len(clip.frame_ids)
-    lo, hi = d.range(n)
+    lo, hi = d.range(n if kf_ids is None else len(kf_ids))
+    pick = lambda b: b if kf_ids is None else b[kf_ids]
     rmbg = background = bg_per_frame = None
     if g.get("background_cond") or (o.fbc and g.fbc_matting):
         from tc_light_amd.model_utils import load_rmbg_state
@@ -182,13 +190,17 @@ def load_background(config, o, clip, models, dev, d):
         rmbg = RMBGEngine(load_rmbg_state(models.get("rmbg"), allow=allow_random(models)), dev)
     if g.get("background_cond"):
         background = clip.parser.load_video(path=g.background_image_path)
-        if background.shape[0] == n and d.world > 1:     # a per-frame background video: this rank's block of it
-            background = background[lo:hi]
+        if background.shape[0] == n:                     # a per-frame background video: this rank's block of it
+            background = pick(background)
+            if d.world > 1:
+                background = background[lo:hi]
     elif o.upload:
         background = clip.parser.load_video(path=g.background_image_path)
         bg_per_frame = fbc_background_per_frame(background.shape[0], n, g.bg_source)
-        if bg_per_frame and d.world > 1:
-            background = background[lo:hi]
+        if bg_per_frame:
+            background = pick(background)
+            if d.world > 1:
+                background = background[lo:hi]
     return rmbg, background, bg_per_frame
 
 
@@ -237,6 +249,8 @@ def save_relit_run(config, o, name, out, info, clip):
     g, n = config.generation, len(clip.frame_ids)
     if o.light:                               # light_path is in g already; the angles of the first and the last frame of the run
         g.light_angle_first, g.light_angle_last = (float(a) for a in light_angles(g.light_path, [0.0, 1.0 if n > 1 else 0.0]))
+    if "keyframes" in info:                   # the block is in g already; how many frames went through the denoise, the share of hole pixels
+        g.keyframes_denoised, g.keyframes_holes = int(info["keyframes"]["denoised"]), float(info["keyframes"]["holes"])
     if o.highres:                             # total_time / sec_per_frame cover both passes
         g.highres_size = list(info["highres_size"])
         g.highres_scheduler_steps, g.highres_steps_executed = info["highres_scheduler_steps"], info["highres_steps_executed"]
@@ -262,11 +276,18 @@ def main(argv=None):
     config.max_memory_allocated, config.total_time = 0, 0
     clip = load_frames(config, o, dev)
     flows, scene = load_flows(config, o, clip, models, dev, d)
-    rmbg, background, bg_per_frame = load_background(config, o, clip, models, dev, d)
     g, n = config.generation, len(clip.frame_ids)
-    lo, hi = d.range(n)
+    # generation.keyframes: only the key frames are denoised -- the frames, backgrounds and start latents handed to the generator are theirs
+    kf_ids = None if o.keyframes is None else keyframe_ids(n, o.keyframes["interval"])
+    rmbg, background, bg_per_frame = load_background(config, o, clip, models, dev, d, kf_ids)
+    n_gen = n if kf_ids is None else len(kf_ids)
+    frames_in = clip.frames if kf_ids is None else clip.frames[kf_ids]
+    frames_hr = None if not o.highres else (clip.frames_out if kf_ids is None else clip.frames_out[kf_ids])
+    lo, hi = d.range(n_gen)
     cfg = dict(g); cfg.update(config.post_opt); cfg["seed"] = config.seed
-    cfg["frame_ids"], cfg["model_key"] = clip.frame_ids, config.model_key      # generation.latents_path: which saved start latents are this run's
+    # generation.latents_path: which saved start latents are this run's
+    cfg["frame_ids"] = clip.frame_ids if kf_ids is None else [clip.frame_ids[k] for k in kf_ids]
+    cfg["model_key"] = config.model_key
     image_prompt = None
     if o.ip_block is not None:    # on every rank, once per run: the image tower is built, run on the one image and freed before the UNet loop
         from tc_light_amd import ip_adapter
@@ -276,7 +297,7 @@ def main(argv=None):
     for name, prompt in g.prompt.items():
         if g.prompt_path is not None:      # every distinct keyframe prompt is encoded once; the rows of this rank's frames are blended from them
             uncond, keys = encode_prompt_set(prompt_table(g.prompt_path, n)[0], g.negative_prompt, dev, models.get("text_encoder"), **text)
-            conds = gen.frame_text(uncond, keys, hi - lo, n_total=n)
+            conds = gen.frame_text(uncond, keys, hi - lo, n_total=n)      # (refused beside generation.keyframes: n is every frame)
         else:
             conds = encode_prompt_pair(prompt, g.negative_prompt, dev, models.get("text_encoder"), **text)
         conds_t = encode_prompt_pair(g.prompt_t, g.negative_prompt_t, dev, models.get("text_encoder"), **text)
@@ -292,9 +313,10 @@ def main(argv=None):
             from tc_light_amd.flow_ids import soft_masks_and_ids
             fut, past = flows
             masks, inv, k = soft_masks_and_ids(clip.frames_out, fut, past, alpha=clip.parser.alpha)
-        out, info = gen(clip.frames[lo:hi], conds, conds_t, past, masks, inv, n_total=n, k=k, background=background,
-                        frames_hr=clip.frames_out[lo:hi] if o.highres else None, background_per_frame=bg_per_frame,
-                        source=clip.frames_out if o.detail is not None else None)
+        out, info = gen(frames_in[lo:hi], conds, conds_t, past, masks, inv, n_total=n_gen, k=k, background=background,
+                        frames_hr=frames_hr[lo:hi] if o.highres else None, background_per_frame=bg_per_frame,
+                        source=clip.frames_out if o.detail is not None or kf_ids is not None else None,
+                        flows=flows if kf_ids is not None else None, keyframes=kf_ids)
         if d.rank == 0:
             save_relit_run(config, o, name, out, info, clip)
     if d.world > 1:

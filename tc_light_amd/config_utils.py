@@ -10,7 +10,8 @@ import yaml
 
 # keys a YAML may leave out and that are not generation.* / post_opt.* settings of the Generator (those: generate.DEFAULTS)
 DEFAULTS = dict(generation=dict(ip_adapter=None,                        # IP-Adapter off; else {image, scale, path} (hostlogic.check_ip_adapter)
-                                detail_transfer=None),                  # detail transfer off; else {sigma, mode, blend, channels} (hostlogic.check_detail)
+                                detail_transfer=None,                   # detail transfer off; else {sigma, mode, blend, channels} (hostlogic.check_detail)
+                                keyframes=None),                        # every frame denoised; else K or {interval, alpha, diff_threshold, eps} (check_keyframes)
                 models=dict(ip_adapter="", image_encoder=""))           # ip-adapter_sd15.safetensors / .bin; a CLIP ViT-H/14 vision snapshot directory
 
 
@@ -120,8 +121,14 @@ def load_config(argv=None, print_config=True):
     ap.add_argument("--detail_mode", choices=("add", "ratio"), default=None, help="add: the source's high-pass is added; ratio: the source times the "
                     "ratio of the two blurs (generation.detail_transfer.mode), for a fast usage")
     ap.add_argument("--detail_blend", type=float, default=None, help="strength of the step in [0, 1] (generation.detail_transfer.blend), for a fast usage")
+    # keyframe relighting: only every K-th frame is denoised, the others are propagated along the flows (generation.keyframes, generate.py DEFAULTS)
+    ap.add_argument("--keyframes", type=int, default=None, metavar="K", help="denoise only every K-th frame (K in [1, 16]) and carry the relight to "
+                    "the frames in between along the optical flow: generation.keyframes.interval, for a fast usage")
     a = ap.parse_args(argv)
     cfg = load_yaml_chain(a.config, a.base_config)
+    if a.keyframes is not None:
+        block = cfg.generation.get("keyframes")
+        cfg.generation.keyframes = Config(dict(block, interval=a.keyframes)) if isinstance(block, dict) else a.keyframes
     if a.ip_image is not None or a.ip_scale is not None:
         block = Config(cfg.generation.get("ip_adapter") or {})
         if a.ip_image is not None:

@@ -87,6 +87,12 @@ DEFAULTS = dict(  # configs/tclight_default.yaml (generation / post_opt sections
     #   stage 1 / 2: the returned frames keep their low frequencies (the new light) and take the high ones (texture, small text, faces) from the source
     #   frames handed in as source= -- one tcl_detail_transfer_f32 call over all frames (detail.py), weighted by the matting alpha under fbc.
     #   None (default): nothing of it is consulted and every path is what it was.
+    keyframes=None,
+    # ^ keyframe relighting: an integer K or {interval: K, alpha, diff_threshold, eps} (HL.check_keyframes).  Only every K-th frame (HL.keyframe_ids) is
+    #   handed in and denoised; propagate_step, behind the decode and the highres pass and in front of stage 1 / 2, fills the frames in between: their
+    #   source frame times the gain field relit / source of the two neighbouring keys, carried along the chained flows handed in as flows= and blended
+    #   by distance (keyframe.py: tcl_flow_chain_f32, tcl_keyframe_propagate_f32).  Stage 1 / 2 and detail_transfer then see all frames.
+    #   None (default) or interval 1: nothing of it is consulted and every path is what it was.
     max_tokens_per_pass=None)
     # ^ level-0 tokens (samples x pixels) one block-major UNet pass may carry; longer chunk lists are split into consecutive groups.  None:
     #   TCL_MAX_TOKENS_PER_PASS (read when the Generator is built), else min(16 M, 80 % of the device's free memory / 10.5 KB) -- a pass peaks at
@@ -116,6 +122,7 @@ class Generator:
         cfg.update(config or {})
         r = HL.resolve_generation(cfg)     # every option checked once, in run.py's order; what is refused is refused before anything is built
         cfg.update({k: r[k] for k in HL.RESOLVED_KEYS})
+        cfg["keyframes"] = r.get("keyframes")      # the normalised block, None when off (interval 1 included)
         self.cfg = SimpleNamespace(**cfg)
         self.fbc, self.light, self.img2img, self.highres = r["fbc"], r["light"], r["img2img"], r["highres"]
         self.normal_sides = r["normal_sides"]                                      # () unless generation.normal
@@ -669,7 +676,7 @@ class Generator:
 
     # ------------------------------------------------------------------ end to end
     def __call__(self, frames, conds, conds_t, past_flows, mask_bwds, unq_inv, n_total=None, k=None, background=None, frames_hr=None,
-                 background_per_frame=None, source=None):
+                 background_per_frame=None, source=None, flows=None, keyframes=None):
         """frames: local block [n_local,3,H,W]; conds / conds_t: [2,L,768] f16 (uncond, cond) text embeddings for the xy / yt
         passes (generate.py:553-555) -- under generation.prompt_path conds is the FrameText of frame_text; past_flows / mask_bwds / unq_inv: stage-2 inputs for ALL frames (device).
         Returns (relit frames [N,3,H,W] f32, info dict).
@@ -679,17 +686,39 @@ class Generator:
         rank's block of a per-frame clip); background_per_frame says which when the block alone cannot (None: more than one frame handed in) --
         every rank must give the same answer, since a per-frame background is all-gathered for the yt pass.
         With generation.detail_transfer: source [N,3,H,W] f32 in [0,1] holds the source frames of ALL ranks at the size of the result (the final size
-        under the highres pass); see detail_step."""
+        under the highres pass); see detail_step.
+        With generation.keyframes: frames (and a per-frame background) are this rank's block of the KEY frames only, n_total their number,
+        keyframes=their frame numbers in the clip (HL.keyframe_ids), flows=(fut, past) [N,2,H,W] the flows between all consecutive frames of the clip
+        and source all its N frames, both at the size of the result; the stage-2 inputs belong to all N frames, as do the returned frames; see
+        propagate_step."""
         c, d = self.cfg, self.dist
         if self.highres and background is not None:
             raise ValueError("generation.background_cond together with generation.highres_scale > 1 is not supported")
         self._total(frames.shape[0], n_total, keep=False)
         if (c.prompt_path is not None) != isinstance(conds, FrameText) or (isinstance(conds, FrameText) and len(conds.index) != frames.shape[0]):
             raise ValueError("generation.prompt_path: conds must be the FrameText of Generator.frame_text for this rank's frames (and only then)")
+        n_out = self.n_total                  # the frames returned: with generation.keyframes all frames of the clip, of which n_total are denoised
+        keys = None
+        if c.keyframes is not None:
+            if keyframes is None:
+                raise ValueError("generation.keyframes: the frame numbers of the key frames are missing (Generator(...)(..., keyframes=...))")
+            keys = [int(k) for k in keyframes]
+            n_out = keys[-1] + 1
+            if len(keys) != self.n_total or HL.keyframe_ids(n_out, c.keyframes["interval"]) != keys:
+                raise ValueError(f"generation.keyframes: keyframes {keys} are not the {self.n_total} key frames of a clip at interval "
+                                 f"{c.keyframes['interval']} (hostlogic.keyframe_ids)")
+            if source is None or source.dim() != 4 or source.shape[0] != n_out:
+                raise ValueError(f"generation.keyframes: source frames {None if source is None else tuple(source.shape)}, expected all {n_out} "
+                                 "frames of the clip at the size of the result (Generator(...)(..., source=...))")
+            if flows is None or len(flows) != 2 or any(f is None or f.dim() != 4 or f.shape[0] != n_out for f in flows):
+                raise ValueError(f"generation.keyframes: flows are missing or not (fut, past) over all {n_out} frames of the clip at the size of "
+                                 "the result (Generator(...)(..., flows=...))")
+        elif keyframes is not None and len(keyframes) != self.n_total:
+            raise ValueError("generation.keyframes is off: keyframes= must be left out (or name every frame)")
         detail = c.detail_transfer is not None and c.detail_transfer["blend"] > 0.0      # blend 0: nothing runs, the frames are returned as they are
-        if detail and (source is None or source.dim() != 4 or source.shape[0] != self.n_total):
+        if detail and (source is None or source.dim() != 4 or source.shape[0] != n_out):
             raise ValueError(f"generation.detail_transfer: source frames {None if source is None else tuple(source.shape)}, expected all "
-                             f"{self.n_total} frames of the run at the size of the result (Generator(...)(..., source=...))")
+                             f"{n_out} frames of the run at the size of the result (Generator(...)(..., source=...))")
         ev = self._now
         t0 = ev()
         self.prepare_data(frames, background)
@@ -710,7 +739,11 @@ class Generator:
             raise ValueError(f"post_opt_mode {mode!r}: expected replicated | replicated_all | global | shard")
         shard = d.multi and mode == "shard" and c.apply_opt
         clean, past_flows, mask_bwds, unq_inv, k = self.decode_gather(x, shard, past_flows, mask_bwds, unq_inv, k)
-        t3 = t4 = t5 = ev()
+        t3 = ev()
+        holes = None
+        if keys is not None:               # the frames between the keys, at the final size; stage 1 / 2 and detail_step see all frames of the clip
+            clean, holes = self.propagate_step(clean, source, flows, keys)
+        t3p = t4 = t5 = t3 if keys is None else ev()
         losses1 = losses2 = None
         if c.apply_opt:
             clean, losses1, losses2, t4 = self.post_optimize(clean, mode, shard, past_flows, mask_bwds, unq_inv, k)
@@ -719,12 +752,16 @@ class Generator:
         if detail:
             clean = self.detail_step(clean, source)
             t6 = ev()
-        self.timing = dict(encode=t1 - t0, denoise=t2a - t1, decode=t3 - t2, stage1=t4 - t3, stage2=t5 - t4, total=t6 - t0)
+        self.timing = dict(encode=t1 - t0, denoise=t2a - t1, decode=t3 - t2, stage1=t4 - t3p, stage2=t5 - t4, total=t6 - t0)
         info = dict(timing=self.timing, losses_exposure=losses1, losses_unique=losses2, total_time=t6 - t0,
-                    sec_per_frame=(t6 - t0) / self.n_total, total_number_of_frames=self.n_total, init_latent=c.init_latent,
+                    sec_per_frame=(t6 - t0) / n_out, total_number_of_frames=n_out, init_latent=c.init_latent,
                     iclight_model=c.iclight_model, ip_adapter=c.ip_adapter,
                     init_strength=c.init_strength, scheduler_steps=self.schedule[0], steps_executed=self.schedule[2],
                     max_memory_allocated=torch.cuda.max_memory_allocated(self.dev) / 1024.0 ** 2)
+        if keys is not None:
+            self.timing["propagate"] = t3p - t3
+            between = (n_out - len(keys)) * clean.shape[-2] * clean.shape[-1]
+            info["keyframes"] = dict(interval=c.keyframes["interval"], denoised=len(keys), holes=int(holes.sum().item()) / between if between else 0.0)
         if detail:
             self.timing["detail"] = t6 - t5
             info["detail"] = dict(c.detail_transfer)
@@ -733,6 +770,17 @@ class Generator:
             info.update(highres_scale=c.highres_scale, highres_denoise=c.highres_denoise, highres_size=[8 * self.h, 8 * self.w],
                         highres_scheduler_steps=self.schedule_highres[0], highres_steps_executed=self.schedule_highres[2])
         return clean, info
+
+    def propagate_step(self, clean, source, flows, keys):
+        """generation.keyframes: clean [M,3,H,W], the decoded key frames of all ranks -> ([N,3,H,W] all frames of the clip, holes [N]): the keys bit
+        for bit, every frame in between its source frame times the gain field relit / source of its two neighbouring keys, carried along the chained
+        flows and blended by distance (keyframe.propagate).  It runs at the final size, behind the decode and the highres pass, where the flows and
+        the source frames live, and in front of stage 1 / 2, which smooth the whole clip along its tracks.  Every rank does the whole clip, no
+        collective."""
+        from .keyframe import propagate
+        b = self.cfg.keyframes
+        fut, past = (f.float().contiguous() for f in flows)
+        return propagate(source.float().contiguous(), clean.float().contiguous(), keys, fut, past, b["alpha"], b["diff_threshold"], b["eps"])
 
     def detail_step(self, clean, source):
         """generation.detail_transfer, the last step: clean [N,3,H,W], the frames __call__ is about to return (all of the run's, on every rank) ->

@@ -433,6 +433,67 @@ def check_detail(block, normal=False, iclight_model="fc", fbc_matting=True):
     return out
 
 
+KEYFRAME_MAX_INTERVAL = 16               # TCL_KEYFRAME_MAX_GAP: the longest chain of flows tcl_flow_chain_f32 composes
+# alpha, diff_threshold: the reference's own (compute_fwdbwd_mask(alpha=0.1), get_mask_bwds(diff_threshold=0.1), utils/flow_utils.py); eps = 1/64 is a
+# definition: the floor under numerator and denominator of the gain, a power of two so that adding and removing it is exact on lattice inputs
+KEYFRAME_DEFAULTS = dict(interval=4, alpha=0.1, diff_threshold=0.1, eps=0.015625)
+
+
+def check_keyframes(block, normal=False, light_path=None, prompt_path=None, scene_type="video", post_opt_mode="replicated", shard_post_opt=False):
+    """generation.keyframes: None (off: nothing else is looked at), a bare integer K or {interval: K, alpha, diff_threshold, eps} -> the block with
+    the defaults filled in (KEYFRAME_DEFAULTS), or None for interval 1 -- the key switched off: every frame is a key, nothing is launched and nothing
+    is recorded, like blend 0 of detail transfer.  Each fault is a ValueError naming its key: an unknown key, an interval that is no integer in
+    [1, KEYFRAME_MAX_INTERVAL], alpha or diff_threshold not > 0, eps outside (0, 0.25].  With interval > 1, refused by both key names as out of scope
+    (not impossible): generation.normal (its outputs are ratios of four relights), generation.light_path and generation.prompt_path (their
+    per-frame positions belong to the full clip), data.scene_type sceneflow (its producer hands on past flows only), post_opt_mode shard /
+    shard_post_opt (propagation needs the keys on both sides of a rank's block)."""
+    if block is None:
+        return None
+    if isinstance(block, int) and not isinstance(block, bool):
+        block = dict(interval=block)
+    if not isinstance(block, dict) or "interval" not in block or any(k not in KEYFRAME_DEFAULTS for k in block):
+        raise ValueError(f"generation.keyframes {block!r}: expected null, an integer (interval) or {{interval: <int in [1, {KEYFRAME_MAX_INTERVAL}]>, "
+                         "alpha: <float > 0>, diff_threshold: <float > 0>, eps: <float in (0, 0.25]>}")
+    out = dict(KEYFRAME_DEFAULTS, **block)
+    k = out["interval"]
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= KEYFRAME_MAX_INTERVAL:
+        raise ValueError(f"generation.keyframes.interval {k!r}: expected an integer in [1, {KEYFRAME_MAX_INTERVAL}]")
+    for key in ("alpha", "diff_threshold"):
+        if not _is_number(out[key]) or not 0.0 < float(out[key]) < float("inf"):
+            raise ValueError(f"generation.keyframes.{key} {out[key]!r}: expected a number > 0")
+        out[key] = float(out[key])
+    if not _is_number(out["eps"]) or not 0.0 < float(out["eps"]) <= 0.25:
+        raise ValueError(f"generation.keyframes.eps {out['eps']!r}: expected a number in (0, 0.25]")
+    out["eps"] = float(out["eps"])
+    if k == 1:
+        return None
+    if normal:
+        raise ValueError("generation.keyframes together with generation.normal is not supported: the normal's outputs are ratios of four relights, "
+                         "not a relight")
+    for key, v in (("light_path", light_path), ("prompt_path", prompt_path)):
+        if v is not None:
+            raise ValueError(f"generation.keyframes together with generation.{key} is not supported: the path's per-frame positions belong to the "
+                             "full clip, not to the keyframes")
+    if str(scene_type).lower() == "sceneflow":
+        raise ValueError("generation.keyframes together with data.scene_type sceneflow is not supported: its producer hands on past flows only, "
+                         "propagation needs both directions")
+    if shard_post_opt or str(post_opt_mode) == "shard":
+        raise ValueError("generation.keyframes together with post_opt_mode shard (shard_post_opt) is not supported: propagation needs the keys on "
+                         "both sides of a rank's block")
+    return out
+
+
+def keyframe_ids(n, interval):
+    """The key frames of an n-frame run: 0, K, 2K, ... plus n - 1 when it is not one of them, so every other frame has a key on each side."""
+    n, interval = int(n), int(interval)
+    if n < 1 or interval < 1:
+        raise ValueError(f"keyframe_ids: n {n} and interval {interval} must be at least 1")
+    ids = list(range(0, n, interval))
+    if ids[-1] != n - 1:
+        ids.append(n - 1)
+    return ids
+
+
 # what resolve_generation normalises: run.py writes these back into the configuration (config.yaml records them), Generator into its cfg
 RESOLVED_KEYS = ("init_latent", "init_strength", "highres_scale", "highres_denoise", "iclight_model", "bg_source", "light_path", "prompt_path")
 
@@ -442,7 +503,9 @@ def resolve_generation(cfg):
     with generation.*, post_opt.* and background_cond.  Every check_* above runs once, in this order, so two faults at once are reported the same
     way everywhere; check_ip_adapter (models, the file system) is the caller's.  -> the RESOLVED_KEYS normalised, and what follows from them:
     fbc / light / img2img / highres, normal_sides (() unless generation.normal), schedule = (scheduler steps, begin index, steps executed) -- the
-    whole n_timesteps unless the start is an img2img one -- and schedule_highres (the second pass's; None when it is off)."""
+    whole n_timesteps unless the start is an img2img one -- and schedule_highres (the second pass's; None when it is off).  generation.keyframes
+    (check_keyframes; cfg may carry data.scene_type as scene_type) is checked here too; its normalised block is in the result as "keyframes" only
+    when the key is on (interval > 1), so a run without it resolves to exactly what it did."""
     n, normal, bg_cond = cfg["n_timesteps"], cfg["normal"], bool(cfg.get("background_cond"))
     r = {}
     r["init_latent"], r["init_strength"] = check_init(cfg["init_latent"], cfg["init_strength"], n)
@@ -451,6 +514,10 @@ def resolve_generation(cfg):
     r["light_path"] = check_light_path(cfg["light_path"], r["init_latent"], normal, r["iclight_model"], r["bg_source"], r["init_strength"], n)
     r["normal_sides"] = check_normal(normal, r["iclight_model"], cfg["fbc_matting"], cfg["apply_opt"])
     r["prompt_path"] = check_prompt_path(cfg["prompt_path"], normal, r["highres_scale"])
+    keyframes = check_keyframes(cfg.get("keyframes"), bool(normal), r["light_path"], r["prompt_path"], cfg.get("scene_type", "video"),
+                                cfg.get("post_opt_mode", "replicated"), bool(cfg.get("shard_post_opt")))
+    if keyframes is not None:
+        r["keyframes"] = keyframes
     r["fbc"], r["light"], r["highres"] = r["iclight_model"] == "fbc", r["light_path"] is not None, r["highres_scale"] != 1.0
     r["img2img"] = r["init_latent"] != "none" or (r["light"] and not r["fbc"])      # fc: the path's ramps are the start
     r["schedule"] = img2img_schedule(n, r["init_strength"]) if r["img2img"] else (n, 0, n)
