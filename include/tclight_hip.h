@@ -740,6 +740,39 @@ int tcl_keyframe_propagate_f32(const float* source, const float* relit_keys, flo
                                const int* h_left, const int* h_right, const float* h_tw, int N, int H, int W, float diff_threshold, float eps,
                                const void* ws, long ws_bytes, hipStream_t st);
 
+/* ===================================================================== flow-warped noise (generation.noise_mode warp); csrc/noisewarp.hip */
+/* The noise of a clip as a field F_t [4,H,W] f32 at PIXEL resolution (H, W multiples of TCL_NOISE_WARP_CELL = 8), carried from frame to frame along the
+ *   backward flow so that it stays white and unit-variance in every frame.  past_flows [N,2,H,W] f32 (channel 0 dx, 1 dy; frame t to t-1), mask_bwds
+ *   [N,1,H,W] f32, G (the fresh field of frame t) and F_prev / F [4,H,W] f32, all contiguous.  Everything in f32 unless said, no fma contraction, IEEE
+ *   division and square root, in the order written.  Per pixel p = (x, y) of frame t >= 1, with (u, v) = past_flows[t, :, y, x]:
+ *     qx = rintf((float)x + u), qy = rintf((float)y + v)                       (round to nearest, ties to even: torch.round)
+ *     valid(p) = qx >= 0 && qx <= W-1 && qy >= 0 && qy <= H-1 && mask_bwds[t, 0, y, x] > 0.5     (false for a NaN anywhere, an inf flow)
+ *     k(q) = the number of valid p with source q;  S_c(q) = the sum over them of llrintf(G[c, p] * 16777216.f) in int64 (two's complement)
+ *     invalid p:          F[c, p] = G[c, p]
+ *     valid p, k(q) == 1: F[c, p] = F_prev[c, q]                                 (the bits)
+ *     valid p, k(q) > 1:  mean = (float)((double)S_c(q) / (16777216.0 * (double)k));  a = F_prev[c, q] / sqrtf((float)k);  b = G[c, p] - mean;
+ *                         F[c, p] = a + b
+ *   Frame 0: F = G.  The latent noise of the frame, z[t] [4,h,w] with h = H/8, w = W/8:
+ *     row_i = ((((((F[c,8y+i,8x] + F[c,8y+i,8x+1]) + F[c,8y+i,8x+2]) + ...) + F[c,8y+i,8x+7]     (the 8 pixels of a row, left to right)
+ *     z[t, c, y, x] = (((row_0 + row_1) + row_2) + ... + row_7) * 0.125f                          (the 8 rows, top to bottom)
+ *   ws: int64 S [4,H,W] first, then int32 k [H,W]; tcl_noise_warp_workspace_bytes(H, W) = 36 * H * W, 0 for a size the calls would refuse.  8 B aligned.
+ *
+ * tcl_noise_warp_count: frame t >= 1.  Clears the workspace (one memset), then one launch: k and S of every source, by integer atomics -- the result
+ *   is the same bits whatever order the adds arrive in.
+ * tcl_noise_warp_apply_f32: frame t.  One launch: recomputes q, writes F and, fused, z[t] into the caller's z [N,4,h,w].  t == 0: F = G and the
+ *   reduction; past_flows, mask_bwds, F_prev and ws are not read and may be null.  F_prev, G and F must be three different buffers.
+ *   A pixel with k == 1 reads k and F_prev[q] only; S is read where k > 1.  Safe for any flow: an invalid pixel reads nothing outside its own address.
+ *
+ * TCL_EINVAL from both, with nothing launched or written: a null pointer among those read, H or W not a positive multiple of 8, H * W > 2^30,
+ *   H > 4 * 65535, N <= 0, t outside [1, N) (count) / [0, N) (apply), a workspace below 36 * H * W bytes or not 8 B aligned, F_prev, G, F not distinct. */
+#define TCL_NOISE_WARP_TILE_W 64
+#define TCL_NOISE_WARP_CELL 8
+size_t tcl_noise_warp_workspace_bytes(int H, int W);
+int tcl_noise_warp_count(const float* past_flows, const float* mask_bwds, const float* G, int t, int N, int H, int W, void* ws, long ws_bytes,
+                         hipStream_t st);
+int tcl_noise_warp_apply_f32(const float* past_flows, const float* mask_bwds, const float* G, const float* F_prev, float* F, float* z, int t, int N,
+                             int H, int W, const void* ws, long ws_bytes, hipStream_t st);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,6 +16,8 @@ its CLIP ViT-H/14 embedding (models.image_encoder) becomes 4 image tokens every 
 step gives the relit frames the source's high frequencies (texture, small text, faces) back and keeps the relight's low ones (the new light).
 [--keyframes K] (generation.keyframes: K or {interval, alpha, diff_threshold, eps}): keyframe relighting -- only every K-th frame is denoised; the frames
 in between are their source frame times the two neighbouring keys' gain field relit / source, carried along the chained flows; stage 1 / 2 see all frames.
+[--noise_mode same|vanilla|warp] [--noise_warp_steps 0|1] (generation.noise_mode / noise_warp: {steps}): warp carries the noise from frame to frame
+along the backward optical flow -- the start noise and, with steps on (the default), the per-step noise of the SDE solver.
 data.scene_type picks the parser (generate.py:84-95): video (VideoDataParser) or sceneflow (SceneFlowDataParser: ground-truth depth, poses and
 flows -> voxelised Unique Video Tensor ids); carla and interiornet are not built.
 
@@ -66,12 +68,15 @@ def resolve_options(config):
     opts = {**DEFAULTS, **g, **config.post_opt}
     opts["fbc_matting"] = bool(opts["fbc_matting"])
     opts["scene_type"] = scene_type       # generation.keyframes is refused beside sceneflow
-    # init_latent, the highres pass, fbc, light_path, normal, prompt_path, keyframes: each refused by the names of its keys
+    # init_latent, the highres pass, fbc, light_path, normal, prompt_path, keyframes, noise_mode warp: each refused by the names of its keys
     r = resolve_generation(opts)
     g.update({k: r[k] for k in RESOLVED_KEYS}, fbc_matting=opts["fbc_matting"], normal=opts["normal"])
     o = SimpleNamespace(scene_type=scene_type, fbc=r["fbc"], light=r["light"], normal=bool(r["normal_sides"]), highres=r["highres"], data_hr=None,
                         lora=None, keyframes=r.get("keyframes"))      # the normalised block; None when off (interval 1 included)
     g.keyframes = None if o.keyframes is None else Config(o.keyframes)      # what config.yaml records
+    o.noise_warp = r.get("noise_warp")        # the normalised block under noise_mode warp, else None
+    if o.noise_warp is not None:
+        g.noise_warp = Config(o.noise_warp)
     if o.normal:
         print("[INFO] generation.normal: the four ramps left / right / bottom / top are the backgrounds; generation.bg_source and "
               "generation.background_image_path are not consulted.")
@@ -141,12 +146,12 @@ def load_frames(config, o, dev):
 
 def load_flows(config, o, clip, models, dev, d):
     """The stage-1 / 2 producers' input -> (flows, scene), both None without post_opt.apply_opt -- unless generation.keyframes is on: propagation
-    needs the flows of the whole clip even without the optimiser.  sceneflow: every rank reads the files itself --
+    needs the flows of the whole clip even without the optimiser; so does generation.noise_mode warp, which carries the noise along them.  sceneflow: every rank reads the files itself --
     ground-truth (or RAFT) flows, masks and the voxelised ids all come from load_data.  video: rank 0 owns the flow cache (read, or estimated with
     MemFlowNet / RAFT (data.flow_model) and written: video_dataparser.py:63-110); the other ranks receive the tensors.  A failure on rank 0 (e.g.
     missing MemFlow weights) is announced before the payload so that every rank raises instead of waiting in the broadcast until the collective
     times out."""
-    if not config.post_opt.apply_opt and o.keyframes is None:
+    if not config.post_opt.apply_opt and o.keyframes is None and o.noise_warp is None:
         return None, None
     ok_random, frame_ids, parser_hr = allow_random(models), clip.frame_ids, clip.parser_hr
     if o.scene_type == "sceneflow":
@@ -313,6 +318,10 @@ def main(argv=None):
             from tc_light_amd.flow_ids import soft_masks_and_ids
             fut, past = flows
             masks, inv, k = soft_masks_and_ids(clip.frames_out, fut, past, alpha=clip.parser.alpha)
+        elif o.noise_warp is not None:        # no optimiser, so no track ids: the masks alone, which the noise is carried under
+            from tc_light_amd.flow_ids import get_soft_mask_bwds
+            fut, past = flows
+            masks = get_soft_mask_bwds(clip.frames_out, fut, past, alpha=clip.parser.alpha)
         out, info = gen(frames_in[lo:hi], conds, conds_t, past, masks, inv, n_total=n_gen, k=k, background=background,
                         frames_hr=frames_hr[lo:hi] if o.highres else None, background_per_frame=bg_per_frame,
                         source=clip.frames_out if o.detail is not None or kf_ids is not None else None,

@@ -11,7 +11,8 @@ import yaml
 # keys a YAML may leave out and that are not generation.* / post_opt.* settings of the Generator (those: generate.DEFAULTS)
 DEFAULTS = dict(generation=dict(ip_adapter=None,                        # IP-Adapter off; else {image, scale, path} (hostlogic.check_ip_adapter)
                                 detail_transfer=None,                   # detail transfer off; else {sigma, mode, blend, channels} (hostlogic.check_detail)
-                                keyframes=None),                        # every frame denoised; else K or {interval, alpha, diff_threshold, eps} (check_keyframes)
+                                keyframes=None,                         # every frame denoised; else K or {interval, alpha, diff_threshold, eps} (check_keyframes)
+                                noise_warp=None),                       # read under noise_mode warp only: {steps} (check_noise_warp)
                 models=dict(ip_adapter="", image_encoder=""))           # ip-adapter_sd15.safetensors / .bin; a CLIP ViT-H/14 vision snapshot directory
 
 
@@ -124,8 +125,18 @@ def load_config(argv=None, print_config=True):
     # keyframe relighting: only every K-th frame is denoised, the others are propagated along the flows (generation.keyframes, generate.py DEFAULTS)
     ap.add_argument("--keyframes", type=int, default=None, metavar="K", help="denoise only every K-th frame (K in [1, 16]) and carry the relight to "
                     "the frames in between along the optical flow: generation.keyframes.interval, for a fast usage")
+    # the noise of the clip (generation.noise_mode / noise_warp, generate.py DEFAULTS)
+    ap.add_argument("--noise_mode", type=str, default=None, help="same: one noise frame for the whole clip; vanilla: independent noise per frame; "
+                    "warp: the noise is carried from frame to frame along the optical flow (generation.noise_mode), for a fast usage")
+    ap.add_argument("--noise_warp_steps", type=int, choices=(0, 1), default=None, help="under --noise_mode warp: 1 (default) warps the per-step "
+                    "noise of the SDE solver too, 0 draws it per frame as before (generation.noise_warp.steps), for a fast usage")
     a = ap.parse_args(argv)
     cfg = load_yaml_chain(a.config, a.base_config)
+    if a.noise_mode is not None:
+        cfg.generation.noise_mode = a.noise_mode
+    if a.noise_warp_steps is not None:
+        block = cfg.generation.get("noise_warp")
+        cfg.generation.noise_warp = Config(dict(block if isinstance(block, dict) else {}, steps=bool(a.noise_warp_steps)))
     if a.keyframes is not None:
         block = cfg.generation.get("keyframes")
         cfg.generation.keyframes = Config(dict(block, interval=a.keyframes)) if isinstance(block, dict) else a.keyframes

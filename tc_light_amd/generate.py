@@ -93,6 +93,12 @@ DEFAULTS = dict(  # configs/tclight_default.yaml (generation / post_opt sections
     #   source frame times the gain field relit / source of the two neighbouring keys, carried along the chained flows handed in as flows= and blended
     #   by distance (keyframe.py: tcl_flow_chain_f32, tcl_keyframe_propagate_f32).  Stage 1 / 2 and detail_transfer then see all frames.
     #   None (default) or interval 1: nothing of it is consulted and every path is what it was.
+    noise_warp=None,
+    # ^ read under noise_mode warp only: {steps: <bool>} (HL.check_noise_warp; default {steps: true}).  noise_mode warp: the start noise is carried
+    #   from frame to frame along the backward flows handed to __call__ as past_flows / mask_bwds -- a pixel-resolution field, the same where nothing
+    #   moves, following the surface where it moves, fresh where something is uncovered, white and unit-variance in every frame (noisewarp.py:
+    #   tcl_noise_warp_count, tcl_noise_warp_apply_f32); steps: the per-step noise of the SDE solver is a new chain over the same flows too.
+    #   noise_mode same | vanilla: nothing of it is consulted and every path, launch and draw is what it was.
     max_tokens_per_pass=None)
     # ^ level-0 tokens (samples x pixels) one block-major UNet pass may carry; longer chunk lists are split into consecutive groups.  None:
     #   TCL_MAX_TOKENS_PER_PASS (read when the Generator is built), else min(16 M, 80 % of the device's free memory / 10.5 KB) -- a pass peaks at
@@ -123,6 +129,7 @@ class Generator:
         r = HL.resolve_generation(cfg)     # every option checked once, in run.py's order; what is refused is refused before anything is built
         cfg.update({k: r[k] for k in HL.RESOLVED_KEYS})
         cfg["keyframes"] = r.get("keyframes")      # the normalised block, None when off (interval 1 included)
+        cfg["noise_warp"] = r.get("noise_warp")    # the normalised block, None unless noise_mode warp
         self.cfg = SimpleNamespace(**cfg)
         self.fbc, self.light, self.img2img, self.highres = r["fbc"], r["light"], r["img2img"], r["highres"]
         self.normal_sides = r["normal_sides"]                                      # () unless generation.normal
@@ -149,6 +156,7 @@ class Generator:
         self.bg_index = None               # fbc under light_path: the image of bg_frames that is each frame's background (None: bg_frames as they are)
         self._bg_per_frame = None          # fbc: is the background one frame per frame?  The entry point says (None: by the length of its latents)
         self.fbc_alpha = None              # fbc with matting: the alpha of this rank's frames (prepare_fbc), the weight of detail_transfer
+        self.warp_flows = None             # noise_mode warp: (past_flows, mask_bwds) of ALL frames at the working size (prepare_start)
         cin = getattr(self.unet, "w", {}).get("conv_in", (None, None, None))[2]      # a stand-in engine may carry no weights
         if cin is not None and cin != 4 + HL.cond_channels(c.iclight_model):
             raise ValueError(f"generation.iclight_model {c.iclight_model}: the UNet's conv_in takes {cin} channels, expected "
@@ -165,10 +173,11 @@ class Generator:
             c.max_tokens_per_pass = default_max_tokens_per_pass(self.unet, self.dev, reserve)
 
     # ------------------------------------------------------------------ data
-    def prepare_data(self, frames, background=None):
+    def prepare_data(self, frames, background=None, past_flows=None, mask_bwds=None):
         """frames: this rank's block [n_local,3,H,W] f32 in [0,1] on the device (generate.py:138-204).  background [1|n_local,3,H,W]:
         background compositing (generate.py:147-167): alpha from BriaRMBG on the resized frames, `alpha*fg + (1-alpha)*bg`.
-        Under iclight_model fbc nothing is composited: prepare_fbc builds the two condition images and self.frames stays the source."""
+        Under iclight_model fbc nothing is composited: prepare_fbc builds the two condition images and self.frames stays the source.
+        past_flows / mask_bwds: the backward flows and masks of ALL frames, which noise_mode warp carries the noise along (prepare_start)."""
         c = self.cfg
         if self.fbc:
             self.prepare_fbc(frames, background)
@@ -178,14 +187,18 @@ class Generator:
             alpha = self.rmbg.estimate_alpha(frames, self.batch_size)
             frames = alpha * frames + (1 - alpha) * background.to(frames)
         self.frames = frames.contiguous()
-        self.prepare_start(frames.shape[0], *frames.shape[-2:])
+        self.prepare_start(frames.shape[0], *frames.shape[-2:], past_flows, mask_bwds)
 
-    def prepare_start(self, n, H, W):
+    def prepare_start(self, n, H, W, past_flows=None, mask_bwds=None):
         """The start of one denoise of n local frames at (H, W): the device generator seeded afresh, then init_noise (or start_noise for an
-        img2img start, or the saved latents of latents_path).  Generator.normals calls it once per direction, so all four start alike."""
+        img2img start, or the saved latents of latents_path).  Generator.normals calls it once per direction, so all four start alike.
+        noise_mode warp: past_flows [n_total,2,H,W] / mask_bwds [n_total,1,H,W] of all frames are checked and kept for the start and the steps."""
         c = self.cfg
         self.h, self.w = H // 8, W // 8
         self._total(n)
+        self.warp_flows = None
+        if c.noise_warp is not None:
+            self.warp_flows = self._warp_inputs(past_flows, mask_bwds, 8 * self.h, 8 * self.w)
         self.rng_dev = torch.Generator(device=self.dev).manual_seed(int(c.seed))
         self.start_noise = None
         if self.img2img:
@@ -193,6 +206,9 @@ class Generator:
                 what = f"light_path {c.light_path}" if self.light else f"init_latent '{c.init_latent}'"
                 print(f"[INFO] {what}: the start is built from it, generation.latents_path is not consulted.")
         elif c.latents_path is not None and self._load_start_latents(n):
+            if c.noise_warp is not None:
+                print("[INFO] noise_mode warp: the start comes from generation.latents_path; of the warped noise only generation.noise_warp.steps "
+                      f"({'on' if c.noise_warp['steps'] else 'off'}) applies.")
             return
         z = self._draw_start(self.h, self.w)
         if self.img2img:
@@ -213,14 +229,35 @@ class Generator:
 
     def _draw_start(self, h, w):
         """z of one start at latent size (h, w), f32 from rng_dev.  noise_mode same: [1,4,h,w], one frame for all; vanilla: n_total frames are
-        drawn and this rank's block is taken."""
+        drawn and this rank's block is taken; warp: this rank's block of the chain over all n_total frames (_warp_chain)."""
         mode = self.cfg.noise_mode.lower()
         if mode == "same":
             return torch.randn(1, 4, h, w, generator=self.rng_dev, device=self.dev, dtype=torch.float32)
+        if mode == "warp":
+            lo, hi = self.dist.range(self.n_total)
+            return self._warp_chain(h, w)[lo:hi]
         if mode != "vanilla":
             raise NotImplementedError(f"Noise mode '{self.cfg.noise_mode}' is not supported.")
         lo, hi = self.dist.range(self.n_total)
         return torch.randn(self.n_total, 4, h, w, generator=self.rng_dev, device=self.dev, dtype=torch.float32)[lo:hi]
+
+    def _warp_inputs(self, past_flows, mask_bwds, H, W):
+        """noise_mode warp: the flows and masks of all n_total frames at the working size, as noisewarp.warp_chain takes them."""
+        shapes = [None if t is None else tuple(t.shape) for t in (past_flows, mask_bwds)]
+        if shapes != [(self.n_total, 2, H, W), (self.n_total, 1, H, W)]:
+            raise ValueError(f"generation.noise_mode warp: past_flows / mask_bwds {shapes}, expected {(self.n_total, 2, H, W)} and "
+                             f"{(self.n_total, 1, H, W)} -- the backward flows and masks of ALL frames at the working size "
+                             "(Generator(...)(frames, conds, conds_t, past_flows, mask_bwds, ...))")
+        return past_flows.to(self.dev).float().contiguous(), mask_bwds.to(self.dev).float().contiguous()
+
+    def _warp_chain(self, h, w):
+        """noise_mode warp: one chain z [n_total,4,h,w] f32 over all frames from rng_dev -- one [4,8h,8w] draw per frame, in frame order, on every
+        rank, so neither batching nor the number of ranks changes the stream."""
+        from .noisewarp import field_draw, warp_chain
+        if self.warp_flows is None:
+            raise ValueError("generation.noise_mode warp: the backward flows and masks of all frames are missing (prepare_data(..., past_flows=, "
+                             "mask_bwds=))")
+        return warp_chain(field_draw(self.rng_dev, self.dev), *self.warp_flows, self.n_total, 8 * h, 8 * w)
 
     def _noised_start(self, n, x0, x0_stride, z, schedule):
         """The f16 start latents [n,4,h,w] of an img2img denoise (the img2img pipeline's add_noise): alpha*x0 + sigma_t*z at the first executed sigma
@@ -658,6 +695,7 @@ class Generator:
         yt_sampler = HL.ChunkSampler(c.seed + 1, c.chunk_size, c.merge_global, c.chunk_ord)
         cc_full = self._conds_full(x, concat_conds)
         lo, hi = d.range(self.n_total)
+        warp_steps = c.noise_warp is not None and c.noise_warp["steps"]      # the per-step noise is a chain over the flows too
         for i, t in enumerate(sch.timesteps.tolist()):
             self._unet_xy(x, concat_conds, xy_sampler.get_chunks(n_local), conds, t, noises)
             if c.alpha_t > 0:
@@ -668,7 +706,10 @@ class Generator:
                 self.L.tcl_adain_fuse_f16(noises_t, noises, n_local * 4, self.h * self.w, float(alphas[i]), stream())
             z = None
             if i < len(sch.timesteps) - 1:     # the last SDE step has sigma_t = 0: its noise term vanishes
-                zf = torch.randn(self.n_total, 4, self.h, self.w, generator=self.rng_dev, device=self.dev, dtype=torch.float32)
+                if warp_steps:
+                    zf = self._warp_chain(self.h, self.w)
+                else:
+                    zf = torch.randn(self.n_total, 4, self.h, self.w, generator=self.rng_dev, device=self.dev, dtype=torch.float32)
                 z = zf[lo:hi].to(H16).contiguous()
             sch.step(noises, t, x, noise=z)
             self.unet.tome.reset_global_tokens()       # post_iter (generate_utils.py:235-238)
@@ -679,6 +720,7 @@ class Generator:
                  background_per_frame=None, source=None, flows=None, keyframes=None):
         """frames: local block [n_local,3,H,W]; conds / conds_t: [2,L,768] f16 (uncond, cond) text embeddings for the xy / yt
         passes (generate.py:553-555) -- under generation.prompt_path conds is the FrameText of frame_text; past_flows / mask_bwds / unq_inv: stage-2 inputs for ALL frames (device).
+        With generation.noise_mode warp: past_flows / mask_bwds are needed whether stage 1 / 2 run or not -- the noise is carried along them.
         Returns (relit frames [N,3,H,W] f32, info dict).
         With generation.highres_scale > 1: frames_hr is the local block at HL.highres_size [n_local,3,H2,W2], the stage-2 inputs live at that size
         and so do the returned frames.
@@ -721,7 +763,7 @@ class Generator:
                              f"{n_out} frames of the run at the size of the result (Generator(...)(..., source=...))")
         ev = self._now
         t0 = ev()
-        self.prepare_data(frames, background)
+        self.prepare_data(frames, background, past_flows, mask_bwds)
         # fbc: is the background one frame per frame?  Under light_path when the run has several ramps, else the caller's word (None: by its length)
         self._bg_per_frame = (self.bg_index is not None) if self.light else (None if background_per_frame is None else bool(background_per_frame))
         concat_conds = self.encode_conds()

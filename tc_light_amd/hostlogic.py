@@ -494,6 +494,34 @@ def keyframe_ids(n, interval):
     return ids
 
 
+NOISE_WARP_DEFAULTS = dict(steps=True)    # generation.noise_warp: is the per-step noise of the SDE solver a warped chain too?
+
+
+def check_noise_warp(noise_mode, block=None, keyframes=None, highres_scale=1.0, normal=False):
+    """generation.noise_mode warp and its block generation.noise_warp: {steps: <bool>} -> the block with the defaults filled in (NOISE_WARP_DEFAULTS),
+    or None under every other noise_mode -- the block is read under warp only, and what an unknown mode raises stays with Generator._draw_start.
+    Each fault is a ValueError naming its key: a block that is no mapping, an unknown key, a steps that is no bool.  Refused by both key names as out
+    of scope: generation.keyframes (the flows of consecutive frames do not connect key frames), generation.highres_scale > 1 (the flows live at the
+    final size, the first denoise at the working size), generation.normal."""
+    if not isinstance(noise_mode, str) or noise_mode.lower() != "warp":
+        return None
+    if block is not None and (not isinstance(block, dict) or any(k not in NOISE_WARP_DEFAULTS for k in block)):
+        raise ValueError(f"generation.noise_warp {block!r}: expected null or {{steps: <bool>}}")
+    out = dict(NOISE_WARP_DEFAULTS, **(block or {}))
+    if not isinstance(out["steps"], bool):
+        raise ValueError(f"generation.noise_warp.steps {out['steps']!r}: expected true or false")
+    if keyframes is not None:
+        raise ValueError("generation.noise_mode warp together with generation.keyframes is not supported: the flows of consecutive frames do not "
+                         "connect key frames")
+    if highres_scale is not None and float(highres_scale) > 1.0:
+        raise ValueError("generation.noise_mode warp together with generation.highres_scale > 1 is not supported: the flows live at the final size, "
+                         "the first denoise at the working size")
+    if normal:
+        raise ValueError("generation.noise_mode warp together with generation.normal is not supported: the four relights start from one noise and "
+                         "no flows are estimated")
+    return out
+
+
 # what resolve_generation normalises: run.py writes these back into the configuration (config.yaml records them), Generator into its cfg
 RESOLVED_KEYS = ("init_latent", "init_strength", "highres_scale", "highres_denoise", "iclight_model", "bg_source", "light_path", "prompt_path")
 
@@ -505,7 +533,8 @@ def resolve_generation(cfg):
     fbc / light / img2img / highres, normal_sides (() unless generation.normal), schedule = (scheduler steps, begin index, steps executed) -- the
     whole n_timesteps unless the start is an img2img one -- and schedule_highres (the second pass's; None when it is off).  generation.keyframes
     (check_keyframes; cfg may carry data.scene_type as scene_type) is checked here too; its normalised block is in the result as "keyframes" only
-    when the key is on (interval > 1), so a run without it resolves to exactly what it did."""
+    when the key is on (interval > 1), so a run without it resolves to exactly what it did; likewise "noise_warp" (check_noise_warp), in the result
+    under noise_mode warp only."""
     n, normal, bg_cond = cfg["n_timesteps"], cfg["normal"], bool(cfg.get("background_cond"))
     r = {}
     r["init_latent"], r["init_strength"] = check_init(cfg["init_latent"], cfg["init_strength"], n)
@@ -518,6 +547,9 @@ def resolve_generation(cfg):
                                 cfg.get("post_opt_mode", "replicated"), bool(cfg.get("shard_post_opt")))
     if keyframes is not None:
         r["keyframes"] = keyframes
+    noise_warp = check_noise_warp(cfg.get("noise_mode"), cfg.get("noise_warp"), keyframes, r["highres_scale"], bool(normal))
+    if noise_warp is not None:
+        r["noise_warp"] = noise_warp
     r["fbc"], r["light"], r["highres"] = r["iclight_model"] == "fbc", r["light_path"] is not None, r["highres_scale"] != 1.0
     r["img2img"] = r["init_latent"] != "none" or (r["light"] and not r["fbc"])      # fc: the path's ramps are the start
     r["schedule"] = img2img_schedule(n, r["init_strength"]) if r["img2img"] else (n, 0, n)
