@@ -50,6 +50,26 @@ def seeded_state_dict(seed=5):
     return sd
 
 
+def gru_taps(w):
+    """SepConvGRU weight [co, 384, 1, 5] / [co, 384, 5, 1] -> [co, tap, ci] with ci = h | inp | motion."""
+    return w.reshape(w.shape[0], 384, 5).permute(0, 2, 1)
+
+
+def gru_hm_weight(t):
+    """[co, 5, 384] -> [co, 1280]: the (h or r*h) | motion share, column tap*256 + src*128 + c (the layout tcl_raft_sepconv_f16 reads at C1 = 128)."""
+    return torch.cat([t[:, :, :128], t[:, :, 256:]], 2).reshape(t.shape[0], 1280)
+
+
+def gru_ctx_weight(t):
+    """[co, 5, 384] -> [co, 640]: the inp share, column tap*128 + c (C1 = 0)."""
+    return t[:, :, 128:256].reshape(t.shape[0], 640)
+
+
+def convf1_weight_t(w):
+    """[128, 2, 7, 7] -> w_t [98, 128] with row c*49 + ky*7 + kx."""
+    return w.reshape(128, 98).t().contiguous()
+
+
 def check_size(H, W):
     """The working size RAFT can take here: InputPadder pads to multiples of 8 and the raft branch of load_flow never unpads (so only sizes the
     padder leaves alone are served), and the coarsest correlation level must be at least 2 x 2 (bilinear_sampler divides by W - 1)."""
@@ -73,19 +93,15 @@ class RAFTEngine(FlowEngine):
         f = {k[len("update_block."):]: v.float() for k, v in state_dict.items() if k.startswith("update_block.")}
         self.convc1 = Lin(f["encoder.convc1.weight"], f["encoder.convc1.bias"], d)                       # 324 -> 384 padded input channels
         self.convc2 = self._conv3w(f["encoder.convc2.weight"], f["encoder.convc2.bias"], 192)
-        self.convf1 = (f["encoder.convf1.weight"].reshape(128, 98).t().contiguous().to(d), f["encoder.convf1.bias"].contiguous().to(d))
+        self.convf1 = (convf1_weight_t(f["encoder.convf1.weight"]).to(d), f["encoder.convf1.bias"].contiguous().to(d))
         self.convf2 = self._conv3w(f["encoder.convf2.weight"], f["encoder.convf2.bias"], 64)
         self.conv = self._conv3w(f["encoder.conv.weight"], f["encoder.conv.bias"], 128)                       # 126 + 2 zero channels (the flow goes there)
         self.gru = []
         for dn in ("1", "2"):
-            taps = lambda g: f[f"gru.conv{g}{dn}.weight"].reshape(128, 384, 5).permute(0, 2, 1)            # [co, tap, ci]: ci = h | inp | motion
+            taps = lambda g: gru_taps(f[f"gru.conv{g}{dn}.weight"])                                      # [co, tap, ci]: ci = h | inp | motion
             zr, q = torch.cat([taps("z"), taps("r")]), taps("q")
-
-            def hm(t):                                                  # [co, 5, 256] = (h or r*h) | motion, column tap*256 + src*128 + c
-                return torch.cat([t[:, :, :128], t[:, :, 256:]], 2).reshape(t.shape[0], 1280).to(H16).contiguous().to(d)
-
-            def ctx(t):                                                 # the inp share: [co, 5*128]
-                return t[:, :, 128:256].reshape(t.shape[0], 640).to(H16).contiguous().to(d)
+            hm = lambda t: gru_hm_weight(t).to(H16).contiguous().to(d)                                    # (h or r*h) | motion
+            ctx = lambda t: gru_ctx_weight(t).to(H16).contiguous().to(d)                                  # the inp share
 
             bzr = torch.cat([f[f"gru.convz{dn}.bias"], f[f"gru.convr{dn}.bias"]]).contiguous().to(d)
             self.gru.append(dict(w_zr=hm(zr), w_q=hm(q), c_zr=ctx(zr), c_q=ctx(q), b_zr=bzr, b_q=f[f"gru.convq{dn}.bias"].contiguous().to(d)))
