@@ -8,9 +8,14 @@ transformer block.  Differences, all deliberate and documented in DESIGN.md:
     draws shared by all blocks of one UNet forward -- in the reference every block owns a generator forked from the same
     state, so they draw identical numbers in lock-step (vidtome/utils.py:18-30, patch.py:215-231);
   * ties in the greedy matching are broken deterministically (csrc/merge.hip header).
+
+`compute_merge` is ONE chain.  The cosine-normalised rows (the matching metric) are CARRIED beside the tokens instead of re-derived: normalisation is per
+row, so `normalise(gather(x)) == gather(normalise(x))` bit for bit, and wherever tokens move through a map their metric moves through the same map in
+the same launch (tcl_gather_rows_pair_f16).  Nothing is copied together either: the survivors of the last local round are gathered straight into their
+slot of the [local | bank] block, and a bank is written straight into its slot of the block of the chunk that will meet it.  The chain that materialises
+every stage (gather -> `cat` copy -> normalise -> match) lives on as the test reference, tests/tome_chain_ref.py: same maps, tokens and banks, bit for bit.
 """
 import math
-import os
 from typing import NamedTuple, Optional
 
 import numpy as np
@@ -43,7 +48,7 @@ class VidToMe:
         self.enabled = enabled
         self.rng = np.random.default_rng(seed)
         self.banks = {}                 # block name -> [2, Tb, C] f16 (module.global_tokens, patch.py:60-82); may be a strided view (see _home)
-        self._bank_met = {}             # block name -> the bank's cosine-normalised rows, same shape / strides (None: not carried, normalise on use)
+        self._bank_met = {}             # block name -> the bank's cosine-normalised rows, same shape / strides
         self._home = {}                 # block name -> the [src | dst] blocks of the NEXT chunk, which already hold this bank in their slot (compute_merge)
         self._cur = (None, 0)
         self._pos = {}
@@ -79,7 +84,6 @@ class VidToMe:
     def begin_step(self, Fs, size):
         """One UNet pass over the chunks Fs (reference chunk order): draw each chunk's (randf per round, coin) in that order."""
         self.size = size
-        self._legacy_chain = os.environ.get("TCL_TOME_CAT", "0") != "0"       # gather -> cat -> normalise -> match instead of the carried-metric chain
         self._chunks = []
         for F in Fs:
             if self.draws is not None:
@@ -117,15 +121,23 @@ class VidToMe:
         return hit
 
     # Maps are int32 tensors: 1-D when the two batch entries share the matching (align_batch, merge.py:93-108), [2, n] when every entry has
-    # its own (merge.py:109-118).  The three helpers below hide the difference from compute_merge.
-    def _gather(self, s1, bs1, mp, out, bso, n, C, nb=2):
-        L = self.L
+    # its own (merge.py:109-118).  The helpers below hide the difference from compute_merge.
+    def _each(self, mp, nb, launch, *blocks):
+        """launch(map, entries, *tensors) once over all nb batch entries when they share `mp` (1-D, or None = identity), else once per entry b with
+        mp[b] and every block from its entry b on.  blocks: (tensor or None, elements between its batch entries)."""
         if mp is None or mp.dim() == 1:
-            L.tcl_gather_rows_f16(s1, bs1, 0, 0, mp if mp is not None else 0, out, bso, nb, n, C, stream())
+            launch(mp, nb, *(t for t, _ in blocks))
         else:
-            f1, fo = s1.reshape(-1), out.reshape(-1)
             for b in range(nb):
-                L.tcl_gather_rows_f16(f1[b * bs1:], bs1, 0, 0, mp[b], fo[b * bso:], bso, 1, n, C, stream())
+                launch(mp[b], 1, *(None if t is None else torch.as_strided(t, (1,), (1,), t.storage_offset() + b * bs) for t, bs in blocks))
+
+    def _gather(self, s1, bs1, mp, out, bso, n, C, nb=2):
+        self._each(mp, nb, lambda m, e, s, o: self.L.tcl_gather_rows_f16(s, bs1, 0, 0, m, o, bso, e, n, C, stream()), (s1, bs1), (out, bso))
+
+    def _move(self, sa, bsa, sb, bsb, mp, oa, boa, ob, bob, n, C, nb):
+        """oa[b][i] = sa[b][mp[i]] and ob[b][i] = sb[b][mp[i]] in one launch: a token block and its metric through the same map (sb = ob = None: tokens only)."""
+        self._each(mp, nb, lambda m, e, a, b, c, d: self.L.tcl_gather_rows_pair_f16(a, bsa, b, bsb, m, c, boa, d, bob, e, n, C, stream()),
+                   (sa, bsa), (sb, bsb), (oa, boa), (ob, bob))
 
     def _compose(self, outer, inner, off, n):
         """out[i] = outer[off + inner[i]] (inner None = identity), per batch entry when either map is."""
@@ -143,7 +155,7 @@ class VidToMe:
         return out
 
     def _merged(self, cat, T, mrg, Tm, C, ne, lazy):
-        if lazy:
+        if lazy and mrg.dim() == 1:
             return Merged(cat, T * C, mrg)
         out = torch.empty(ne, Tm, C, dtype=H16, device=self.dev)
         self._gather(cat, T * C, mrg, out, Tm * C, Tm, C, ne)
@@ -151,34 +163,16 @@ class VidToMe:
 
     def unmerge_add(self, h, bsh, y, T, unm, n, C, nb=2):
         """h[b][i] += y[b][unm[i]]: unmerge of attn1's output + residual (patch.py:178-179); unm None = identity."""
-        L = self.L
-        if unm is None or unm.dim() == 1:
-            L.tcl_gather_add_rows_f16(h, bsh, y, T * C, unm if unm is not None else 0, nb, n, C, stream())
-        else:
-            fh, fy = h.reshape(-1), y.reshape(-1)
-            for b in range(nb):
-                L.tcl_gather_add_rows_f16(fh[b * bsh:], bsh, fy[b * T * C:], T * C, unm[b], 1, n, C, stream())
+        self._each(unm, nb, lambda m, e, hh, yy: self.L.tcl_gather_add_rows_f16(hh, bsh, yy, T * C, m, e, n, C, stream()), (h, bsh), (y, T * C))
 
-    def _match(self, tokens, T, C, a_pos, na, b_pos, nb, ratio, tbs=None, affine=None, metric=None, ne=2):
-        """tokens: two [T, C] slices tbs elements apart (default T*C: a contiguous [2, T, C]) -> (mrg [na-r+nb], unm [T]) int32 maps ([2, .]
-        each without align_batch).  metric: the tokens' cosine-normalised rows in the same layout, when the producer already wrote them
-        (tcl_layernorm_metric_f16); otherwise they are normalised here.  ne: batch entries present (1: the unconditional / conditional pair is
-        known to be identical, see compute_merge).
+    def _match(self, metric, mbs, T, C, a_pos, na, b_pos, nb, ratio, affine=None, ne=2):
+        """metric: the cosine-normalised rows of ne [T, C] token slices, mbs elements apart -> (mrg [na-r+nb], unm [T], na-r+nb) int32 maps ([ne, .]
+        each without align_batch).  ne: batch entries present (1: the unconditional / conditional pair is known to be identical, see compute_merge).
         affine = (a_split, a_gap, b0): a_pos[i] = i if i < a_split else i + a_gap, b_pos[j] = b0 + j (true of the single-round VidToMe matches;
         lets the C = 320 matches take the strip-resident kernel, csrc/merge.hip::k_tome_match320 -- same maps, bit for bit)."""
         L = self.L
         r = min(na, int(na * ratio))                                            # merge.py:90
-        mbs = T * C                                                             # elements between the two batch entries of the metric
-        if metric is not None:
-            metric, mbs = metric.reshape(-1), (T * C if tbs is None else tbs)
-        else:
-            metric = torch.empty(ne * T * C, dtype=H16, device=self.dev)
-            if ne == 1 or tbs is None or tbs == T * C:
-                L.tcl_tome_normalize_f16(tokens, metric, ne * T, C, stream())
-            else:
-                flat = tokens.reshape(-1)
-                L.tcl_tome_normalize_f16(flat, metric, T, C, stream())
-                L.tcl_tome_normalize_f16(flat[tbs:], metric[T * C:], T, C, stream())
+        metric = metric.reshape(-1)
         need = L.tcl_tome_match_workspace_bytes(na)
         if self._ws is None or self._ws.numel() < need:
             self._ws = torch.zeros(need, dtype=torch.uint8, device=self.dev)        # zeroed once; every match leaves it zero again
@@ -206,8 +200,8 @@ class VidToMe:
         return (TL, 0, TL) if coin > self.args["global_rand"] else (Tb, Tb, 0)
 
     def _next_block(self, ne, TL_bank, N, C):
-        """If the chunk that will meet the bank this chunk leaves is known (the next one of the pass), allocate ITS [src | dst] token and metric blocks now
-        and return where the bank goes in them: (cat, catm, TL_next, loff, boff).  The bank is then written once, into place."""
+        """If the chunk that will meet the bank this chunk leaves is known (the next one of the pass) and has one local round, allocate ITS [src | dst]
+        token and metric blocks now and return where the bank goes in them: (cat, catm, TL_next, loff, boff).  The bank is then written once, into place."""
         lst, i = self._cur
         if lst is None or i + 1 >= len(lst):
             return None
@@ -226,66 +220,6 @@ class VidToMe:
             return torch.empty(ne, TL, C, dtype=H16, device=self.dev), torch.empty(ne, TL, C, dtype=H16, device=self.dev)
         cat_n, catm_n, _, _, boff_n = self._home[name] = nxt
         return cat_n[:, boff_n:boff_n + TL], catm_n[:, boff_n:boff_n + TL]
-
-    def _compute_merge_carried(self, name, x, F, N, C, xbs, metric, ne, lazy_merged):
-        """compute_merge for the shape every TC-Light configuration has (one local round, maps shared by the batch entries, global merge on), with the
-        cosine-normalised rows CARRIED beside the tokens instead of re-derived: normalisation is per row, so `normalise(gather(x))` == `gather(normalise(x))`
-        bit for bit, and the metric of the [local | bank] block is the two gathers the tokens take anyway (tcl_gather_rows_pair_f16: one launch moves
-        both).  The block itself is never copied together: the local survivors are gathered straight into their slot of it, and the bank was written into
-        its slot by the chunk that left it (`_next_block`: the next chunk's frame count and coin were drawn at begin_step, so its layout is known).
-        Per chunk and block this drops two copies of T x C, one normalisation of T x C (k_tome_normalize: 4.6 s of side-stream kernel time per 300-frame
-        pass in round 5) and three launches.  Same maps, tokens and banks as the legacy chain, bit for bit (tests/test_gpu_kernels.py, TCL_TOME_CAT=1)."""
-        a, L = self.args, self.L
-        FN, TL = F * N, self._local_len(F, N)
-        if metric is None:                                                      # norm1 did not write it (direct callers / TCL_LN_METRIC=0)
-            mx, mbs = torch.empty(ne, FN, C, dtype=H16, device=self.dev), FN * C
-            flat = x.reshape(-1)
-            for b in range(ne):
-                L.tcl_tome_normalize_f16(flat[b * xbs:], mx[b], FN, C, stream())
-        else:
-            mx, mbs = metric, xbs
-        mrg1 = unm1 = None
-        if F > 1:
-            a_pos, b_pos = self._positions(F, N, self.randf, 0)
-            mrg1, unm1, Tn = self._match(None, FN, C, a_pos, a_pos.numel(), b_pos, b_pos.numel(), a["local_merge_ratio"], tbs=mbs,
-                                         affine=(self.randf * N, N, self.randf * N), metric=mx, ne=ne)
-            assert Tn == TL
-        bank, bmet, home = self.banks.get(name), self._bank_met.get(name), self._home.pop(name, None)
-        if bank is None:                                                        # patch.py:81-82: the first chunk seeds the bank with its local tokens
-            tok, met = self._bank_slot(name, ne, TL, N, C)
-            L.tcl_gather_rows_pair_f16(x, xbs, mx, mbs, mrg1 if mrg1 is not None else 0, tok, tok.stride(0), met, met.stride(0), ne, TL, C, stream())
-            self.banks[name], self._bank_met[name] = tok, met
-            if self.trace is not None:
-                self.trace.append(dict(name=name, F=F, unm=unm1, gather=mrg1, mrg1=mrg1, T=TL))
-            return (Merged(tok, tok.stride(0), None) if lazy_merged else Merged(tok.contiguous(), TL * C, None)), unm1, TL
-        if bank.shape[0] != ne:
-            raise RuntimeError(f"VidToMe bank of block {name!r} was seeded with {bank.shape[0]} batch entr{'y' if bank.shape[0] == 1 else 'ies'}, this call "
-                               f"carries {ne}: call reset_global_tokens() when switching between forward_many(cfg_pair=True) and the two-entry paths")
-        Tb = bank.shape[1]
-        src_len, loff, boff = self._slots(self.coin, TL, Tb)
-        T = TL + Tb
-        if home is not None and home[0].shape == (ne, T, C) and home[2:] == (TL, loff, boff) and bank.data_ptr() == home[0][:, boff:].data_ptr():
-            cat, catm = home[0], home[1]                                        # the bank (and its metric) already sit in their slot
-        else:
-            cat, catm = torch.empty(ne, T, C, dtype=H16, device=self.dev), torch.empty(ne, T, C, dtype=H16, device=self.dev)
-            if bmet is not None:
-                L.tcl_gather_rows_pair_f16(bank, bank.stride(0), bmet, bmet.stride(0), 0, cat[:, boff:], T * C, catm[:, boff:], T * C, ne, Tb, C, stream())
-            else:
-                L.tcl_gather_rows_pair_f16(bank, bank.stride(0), 0, 0, 0, cat[:, boff:], T * C, 0, 0, ne, Tb, C, stream())
-                for b in range(ne):
-                    L.tcl_tome_normalize_f16(bank[b], catm[b, boff:], Tb, C, stream())
-        L.tcl_gather_rows_pair_f16(x, xbs, mx, mbs, mrg1 if mrg1 is not None else 0, cat[:, loff:], T * C, catm[:, loff:], T * C, ne, TL, C, stream())
-        mrg2, unm2, Tm = self._match(None, T, C, self._range(0, src_len), src_len, self._range(src_len, T), T - src_len, a["global_merge_ratio"],
-                                     tbs=T * C, affine=(src_len, 0, src_len), metric=catm, ne=ne)
-        merged = self._merged(cat, T, mrg2, Tm, C, ne, lazy_merged)
-        unm = self._compose(unm2, unm1, loff, FN)                               # 2s-unmerge then the randframe unmerge (func_warper(u_ls[::-1]))
-        bmap = self._compose(mrg2, unm2[loff:], 0, TL)                          # bank <- u(merged_tokens), local part (patch.py:80)
-        tok, met = self._bank_slot(name, ne, TL, N, C)
-        L.tcl_gather_rows_pair_f16(cat, T * C, catm, T * C, bmap, tok, tok.stride(0), met, met.stride(0), ne, TL, C, stream())
-        self.banks[name], self._bank_met[name] = tok, met
-        if self.trace is not None:
-            self.trace.append(dict(name=name, F=F, unm=unm, mrg2=mrg2, mrg1=mrg1, T=Tm, loff=loff, boff=boff, TL=TL, bmap=bmap))
-        return merged, unm, Tm
 
     # ---- patch.py:14-91
     def merges(self, N):
@@ -306,65 +240,71 @@ class VidToMe:
         a = self.args
         if not self.merges(N):
             return None
-        L = self.L
+        FN = F * N
         if xbs is None:
-            xbs = F * N * C
-        if a["align_batch"] and a["merge_global"] and F <= a["target_stride"] and not self._legacy_chain:
-            return self._compute_merge_carried(name, x, F, N, C, xbs, metric, ne, lazy_merged)
-        self._home.pop(name, None)
-        self._bank_met.pop(name, None)
+            xbs = FN * C
+        seq, sbs, met, mbs = x, xbs, metric, xbs                               # the current sequence and its metric: ne slices sbs / mbs elements apart
+        if met is None and (F > 1 or a["merge_global"]):                        # norm1 did not write it (direct callers / TCL_LN_METRIC=0)
+            met, mbs = torch.empty(ne, FN, C, dtype=H16, device=self.dev), FN * C
+            flat = x.reshape(-1)
+            for b in range(ne):
+                self.L.tcl_tome_normalize_f16(flat[b * xbs:], met[b], FN, C, stream())
         # ---- local merging (patch.py:36-58): randframe rounds until one frame is left -- one round for F <= target_stride (every TC-Light
-        # config), 8 -> 2 -> 1 / 16 -> 4 -> 1 for longer chunks, the unmerged tokens of a round riding along as extra dst tokens of the next
-        mrg1 = unm1 = None
-        seq, sbs, T, unm_pre = x, xbs, F * N, 0
+        # config), 8 -> 2 -> 1 / 16 -> 4 -> 1 for longer chunks, the unmerged tokens of a round riding along as extra dst tokens of the next.
+        # After the loop the local tokens are the rows `mrg` (None: all) of seq, TL of them; mrg1 / unm1 are the rounds' maps composed.
+        mrg = mrg1 = unm1 = None
+        TL, unm_pre = FN, 0
         for cur, randf in zip(*self.round_frames(F, self.randfs)):
+            if mrg is not None:                                                 # the round before was not the last: its survivors become a sequence
+                nxt = torch.empty(2, ne, TL, C, dtype=H16, device=self.dev)
+                self._move(seq, sbs, met, mbs, mrg, nxt[0], TL * C, nxt[1], TL * C, TL, C, ne)
+                seq, met, sbs, mbs = nxt[0], nxt[1], TL * C, TL * C
             a_pos, b_pos = self._positions(cur, N, randf, unm_pre)
             single = unm_pre == 0 and cur <= a["target_stride"]                # dst = the N tokens of frame randf, src = the rest: affine
-            mrg, unm, Tn = self._match(seq, T, C, a_pos, a_pos.numel(), b_pos, b_pos.numel(), a["local_merge_ratio"], tbs=sbs,
-                                       affine=(randf * N, N, randf * N) if single else None, metric=metric if seq is x else None, ne=ne)
-            nxt = torch.empty(ne, Tn, C, dtype=H16, device=self.dev)
-            self._gather(seq, sbs, mrg, nxt, Tn * C, Tn, C, ne)
+            mrg, unm, Tn = self._match(met, mbs, TL, C, a_pos, a_pos.numel(), b_pos, b_pos.numel(), a["local_merge_ratio"],
+                                       affine=(randf * N, N, randf * N) if single else None, ne=ne)
             if mrg1 is None:
                 mrg1, unm1 = mrg, unm
             else:
                 mrg1 = self._compose(mrg1, mrg, 0, Tn)                          # merged slot -> row of the joined input
-                unm1 = self._compose(unm, unm1, 0, F * N)                       # joined position -> slot of the current sequence
+                unm1 = self._compose(unm, unm1, 0, FN)                          # joined position -> slot of the current sequence
             unm_pre += Tn - b_pos.numel()                                       # ret_dict["unm_num"] = na - r
-            seq, sbs, T = nxt, Tn * C, Tn
-        if F > 1:
-            local, TL = seq, T
-        else:
-            TL = N                                       # F == 1: nothing to merge locally; keep the [2, T, C] layout
-            if xbs == N * C or ne == 1:
-                local = x.reshape(-1)[:ne * N * C].view(ne, N, C)
-            else:
-                local = torch.empty(2, N, C, dtype=H16, device=self.dev)
-                L.tcl_gather_rows_f16(x, xbs, 0, 0, 0, local, N * C, 2, N, C, stream())
+            TL = Tn
         if not a["merge_global"]:
+            local = torch.empty(ne, TL, C, dtype=H16, device=self.dev)
+            self._move(seq, sbs, None, 0, mrg, local, TL * C, None, 0, TL, C, ne)
             return Merged(local, TL * C, None), unm1, TL
-        bank = self.banks.get(name)
-        if bank is None:                                                        # patch.py:81-82: the first chunk seeds the bank
-            self.banks[name] = local if F > 1 else local.clone()
+        # ---- global merging (patch.py:59-82) against the block's bank.  The [local | bank] block is never copied together: the local tokens are
+        # gathered straight into their slot of it, and the bank was written into its slot by the chunk that left it (`_next_block`: the next chunk's
+        # frame count and coin were drawn at begin_step, so its layout is known).
+        bank, bmet, home = self.banks.get(name), self._bank_met.get(name), self._home.pop(name, None)
+        if bank is None:                                                        # patch.py:81-82: the first chunk seeds the bank with its local tokens
+            tok, tmet = self._bank_slot(name, ne, TL, N, C)
+            self._move(seq, sbs, met, mbs, mrg, tok, tok.stride(0), tmet, tmet.stride(0), TL, C, ne)
+            self.banks[name], self._bank_met[name] = tok, tmet
             if self.trace is not None:
                 self.trace.append(dict(name=name, F=F, unm=unm1, gather=mrg1, mrg1=mrg1, T=TL))
-            return Merged(local, TL * C, None), unm1, TL
+            return (Merged(tok, tok.stride(0), None) if lazy_merged else Merged(tok.contiguous(), TL * C, None)), unm1, TL
         if bank.shape[0] != ne:       # (a real exception: `python -O` strips asserts and a 2-entry gather would then read past a 1-entry bank)
             raise RuntimeError(f"VidToMe bank of block {name!r} was seeded with {bank.shape[0]} batch entr{'y' if bank.shape[0] == 1 else 'ies'}, this call "
                                f"carries {ne}: call reset_global_tokens() when switching between forward_many(cfg_pair=True) and the two-entry paths")
         Tb = bank.shape[1]
         src_len, loff, boff = self._slots(self.coin, TL, Tb)
         T = TL + Tb
-        cat = torch.empty(ne, T, C, dtype=H16, device=self.dev)
-        L.tcl_gather_rows_f16(local, TL * C, 0, 0, 0, cat[:, loff:], T * C, ne, TL, C, stream())
-        L.tcl_gather_rows_f16(bank, bank.stride(0), 0, 0, 0, cat[:, boff:], T * C, ne, Tb, C, stream())
-        mrg2, unm2, Tm = self._match(cat, T, C, self._range(0, src_len), src_len, self._range(src_len, T), T - src_len,
-                                     a["global_merge_ratio"], affine=(src_len, 0, src_len), ne=ne)
-        merged = self._merged(cat, T, mrg2, Tm, C, ne, lazy_merged and mrg2.dim() == 1)
-        unm = self._compose(unm2, unm1, loff, F * N)                            # 2s-unmerge then the randframe unmerges (func_warper(u_ls[::-1]))
-        bmap = self._compose(mrg2, unm2[..., loff:].contiguous() if unm2.dim() == 2 else unm2[loff:], 0, TL)     # bank <- u(merged_tokens) (patch.py:80)
-        nb_ = torch.empty(ne, TL, C, dtype=H16, device=self.dev)
-        self._gather(cat, T * C, bmap, nb_, TL * C, TL, C, ne)
-        self.banks[name] = nb_
+        if home is not None and home[0].shape == (ne, T, C) and home[2:] == (TL, loff, boff) and bank.data_ptr() == home[0][:, boff:].data_ptr():
+            cat, catm = home[0], home[1]                                        # the bank (and its metric) already sit in their slot
+        else:
+            cat, catm = torch.empty(ne, T, C, dtype=H16, device=self.dev), torch.empty(ne, T, C, dtype=H16, device=self.dev)
+            self._move(bank, bank.stride(0), bmet, bmet.stride(0), None, cat[:, boff:], T * C, catm[:, boff:], T * C, Tb, C, ne)
+        self._move(seq, sbs, met, mbs, mrg, cat[:, loff:], T * C, catm[:, loff:], T * C, TL, C, ne)
+        mrg2, unm2, Tm = self._match(catm, T * C, T, C, self._range(0, src_len), src_len, self._range(src_len, T), T - src_len, a["global_merge_ratio"],
+                                     affine=(src_len, 0, src_len), ne=ne)
+        merged = self._merged(cat, T, mrg2, Tm, C, ne, lazy_merged)
+        unm = self._compose(unm2, unm1, loff, FN)                               # 2s-unmerge then the randframe unmerges (func_warper(u_ls[::-1]))
+        bmap = self._compose(mrg2, unm2[..., loff:], 0, TL)                     # bank <- u(merged_tokens), local part (patch.py:80)
+        tok, tmet = self._bank_slot(name, ne, TL, N, C)
+        self._move(cat, T * C, catm, T * C, bmap, tok, tok.stride(0), tmet, tmet.stride(0), TL, C, ne)
+        self.banks[name], self._bank_met[name] = tok, tmet
         if self.trace is not None:
             self.trace.append(dict(name=name, F=F, unm=unm, mrg2=mrg2, mrg1=mrg1, T=Tm, loff=loff, boff=boff, TL=TL, bmap=bmap))
         return merged, unm, Tm

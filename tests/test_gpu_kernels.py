@@ -1,7 +1,5 @@
 """GPU: each path-1 HIP kernel (through the C ABI) against a plain PyTorch fp32 reference of the same op.
 Tolerance: inputs are f16, accumulation f32, outputs rounded to f16 -> rel-L2 <= 2e-3 per op."""
-import os
-
 import numpy as np
 import pytest
 import torch
@@ -266,56 +264,66 @@ def test_vidtome_maps_vs_oracle(L):
         bank = tome.banks["blk"].cpu().float()       # continue the chain from the HIP bank so later rounds stay comparable
 
 
-def test_vidtome_carried_metric_chain_equals_legacy_chain(L):
-    """Round 6: compute_merge carries the cosine-normalised rows beside the tokens and writes local survivors / banks straight into the next
-    [src | dst] block (no `cat` copy, no second normalisation; vidtome.py `_compute_merge_carried`).  Every map, merged sequence and bank must equal
-    the legacy chain's (TCL_TOME_CAT=1: gather -> cat -> normalise -> match) BIT FOR BIT, over a multi-chunk pass in which the next chunk's layout is
-    planned ahead (begin_step with all chunks), with and without norm1's metric, with one and two batch entries, lazy and materialised merged
-    sequences, and across a pass boundary (a second begin_step meeting the bank the first one left)."""
+def _tome_chain_case(L, passes, size, N, C, ne, with_metric, lazy, **kw):
+    """One chain of chunks (passes: begin_step by begin_step, each chunk (F, randf or one per round, coin)) through VidToMe and through the
+    materialised reference chain (tests/tome_chain_ref.py) on the same tokens: T, merged rows, unm, bank and every trace entry must be EQUAL."""
     from tc_light_amd.vidtome import VidToMe
+    from tome_chain_ref import ChainRef
     g = np.random.default_rng(11)
-    N, C = 345, 320
-    passes = [[(4, 2, 0.9), (3, 0, 0.7), (4, 1, 0.1), (1, -1, 0.3), (2, 1, 0.8)], [(4, 3, 0.2), (4, 0, 0.6)]]
     xs = [[torch.from_numpy(g.standard_normal((1, N, C)).astype(np.float32) + 0.3 * g.standard_normal((2 * F, N, C)).astype(np.float32)).half().cuda()
            for F, _, _ in ps] for ps in passes]
+    tome, ref = VidToMe("cuda", **kw), ChainRef("cuda", **kw)
+    tome.trace = []
+    k = 0
+    for ps, xp in zip(passes, xs):
+        tome.draws = [(rf, coin) for _, rf, coin in ps]
+        tome.begin_step([F for F, _, _ in ps], size)
+        for i, ((F, rf, coin), x) in enumerate(zip(ps, xp)):
+            tome.select_chunk(i)
+            xin = x[:F].contiguous() if ne == 1 else x
+            met = None
+            if with_metric:
+                met = torch.empty_like(xin)
+                L.tcl_tome_normalize_f16(xin, met, xin.shape[0] * N, C, st())
+            merged, unm, T = tome.compute_merge("blk", xin, F, N, C, metric=met, ne=ne, lazy_merged=lazy)
+            src, sbs, idx = merged
+            assert lazy or (idx is None and src.is_contiguous() and src.shape == (ne, T, C) and sbs == T * C)
+            rows = torch.stack([torch.as_strided(src, (T if idx is None else src.shape[1], C), (C, 1), src.storage_offset() + b * sbs) for b in range(ne)])
+            m1 = rows if idx is None else rows[:, idx.long()]
+            m0, u0, T0 = ref.compute_merge("blk", xin, F, list(rf) if isinstance(rf, (list, tuple)) else [rf], coin, N, C, metric=met, ne=ne)
+            b1, b0 = tome.banks.get("blk"), ref.banks.get("blk")
+            assert T == T0 and torch.equal(m1, m0), (kw, ne, with_metric, lazy, k)
+            assert (b1 is None and b0 is None) or torch.equal(b1, b0), (kw, ne, with_metric, lazy, k)
+            assert (unm is None and u0 is None) or torch.equal(unm, u0), (kw, ne, with_metric, lazy, k)
+            k += 1
+    torch.cuda.synchronize()
+    assert len(tome.trace) == len(ref.trace)
+    for a_, b_ in zip(tome.trace, ref.trace):
+        assert a_.keys() == b_.keys()
+        for key in a_:
+            va, vb = a_[key], b_[key]
+            assert (torch.equal(va, vb) if isinstance(va, torch.Tensor) else va == vb), key
+    return k
 
-    def run(legacy, ne, with_metric, lazy):
-        os.environ["TCL_TOME_CAT"] = "1" if legacy else "0"
-        try:
-            tome = VidToMe("cuda")
-            tome.trace = []
-            outs = []
-            for ps, xp in zip(passes, xs):
-                tome.draws = [(rf, coin) for _, rf, coin in ps]
-                tome.begin_step([F for F, _, _ in ps], (15, 23))
-                for i, ((F, _, _), x) in enumerate(zip(ps, xp)):
-                    tome.select_chunk(i)
-                    xin = x[:F].contiguous() if ne == 1 else x
-                    met = None
-                    if with_metric:
-                        met = torch.empty_like(xin)
-                        L.tcl_tome_normalize_f16(xin, met, xin.shape[0] * N, C, st())
-                    merged, unm, T = tome.compute_merge("blk", xin, F, N, C, metric=met, ne=ne, lazy_merged=lazy)
-                    src, sbs, idx = merged
-                    assert lazy or (idx is None and src.is_contiguous() and src.shape == (ne, T, C) and sbs == T * C)
-                    rows = torch.stack([torch.as_strided(src, (T if idx is None else src.shape[1], C), (C, 1), src.storage_offset() + b * sbs) for b in range(ne)])
-                    merged = rows if idx is None else rows[:, idx.long()]
-                    outs.append((merged.clone(), None if unm is None else unm.clone(), T, tome.banks["blk"].clone()))
-            torch.cuda.synchronize()
-            return outs, tome.trace
-        finally:
-            os.environ.pop("TCL_TOME_CAT", None)
+
+def test_vidtome_chain_equals_materialised_reference(L):
+    """compute_merge carries the cosine-normalised rows beside the tokens and writes local survivors / banks straight into the next [src | dst]
+    block (no `cat` copy, no second normalisation).  Every map, merged sequence and bank must equal those of the chain that materialises every stage
+    (tests/tome_chain_ref.py: gather -> cat -> normalise -> match) BIT FOR BIT, over a multi-chunk pass in which the next chunk's layout is
+    planned ahead (begin_step with all chunks), with and without norm1's metric, with one and two batch entries, lazy and materialised merged
+    sequences, and across a pass boundary (a second begin_step meeting the bank the first one left) -- and on the branches TC-Light's own configs
+    leave idle: several randframe rounds (F = 8, 16: two rounds, unm_pre > 0 in the second), per-sample maps (align_batch=False) and no global
+    merge, each a chain of chunks that meets its own bank (the chains of test_vidtome_multi_round_and_per_sample_vs_oracle; N = 150 keeps
+    nb >= 128, so single rounds still take the strip kernel)."""
+    passes = [[(4, 2, 0.9), (3, 0, 0.7), (4, 1, 0.1), (1, -1, 0.3), (2, 1, 0.8)], [(4, 3, 0.2), (4, 0, 0.6)]]
     for ne, with_metric, lazy in ((2, True, True), (2, False, False), (1, True, True), (2, True, False)):
-        (o_new, t_new), (o_old, t_old) = run(False, ne, with_metric, lazy), run(True, ne, with_metric, lazy)
-        assert len(o_new) == len(o_old) == 7
-        for k, ((m1, u1, T1, b1), (m0, u0, T0, b0)) in enumerate(zip(o_new, o_old)):
-            assert T1 == T0 and torch.equal(m1, m0) and torch.equal(b1, b0), (ne, with_metric, lazy, k)
-            assert (u1 is None and u0 is None) or torch.equal(u1, u0)
-        for a_, b_ in zip(t_new, t_old):
-            assert a_.keys() == b_.keys()
-            for key in a_:
-                va, vb = a_[key], b_[key]
-                assert (torch.equal(va, vb) if isinstance(va, torch.Tensor) else va == vb), key
+        assert _tome_chain_case(L, passes, (15, 23), 345, 320, ne, with_metric, lazy) == 7
+    for C, kw, chain in ((320, dict(align_batch=True), [(8, [3, 0], 0.9), (8, [1, 1], 0.2), (6, [2], 0.7), (16, [0, 3], 0.4), (4, [1], 0.8)]),
+                         (640, dict(align_batch=False), [(4, [2], 0.9), (4, [0], 0.1), (8, [3, 0], 0.6), (1, [], 0.3), (3, [1], 0.7)]),
+                         (320, dict(merge_global=False), [(4, [1], 0.5), (8, [2, 1], 0.5), (1, [], 0.5)])):
+        for with_metric, lazy in ((False, False), (True, True)):
+            assert _tome_chain_case(L, [chain], (10, 15), 150, C, 2, with_metric, lazy, **kw) == len(chain)      # one pass: every next chunk is planned for
+            assert _tome_chain_case(L, [[c] for c in chain], (10, 15), 150, C, 2, with_metric, lazy, **kw) == len(chain)      # a pass per chunk: none is
 
 
 def _restored(merged, unm, F, N):

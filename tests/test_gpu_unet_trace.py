@@ -1,6 +1,6 @@
 """Launch trace of the UNet host path: every C-ABI call of two consecutive `forward_many` passes -- function, every scalar argument, which operands
 are null, and the stream it is issued on -- must equal the trace tests/golden/unet_trace.txt recorded (tests/golden/make_golden_unet_trace.py), for the
-default route and for every switch of `Switches.from_env` / TCL_TOME_CAT turned the other way.  The host path only sequences launches and owns buffers,
+default route and for every switch of `Switches.from_env` turned the other way.  The host path only sequences launches and owns buffers,
 so equal traces + equal FLOP figures + equal bits of the noise prediction say that a restructuring of unet.py / vidtome.py changed nothing.
 
 Inputs: seeded random weights, an 8x12 latent (levels 8x12, 4x6, 2x3, 1x2: levels 0 and 1 merge, level 2 and mid do not), chunks [2, 4, 1, 3] with
@@ -20,7 +20,7 @@ pytestmark = pytest.mark.gpu
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "unet_trace.txt")
 SWITCHES = ["TCL_GN_CONCAT", "TCL_LN_METRIC", "TCL_QKV_PANEL", "TCL_MERGE_LAZY", "TCL_LN_GEMM", "TCL_QPANEL", "TCL_TOME_STREAM", "TCL_CFG_DEDUP"]
-VARIANTS = [("default", True, {}), ("cfg_pair=False", False, {})] + [(f"{s}=0", True, {s: "0"}) for s in SWITCHES] + [("TCL_TOME_CAT=1", True, {"TCL_TOME_CAT": "1"})]
+VARIANTS = [("default", True, {}), ("cfg_pair=False", False, {})] + [(f"{s}=0", True, {s: "0"}) for s in SWITCHES]
 HH, WW, FS, T_STEP = 8, 12, [2, 4, 1, 3], 601.0
 DRAWS = [(1, 0.9), (3, 0.2), (-1, 0.7), (0, 0.4)]
 
@@ -57,7 +57,7 @@ def record_variants():
     xh = torch.randn(sum(FS), HH, WW, 8, device="cuda", generator=g).half()
     x = torch.cat([xh, xh]).contiguous()                     # the classifier-free-guidance pair: both halves equal
     text = torch.randn(2, 77, 768, device="cuda", generator=g).half()
-    saved = {k: os.environ.pop(k, None) for k in SWITCHES + ["TCL_TOME_CAT"]}
+    saved = {k: os.environ.pop(k, None) for k in SWITCHES}
     traces, eps_sha = {}, None
     try:
         for name, pair, env in VARIANTS:

@@ -107,10 +107,11 @@ def test_unet_switches_from_env(monkeypatch):
 
 
 def test_environment_is_read_in_the_stated_places_only():
-    """The UNet pass reads its switches once, at its top: `os.environ` appears in unet.py only in Switches.from_env and load_gemm_table, in vidtome.py
-    only in VidToMe.begin_step -- never in the code that runs per block or per chunk."""
+    """The UNet pass reads its switches once, at its top: `os.environ` appears in unet.py only in Switches.from_env and load_gemm_table -- never in the
+    code that runs per block or per chunk -- and vidtome.py reads no environment at all."""
     import inspect
     from tc_light_amd import unet, vidtome
-    for mod, fns in ((unet, (unet.Switches.from_env.__func__, unet.load_gemm_table)), (vidtome, (vidtome.VidToMe.begin_step,))):
-        inside = [inspect.getsource(f).count("os.environ") for f in fns]
-        assert all(n > 0 for n in inside) and inspect.getsource(mod).count("os.environ") == sum(inside), (mod.__name__, inside)
+    fns = (unet.Switches.from_env.__func__, unet.load_gemm_table)
+    inside = [inspect.getsource(f).count("os.environ") for f in fns]
+    assert all(n > 0 for n in inside) and inspect.getsource(unet).count("os.environ") == sum(inside), inside
+    assert "os.environ" not in inspect.getsource(vidtome)
