@@ -685,6 +685,45 @@ size_t tcl_detail_transfer_workspace_bytes(int N, int H, int W, int mode, int lu
 int tcl_detail_transfer_f32(const float* src, const float* relit, const float* mask, float* out, int N, int H, int W, const float* h_taps, int n_taps,
                             int radius, int mode, int luma, float blend, void* ws, long ws_bytes, hipStream_t st);
 
+/* ===================================================================== full-resolution output (generation.fullres); csrc/guided.hip */
+/* The fast guided filter (He & Sun 2015): fit  R ~ a G + b  in every window of the working size, average a and b once more, upsample them and apply
+ * them to the source's native pixels.  Every frame on its own, all frames in one call.
+ *
+ * tcl_guided_fit_f32: src S, relit R [N,3,h,w] f32 in [0,1] -> abar, bbar [N,3,h,w] f32.  Guide G: luma 0: G_c = S_c (every channel guided by itself);
+ *   luma 1: G = Y(S) = fmaf(0.114f, S_B, fmaf(0.587f, S_G, 0.299f * S_R)) for the three channels (detail transfer's Y).  The window of pixel (x, y) is
+ *   x-r .. x+r by y-r .. y+r CLIPPED to the image, cnt its true pixel count (exact in f32).  The moments are centred at 0.5 -- one pass, no second
+ *   pass over the data.  All in f32, no fma contraction, IEEE division, every sum  s = 0; s = s + t_k  in ascending index order, rows (x) first, the
+ *   row sums stored as f32 (the workspace), then columns (y):
+ *     g = G - 0.5f;  q = R_c - 0.5f;   T_g, T_q, T_gg, T_gq = the sums of g, q, g * g, g * q over the window;
+ *     m_g = T_g / cnt ... m_gq = T_gq / cnt;   var = max(m_gg - m_g * m_g, 0);   cov = m_gq - m_g * m_q;
+ *     a = cov / (var + eps);   b = ((m_q - a * m_g) + 0.5f) - 0.5f * a;
+ *     abar = (sum of a over the window) / cnt;   bbar = (sum of b over the window) / cnt      -- the same two passes, the row sums again f32.
+ *   No atomics: equal inputs give equal bits.  ws: tcl_guided_workspace_bytes(N, h, w) = N * TCL_GUIDED_WS_PLANES * h * w * 4 bytes (12 planes of
+ *   moment row sums, reused for the 6 of a and b, + 6 planes a, b); 0 for sizes the call would refuse.  Four launches: moment rows (one block per
+ *   TCL_GUIDED_ROW_SEG pixels of a row), columns fused with the solve (TCL_GUIDED_TILE_W x TCL_GUIDED_TILE_H tiles), rows and columns of a, b.
+ *   TCL_EINVAL, with nothing launched or written: a null pointer, N outside 1 .. 65535, h or w < 1, h > 65535, N * 18 * h * w > 2^31 - 1, radius
+ *   outside 1 .. TCL_GUIDED_MAX_RADIUS, eps outside [1e-4f, 1] or NaN, luma other than 0 / 1, a workspace that is too small or misaligned, abar / bbar /
+ *   ws aliasing each other or an input.
+ *
+ * tcl_guided_apply_u8: abar, bbar [N,3,h,w] f32, src [N,Hc,Wc,3] uint8 (interleaved) -> out [N,Hc,Wc,3] uint8.  For output pixel (X, Y), in f32 with no
+ *   fma contraction, sx = (float)w / (float)Wc, sy likewise:
+ *     u = ((float)X + 0.5f) * sx - 0.5f;  u = min(max(u, 0), w - 1);  x0 = (int)u;  x1 = min(x0 + 1, w - 1);  fx = u - x0;      v, y0, y1, fy likewise
+ *     F(f) = t + fy * (l - t)  with  t = f[y0][x0] + fx * (f[y0][x1] - f[y0][x0]),  l = f[y1][x0] + fx * (f[y1][x1] - f[y1][x0])
+ *     out_c = min(max(rint(F(abar_c) * (float)src_c + 255.f * F(bbar_c)), 0), 255)        rint: to nearest, ties to even
+ *   The arithmetic is in 0 .. 255 units: abar = 1, bbar = 0 gives the source back byte for byte.  A lane owns four neighbouring pixels of a row and
+ *   stores their 12 bytes as three dwords where Wc % 4 == 0 and both images are 4-byte aligned, as bytes otherwise.  TCL_EINVAL, with nothing launched
+ *   or written: a null pointer, N outside 1 .. 65535, a size < 1, Hc > 65535, N * 3 * h * w or N * 3 * Hc * Wc > 2^31 - 1, out aliasing an input. */
+#define TCL_GUIDED_ROW_SEG 256
+#define TCL_GUIDED_TILE_W 64
+#define TCL_GUIDED_TILE_H 32
+#define TCL_GUIDED_MAX_RADIUS 64
+#define TCL_GUIDED_WS_PLANES 18
+size_t tcl_guided_workspace_bytes(int N, int h, int w);
+int tcl_guided_fit_f32(const float* src, const float* relit, float* abar, float* bbar, int N, int h, int w, int radius, float eps, int luma, void* ws,
+                       long ws_bytes, hipStream_t st);
+int tcl_guided_apply_u8(const float* abar, const float* bbar, const unsigned char* src, unsigned char* out, int N, int h, int w, int Hc, int Wc,
+                        hipStream_t st);
+
 /* ===================================================================== keyframe relighting (generation.keyframes); csrc/keyframe.hip */
 /* Only every K-th frame (the keys) is denoised; the gain field relit / source of the two neighbouring keys is carried to the frames in between along
  *   the chained flows.  All tensors f32 NCHW, contiguous.  Pixel centres sit at integer coordinates, p = (x, y).  fut [N,2,H,W]: fut[i] maps frame i to

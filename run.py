@@ -18,6 +18,9 @@ step gives the relit frames the source's high frequencies (texture, small text, 
 in between are their source frame times the two neighbouring keys' gain field relit / source, carried along the chained flows; stage 1 / 2 see all frames.
 [--noise_mode same|vanilla|warp] [--noise_warp_steps 0|1] (generation.noise_mode / noise_warp: {steps}): warp carries the noise from frame to frame
 along the backward optical flow -- the start noise and, with steps on (the default), the per-step noise of the SDE solver.
+[--fullres [RADIUS]] [--fullres_eps E] [--fullres_guide rgb|luma] (generation.fullres: true, a radius or {radius, eps, guide}): full-resolution output
+-- the very last step fits relit ~ a * source + b at the size of the result (a guided filter), upsamples the smooth fields a, b and applies them to the
+source's native pixels: output_fullres.npy / output_fullres.* at the source's own resolution beside output.*, which stay what they were.
 data.scene_type picks the parser (generate.py:84-95): video (VideoDataParser) or sceneflow (SceneFlowDataParser: ground-truth depth, poses and
 flows -> voxelised Unique Video Tensor ids); carla and interiornet are not built.
 
@@ -77,6 +80,8 @@ def resolve_options(config):
     o.noise_warp = r.get("noise_warp")        # the normalised block under noise_mode warp, else None
     if o.noise_warp is not None:
         g.noise_warp = Config(o.noise_warp)
+    o.fullres = r.get("fullres")              # the normalised block; None when off
+    g.fullres = None if o.fullres is None else Config(o.fullres)
     if o.normal:
         print("[INFO] generation.normal: the four ramps left / right / bottom / top are the backgrounds; generation.bg_source and "
               "generation.background_image_path are not consulted.")
@@ -141,6 +146,10 @@ def load_frames(config, o, dev):
         if o.scene_type == "video":
             parser_hr._all = parser._all          # the clip is read once
         frames_out = parser_hr.load_video(frame_ids)
+    if o.fullres is not None:                 # refused here, with the sizes, when the source is no larger than the result
+        from tc_light_amd.fullres import geometry
+        o.fullres_geo = geometry(*parser.native_size(), parser_hr.h, parser_hr.w)
+        g.fullres_size = [o.fullres_geo["Hc"], o.fullres_geo["Wc"]]
     return SimpleNamespace(parser=parser, parser_hr=parser_hr, frame_ids=frame_ids, frames=frames, frames_out=frames_out)
 
 
@@ -267,6 +276,24 @@ def save_relit_run(config, o, name, out, info, clip):
                 save_loss_curve(info["losses_unique"], path, "loss_unique_tensor")
     path = save_run(config, name, info, out, clip, then=curves)
     print(f"[INFO] {n} frames in {info['total_time']:.1f} s ({1 / config.sec_per_frame:.3f} frames/s) -> {path}")
+    return path
+
+
+def save_fullres(config, o, path, out, clip):
+    """generation.fullres, the very last step, rank 0 only (frames are independent; sharding them over the ranks is not built): the relight applied
+    to the source's native pixels.  The fit is made against what output.npy holds -- the result quantised to uint8 -- and the source frames at that
+    size, so output_fullres.* is a function of the run's written output and its source alone.  -> output_fullres.npy (uint8 [N,Hc,Wc,3]) and the
+    video of the same stem."""
+    from tc_light_amd.fullres import fullres
+    geo, b = o.fullres_geo, o.fullres
+    relit = (out.clamp(0, 1) * 255).byte().float() / 255.0
+    native = clip.parser.native_u8(clip.frame_ids)
+    full = fullres(clip.frames_out.float().contiguous(), relit.contiguous(), native, b["radius"], b["eps"], b["guide"],
+                   crop=(geo["Y0"], geo["X0"], geo["Hc"], geo["Wc"]))
+    np.save(os.path.join(path, "output_fullres.npy"), full.numpy())
+    # save_video quantises trunc(255 x): (u + 0.5) / 255 comes back as u whatever the rounding of the division
+    save_video((full.permute(0, 3, 1, 2).float() + 0.5) / 255, path, save_frame=False, stem="output_fullres", fps=clip.parser.fps, gif=False)
+    print(f"[INFO] generation.fullres: {full.shape[0]} frames of {geo['Hc']}x{geo['Wc']} -> {os.path.join(path, 'output_fullres.npy')}")
 
 
 def main(argv=None):
@@ -327,7 +354,9 @@ def main(argv=None):
                         source=clip.frames_out if o.detail is not None or kf_ids is not None else None,
                         flows=flows if kf_ids is not None else None, keyframes=kf_ids)
         if d.rank == 0:
-            save_relit_run(config, o, name, out, info, clip)
+            path = save_relit_run(config, o, name, out, info, clip)
+            if o.fullres is not None:
+                save_fullres(config, o, path, out, clip)
     if d.world > 1:
         torch.distributed.destroy_process_group()
 

@@ -12,7 +12,8 @@ import yaml
 DEFAULTS = dict(generation=dict(ip_adapter=None,                        # IP-Adapter off; else {image, scale, path} (hostlogic.check_ip_adapter)
                                 detail_transfer=None,                   # detail transfer off; else {sigma, mode, blend, channels} (hostlogic.check_detail)
                                 keyframes=None,                         # every frame denoised; else K or {interval, alpha, diff_threshold, eps} (check_keyframes)
-                                noise_warp=None),                       # read under noise_mode warp only: {steps} (check_noise_warp)
+                                noise_warp=None,                        # read under noise_mode warp only: {steps} (check_noise_warp)
+                                fullres=None),                          # full-resolution output off; else true, a radius or {radius, eps, guide} (check_fullres)
                 models=dict(ip_adapter="", image_encoder=""))           # ip-adapter_sd15.safetensors / .bin; a CLIP ViT-H/14 vision snapshot directory
 
 
@@ -130,8 +131,22 @@ def load_config(argv=None, print_config=True):
                     "warp: the noise is carried from frame to frame along the optical flow (generation.noise_mode), for a fast usage")
     ap.add_argument("--noise_warp_steps", type=int, choices=(0, 1), default=None, help="under --noise_mode warp: 1 (default) warps the per-step "
                     "noise of the SDE solver too, 0 draws it per frame as before (generation.noise_warp.steps), for a fast usage")
+    # full-resolution output: the relight applied to the source's own pixels (generation.fullres, generate.py DEFAULTS)
+    ap.add_argument("--fullres", type=int, nargs="?", const=8, default=None, metavar="RADIUS",
+                    help="write output_fullres.* at the source's own resolution: a guided-filter fit of relit ~ a * source + b at the working size, "
+                    "radius in [1, 64] (8 when left out), applied to the native frames: generation.fullres.radius, for a fast usage")
+    ap.add_argument("--fullres_eps", type=float, default=None, help="the fit's regulariser in [1e-4, 1] (generation.fullres.eps), for a fast usage")
+    ap.add_argument("--fullres_guide", choices=("rgb", "luma"), default=None, help="rgb: every channel guided by itself; luma: the source's "
+                    "luminance guides all three (generation.fullres.guide), for a fast usage")
     a = ap.parse_args(argv)
     cfg = load_yaml_chain(a.config, a.base_config)
+    if a.fullres is not None or a.fullres_eps is not None or a.fullres_guide is not None:
+        block = cfg.generation.get("fullres")
+        block = Config(dict(radius=block) if isinstance(block, int) and not isinstance(block, bool) else (block if isinstance(block, dict) else {}))
+        for key, v in (("radius", a.fullres), ("eps", a.fullres_eps), ("guide", a.fullres_guide)):
+            if v is not None:
+                block[key] = v
+        cfg.generation.fullres = block
     if a.noise_mode is not None:
         cfg.generation.noise_mode = a.noise_mode
     if a.noise_warp_steps is not None:

@@ -295,6 +295,21 @@ class VideoDataParser:
             fr = (fr + 1.0) * 127.0 / 255.0
         return fr.to(self.device)
 
+    def native_size(self):
+        """(H0, W0) of the frames as they were read."""
+        self.n_frames
+        return tuple(self._all.shape[-2:])
+
+    def native_u8(self, frame_ids=None):
+        """The frames as they were read -- no resize, no crop -- as uint8 [N,H0,W0,3] on the host (generation.fullres applies the relight to them).
+        They come from what read_frames returned and load_video cached: the file is not read a second time.  A uint8 source comes back byte for
+        byte (v / 255 in f32, times 255, rounded to nearest, is v)."""
+        self.n_frames
+        fr = self._all if frame_ids is None else self._all[list(frame_ids)]
+        if fr.min() < 0:                                         # frame directories arrive in [-1, 1] (load_image), as in load_video
+            fr = (fr + 1.0) * 127.0 / 255.0
+        return (fr * 255.0).round().clamp(0, 255).to(torch.uint8).permute(0, 2, 3, 1).contiguous()
+
     def _flow_dir(self, kind):
         """create_folder (video_dataparser.py:126-131): <video>_<name> beside a file, <dir>/<name> inside a frame directory."""
         name = f"{kind}_flow_{self.flow_model}"

@@ -99,6 +99,11 @@ DEFAULTS = dict(  # configs/tclight_default.yaml (generation / post_opt sections
     #   moves, following the surface where it moves, fresh where something is uncovered, white and unit-variance in every frame (noisewarp.py:
     #   tcl_noise_warp_count, tcl_noise_warp_apply_f32); steps: the per-step noise of the SDE solver is a new chain over the same flows too.
     #   noise_mode same | vanilla: nothing of it is consulted and every path, launch and draw is what it was.
+    fullres=None,
+    # ^ full-resolution output: true, a radius or {radius, eps, guide: rgb | luma} (HL.check_fullres).  Not a step of the Generator: run.py, behind
+    #   everything else, fits relit ~ a * source + b at the size of the result and applies the upsampled fields to the source's native pixels
+    #   (fullres.py: tcl_guided_fit_f32, tcl_guided_apply_u8) -> output_fullres.*.  The Generator only checks the key with the others.
+    #   None (default): nothing of it is consulted and every path is what it was.
     max_tokens_per_pass=None)
     # ^ level-0 tokens (samples x pixels) one block-major UNet pass may carry; longer chunk lists are split into consecutive groups.  None:
     #   TCL_MAX_TOKENS_PER_PASS (read when the Generator is built), else min(16 M, 80 % of the device's free memory / 10.5 KB) -- a pass peaks at
@@ -130,6 +135,7 @@ class Generator:
         cfg.update({k: r[k] for k in HL.RESOLVED_KEYS})
         cfg["keyframes"] = r.get("keyframes")      # the normalised block, None when off (interval 1 included)
         cfg["noise_warp"] = r.get("noise_warp")    # the normalised block, None unless noise_mode warp
+        cfg["fullres"] = r.get("fullres")          # the normalised block, None when off; run.py's step, checked here with the others
         self.cfg = SimpleNamespace(**cfg)
         self.fbc, self.light, self.img2img, self.highres = r["fbc"], r["light"], r["img2img"], r["highres"]
         self.normal_sides = r["normal_sides"]                                      # () unless generation.normal

@@ -522,6 +522,49 @@ def check_noise_warp(noise_mode, block=None, keyframes=None, highres_scale=1.0, 
     return out
 
 
+FULLRES_GUIDES = ("rgb", "luma")         # generation.fullres.guide, in the order of the kernel's `luma` argument (0 / 1)
+FULLRES_RADIUS = (1, 64)                 # TCL_GUIDED_MAX_RADIUS
+FULLRES_EPS = (1e-4, 1.0)                # the floor of the fit's denominator: the kernel's error bound scales like 1 / eps
+FULLRES_DEFAULTS = dict(radius=8, eps=1e-3, guide="rgb")
+
+
+def check_fullres(block, normal=False, iclight_model="fc", background_cond=False, scene_type="video"):
+    """generation.fullres: None or false (off: nothing else is looked at), true (the defaults), a bare integer radius or {radius, eps, guide: rgb |
+    luma} -> the block with the defaults filled in (FULLRES_DEFAULTS).  Each fault is a ValueError naming its key: an unknown key, a radius that is
+    no integer in FULLRES_RADIUS, an eps outside FULLRES_EPS, an unknown guide.  Refused by both key names: generation.normal (its outputs are
+    ratios of four relights), generation.iclight_model fbc and background_cond (the new background is not in the source's pixels, so no gain on them
+    reproduces it), and data.scene_type sceneflow (its parser reads the frames its own way: out of scope, not impossible)."""
+    if block is None or block is False:
+        return None
+    if block is True:
+        block = {}
+    elif isinstance(block, int):
+        block = dict(radius=block)
+    if not isinstance(block, dict) or any(k not in FULLRES_DEFAULTS for k in block):
+        raise ValueError(f"generation.fullres {block!r}: expected null, true, an integer (radius) or {{radius: <int in [{FULLRES_RADIUS[0]}, "
+                         f"{FULLRES_RADIUS[1]}]>, eps: <float in [{FULLRES_EPS[0]}, {FULLRES_EPS[1]}]>, guide: rgb | luma}}")
+    out = dict(FULLRES_DEFAULTS, **block)
+    radius, eps, guide = out["radius"], out["eps"], out["guide"]
+    if isinstance(radius, bool) or not isinstance(radius, int) or not FULLRES_RADIUS[0] <= radius <= FULLRES_RADIUS[1]:
+        raise ValueError(f"generation.fullres.radius {radius!r}: expected an integer in [{FULLRES_RADIUS[0]}, {FULLRES_RADIUS[1]}]")
+    if not _is_number(eps) or not FULLRES_EPS[0] <= float(eps) <= FULLRES_EPS[1]:
+        raise ValueError(f"generation.fullres.eps {eps!r}: expected a number in [{FULLRES_EPS[0]}, {FULLRES_EPS[1]}]")
+    if not isinstance(guide, str) or guide.lower() not in FULLRES_GUIDES:
+        raise ValueError(f"generation.fullres.guide {guide!r}: expected one of {' | '.join(FULLRES_GUIDES)}")
+    out["eps"], out["guide"] = float(eps), guide.lower()
+    if normal:
+        raise ValueError("generation.fullres together with generation.normal is not supported: the normal's outputs are ratios of four relights, "
+                         "not a relight")
+    if (iclight_model is not None and str(iclight_model).lower() == "fbc") or background_cond:
+        key = "generation.background_cond" if background_cond else "generation.iclight_model fbc"
+        raise ValueError(f"generation.fullres together with {key} is not supported: the new background is not in the source's pixels, so no "
+                         "gain and offset on them gives it back")
+    if str(scene_type).lower() == "sceneflow":
+        raise ValueError("generation.fullres together with data.scene_type sceneflow is not supported: its parser reads the frames its own way "
+                         "(out of scope, not impossible)")
+    return out
+
+
 # what resolve_generation normalises: run.py writes these back into the configuration (config.yaml records them), Generator into its cfg
 RESOLVED_KEYS = ("init_latent", "init_strength", "highres_scale", "highres_denoise", "iclight_model", "bg_source", "light_path", "prompt_path")
 
@@ -534,7 +577,7 @@ def resolve_generation(cfg):
     whole n_timesteps unless the start is an img2img one -- and schedule_highres (the second pass's; None when it is off).  generation.keyframes
     (check_keyframes; cfg may carry data.scene_type as scene_type) is checked here too; its normalised block is in the result as "keyframes" only
     when the key is on (interval > 1), so a run without it resolves to exactly what it did; likewise "noise_warp" (check_noise_warp), in the result
-    under noise_mode warp only."""
+    under noise_mode warp only, and "fullres" (check_fullres; cfg may carry data.scene_type as scene_type), in the result only when the key is on."""
     n, normal, bg_cond = cfg["n_timesteps"], cfg["normal"], bool(cfg.get("background_cond"))
     r = {}
     r["init_latent"], r["init_strength"] = check_init(cfg["init_latent"], cfg["init_strength"], n)
@@ -550,6 +593,9 @@ def resolve_generation(cfg):
     noise_warp = check_noise_warp(cfg.get("noise_mode"), cfg.get("noise_warp"), keyframes, r["highres_scale"], bool(normal))
     if noise_warp is not None:
         r["noise_warp"] = noise_warp
+    fullres = check_fullres(cfg.get("fullres"), bool(normal), r["iclight_model"], bg_cond, cfg.get("scene_type", "video"))
+    if fullres is not None:
+        r["fullres"] = fullres
     r["fbc"], r["light"], r["highres"] = r["iclight_model"] == "fbc", r["light_path"] is not None, r["highres_scale"] != 1.0
     r["img2img"] = r["init_latent"] != "none" or (r["light"] and not r["fbc"])      # fc: the path's ramps are the start
     r["schedule"] = img2img_schedule(n, r["init_strength"]) if r["img2img"] else (n, 0, n)
